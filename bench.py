@@ -17,7 +17,11 @@ BASELINE.json configs[1]: Conformer-small (12 x 256d, 4 heads, ff 1024), batch 3
 GPU (weak scaling: per-GPU batch fixed).  Random-init weights (torch.manual_seed(0)), synthetic
 N(0, 0.1^2) waveforms.
 
-One JSON line on rank 0 carries the throughput and, at N = 1: `roofline` (the dominant MFMA kernel family
+A plain run sets up, warms up, times the K steps and prints one JSON line on rank 0 with the throughput (`value`) and
+`ms_per_step`; `--dump-outputs DIR` also writes what the last timed step computed as DIR/<name>.npy (float32 / float64),
+on inputs that are the same from run to run, so that two builds can be compared output for output.
+
+With `--full` the line also carries, at N = 1: `roofline` (the dominant MFMA kernel family
 measured live with HIP events around every launch, HBM traffic from two `rocprofv3 --pmc` passes of this
 same script and - `rocprofv3_*` fields - the un-bracketed kernel table of a nested `rocprofv3 --kernel-trace
 --stats` run of the same loop), `cpu_baseline` (the oracle port on this box's host cores + the reference figure it stands in
@@ -28,8 +32,9 @@ traffic of its dominant one), `encoder_ebranchformer_b32` (the E-Branchformer en
 `beam` (configs[2] with the roofline of the search and `bf16_vs_oracle`: per-token error, best-score loss beside the
 oracle search's own path noise, token edit distance), `beam_cfg3_per_gpu` (configs[3]'s per-GPU batch on one GPU,
 with `bf16_vs_oracle`; the beam legs with eight (configs[2]) and four (configs[3] per GPU) joint searches in flight, a host thread each: `SearchLanes`) and `stream` (configs[4] + the 40 ms-per-call
-stress case); `box_state` (three probes of the pool's slow state: a slow lease is labelled, not read as a regression).  `--quick`
-keeps only the main line, `roofline` and `cpu_baseline`.
+stress case); `box_state` (three probes of the pool's slow state: a slow lease is labelled, not read as a regression).  `--full
+--quick` keeps only the main line, `roofline` and `cpu_baseline`.  `--workload beam` / `stream` with `--full` add their own
+sub-objects (the search's per-label-step figures and traffic, the CPU baseline; the many-stream ticks).
 """
 import argparse
 import csv
@@ -48,6 +53,7 @@ REPO = Path(__file__).resolve().parent
 sys.path.insert(0, str(REPO))
 os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
 
+import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 AUDIO_SEC = 10.0
@@ -264,12 +270,13 @@ def beam_vs_oracle(model, enc_row, hyps, beam, ctc_weight, noise_seeds=4, noise_
     return out
 
 
-def run_stream(dtype, steps, warmup, chunk=10240, stream_beam=1, cpu_base=True):
+def run_stream(dtype, steps, warmup, chunk=10240, stream_beam=1, cpu_base=True, dump=None):
     """BASELINE.json configs[4]: streaming contextual-block Conformer (aishell recipe shape: 12 x
     256d, 4 heads, ff 2048, conv k 15, block 40 / hop 16 / look-ahead 16), one audio stream fed in
     chunks of `chunk` samples (10 240 = 640 ms, the reference's sim_chunk_length; 640 = the 40 ms-per-call
     stress case) through Speech2TextStreaming (HIP frontend -> hipGraph-captured encoder step ->
-    incremental greedy CTC).  A step = one 10 s utterance."""
+    incremental greedy CTC).  A step = one 10 s utterance.  `dump` (a dict): filled with the n-best token ids and scores
+    of the last timed step (--dump-outputs)."""
     import yaml
 
     from espnet_amd.bin.asr_inference_streaming import Speech2TextStreaming
@@ -311,6 +318,9 @@ def run_stream(dtype, steps, warmup, chunk=10240, stream_beam=1, cpu_base=True):
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     lats.sort()
+    if dump is not None:
+        dump["tokens"], dump["token_lens"] = padded_tokens([r[2] for r in out])
+        dump["scores"] = [float(r[3].score) for r in out]
     res = {"value": round(AUDIO_SEC * steps / elapsed, 1), "unit": "audio-s/s", "steps": steps, "warmup": warmup,
            "ms_per_step": round(elapsed / steps * 1e3, 3), "dtype": "bf16" if dtype == "bfloat16" else "f32",
            "config": {"workload": "BASELINE.json configs[4]: streaming contextual_block_conformer (12x256d, "
@@ -410,9 +420,12 @@ def run_stream_batch(dtype, n_streams, steps, warmup, chunk=10240, groups=1, gra
 def main_stream(args):
     assert int(os.environ.get("WORLD_SIZE", "1")) == 1, "--workload stream is single-stream"
     torch.cuda.set_device(0)
+    dump = {} if args.dump_outputs else None
     res = run_stream(args.dtype, args.steps, args.warmup, args.stream_chunk, args.stream_beam,
-                     cpu_base=not args.no_cpu_baseline)
-    if args.stream_beam <= 1 and args.stream_chunk == 10240:
+                     cpu_base=args.full and not args.no_cpu_baseline, dump=dump)
+    if dump is not None:
+        dump_outputs(args.dump_outputs, dump)
+    if args.full and args.stream_beam <= 1 and args.stream_chunk == 10240:
         res["batch32"] = run_stream_batch(args.dtype, 32, max(1, args.steps), 1)
         res["batch128"] = run_stream_batch(args.dtype, 128, max(1, min(args.steps, 4)), 1)
         res["batch32_hipgraph"] = run_stream_batch(args.dtype, 32, max(1, args.steps), 1, graph=True)
@@ -626,6 +639,39 @@ def _edit_distance(a, b):
     return prev[-1]
 
 
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs: all files together
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: `arrays` ({name: tensor or array}) as path/<name>.npy, float arrays in float32, integer ones
+    (token ids, lengths) in float64, where they are exact."""
+    out = {}
+    for name, a in arrays.items():
+        if isinstance(a, torch.Tensor):
+            a = a.detach().cpu()
+            a = a.float() if a.is_floating_point() and a.dtype != torch.float64 else a.double()
+            a = a.numpy()
+        else:
+            a = np.asarray(a)
+            a = a.astype(np.float32 if a.dtype.kind == "f" and a.dtype != np.float64 else np.float64)
+        out[name] = a
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise ValueError(f"--dump-outputs: {total} bytes, more than {DUMP_LIMIT_BYTES}")
+    os.makedirs(path, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(path, f"{name}.npy"), a)
+
+
+def padded_tokens(token_lists):
+    """Token-id lists -> (n, longest) float64 array padded with -1, and the lengths."""
+    lens = np.array([len(t) for t in token_lists], dtype=np.float64)
+    a = np.full((len(token_lists), max([1] + [len(t) for t in token_lists])), -1.0)
+    for i, t in enumerate(token_lists):
+        a[i, : len(t)] = t
+    return a, lens
+
+
 def timed_loop(step, steps, warmup, barrier, finish=None):
     with torch.no_grad():
         for _ in range(warmup):
@@ -658,8 +704,9 @@ def decoder_step_bytes(model, B, W, T, NC, steps, es):
     return w + mem + cache + logits + ctc
 
 
-def run_beam(args, dev, B, beam, steps, warmup, cpu_base, want_traffic=True, want_oracle=False):
-    """configs[2] / configs[3]'s per-GPU batch: Conformer-large + 6-layer decoder, joint CTC/attention beam search."""
+def run_beam(args, dev, B, beam, steps, warmup, cpu_base, want_traffic=True, want_oracle=False, instrument=True):
+    """configs[2] / configs[3]'s per-GPU batch: Conformer-large + 6-layer decoder, joint CTC/attention beam search.
+    instrument: one more (untimed) step behind the timed ones for the `search` object (one search alone on the chip)."""
     from espnet_amd import distributed as D
     from espnet_amd.nets.batch_beam_search import build_beam_search
     from espnet_amd.tasks.asr import ASRTask
@@ -754,13 +801,17 @@ def run_beam(args, dev, B, beam, steps, warmup, cpu_base, want_traffic=True, wan
         elapsed = time.perf_counter() - t0
         if lanes is not None:
             lanes.close()
-        step(instrument=True)
+        if instrument:
+            step(instrument=True)
     n_tok = sum(len(t) for t, _ in hyps[-B:])
+    res = {"model": model, "elapsed": elapsed, "tokens": n_tok, "hyps": hyps, "steps_this_rank": len(mine)}
+    if not instrument:
+        return res
     es = 2 if args.dtype == "bfloat16" else 4
     S = bs.pre_beam_size if bs.do_pre_beam else VOCAB
     n_steps = t_search[1]
     per_step = decoder_step_bytes(model, B, beam, T, S + 1, n_steps, es)
-    res = {"model": model, "elapsed": elapsed, "tokens": n_tok, "steps_this_rank": len(mine),
+    res.update({
            "search": {"ms_per_search_step": round(t_search[0] / max(1, n_steps) * 1e3, 4),
                       "search_steps_per_utt_batch": n_steps, "steps_per_s": round(n_steps / t_search[0], 1),
                       "rows": B * beam,
@@ -774,7 +825,7 @@ def run_beam(args, dev, B, beam, steps, warmup, cpu_base, want_traffic=True, wan
                                    "algorithmic_mb_per_search_step": round(per_step / 1e6, 2),
                                    "what": "decoder weights + memory K/V + self-attention cache + logits + CTC "
                                            "columns and forward variables per label step (bench.py "
-                                           "decoder_step_bytes), over the wall time of search_batch"}}}
+                                           "decoder_step_bytes), over the wall time of search_batch"}}})
     inner = os.environ.get("ESPNET_AMD_BENCH_INNER") == "1"
     if (want_traffic and int(os.environ.get("WORLD_SIZE", "1")) == 1 and not inner and not args.no_traffic
             and not getattr(args, "quick", False)):
@@ -1139,9 +1190,14 @@ def box_state(dev, roofline):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=2000,
-                    help="timed steps (default: ~3 s of the greedy workload, long enough for coarse GPU-busy sampling)")
-    ap.add_argument("--warmup", type=int, default=50)
+    ap.add_argument("--steps", type=int, default=None,
+                    help="timed steps (default: greedy 2000, ~3 s, long enough for coarse GPU-busy sampling; beam 12; stream 20)")
+    ap.add_argument("--warmup", type=int, default=None, help="untimed steps before them (default: greedy 50, beam 1, stream 2)")
+    ap.add_argument("--full", action="store_true",
+                    help="also every other measurement and check of the line: roofline, traffic, CPU baselines, the "
+                         "sub-legs (other precisions, models, workloads, configurations) and the oracle comparisons")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them computed as DIR/<name>.npy")
     ap.add_argument("--batch", type=int, default=None, help="utterances per GPU per step")
     ap.add_argument("--model", default=None, choices=sorted(CONFIGS))
     ap.add_argument("--workload", default="greedy", choices=["greedy", "beam", "stream"],
@@ -1163,7 +1219,7 @@ def main():
     ap.add_argument("--no-lane-threads", action="store_true",
                     help="beam workload: ONE host thread drives every search in flight (round 6's first form; saturates at two lanes) "
                          "instead of a host thread per lane (SearchLanes(threaded=True))")
-    ap.add_argument("--quick", action="store_true", help="main line + roofline + cpu_baseline only")
+    ap.add_argument("--quick", action="store_true", help="with --full: main line + roofline + cpu_baseline only")
     ap.add_argument("--dist-debug-one-gpu", action="store_true",
                     help="developer check of the multi-rank control flow on a ONE-GPU box: every rank uses "
                          "cuda:0 and the collectives go through gloo on host copies (not a measurement)")
@@ -1172,16 +1228,16 @@ def main():
     ap.add_argument("--no-traffic", action="store_true", help="skip the rocprofv3 --pmc passes (roofline.traffic null)")
     args = ap.parse_args()
     inner = os.environ.get("ESPNET_AMD_BENCH_INNER") == "1"
+    # a stream step is a whole 10 s utterance fed chunk by chunk, a beam step ~100x a greedy one
+    steps, warmup = {"greedy": (2000, 50), "beam": (12, 1), "stream": (20, 2)}[args.workload]
+    args.steps = steps if args.steps is None else args.steps
+    args.warmup = warmup if args.warmup is None else args.warmup
     if args.workload == "stream":
-        if args.steps == 2000 and args.warmup == 50:
-            args.steps, args.warmup = 20, 2  # a step is a whole 10 s utterance fed chunk by chunk
         return main_stream(args)
     if args.model is None:
         args.model = "small" if args.workload == "greedy" else "large"
     if args.batch is None:
         args.batch = 32 if args.workload == "greedy" else 16
-    if args.workload == "beam" and args.steps == 2000 and args.warmup == 50:
-        args.steps, args.warmup = 12, 1  # a beam step is ~100x a greedy one
     if args.in_flight is None:
         args.in_flight = 4 if args.workload == "beam" else 2
     args.lane_threads = not args.no_lane_threads
@@ -1237,8 +1293,15 @@ def main():
     extras = {}
     if args.workload == "beam":
         r = run_beam(args, dev, B, args.beam, args.steps, args.warmup,
-                     cpu_base=(rank == 0 and world == 1 and not args.no_cpu_baseline))
+                     cpu_base=(args.full and rank == 0 and world == 1 and not args.no_cpu_baseline),
+                     want_traffic=args.full, instrument=args.full)
         model, elapsed, n_tok = r.pop("model"), r.pop("elapsed"), r.pop("tokens")
+        if rank == 0 and args.dump_outputs:
+            # the hypotheses of the last work unit (B utterances; every unit decodes the same batch)
+            tok, tlen = padded_tokens([t for t, _ in r["hyps"][-B:]])
+            dump_outputs(args.dump_outputs, {"tokens": tok, "token_lens": tlen,
+                                             "scores": [s for _, s in r["hyps"][-B:]]})
+        del r["hyps"]
         extras = r
         step_plain = None
     else:
@@ -1256,9 +1319,13 @@ def main():
         feeder = (HostFeeder(wav_host, dev, nbuf=(pipe.depth if pipe is not None else 1) + 1,
                              beside=pipe.streams if pipe is not None else None) if args.h2d else None)
 
+        last = {}
+
         def step_plain(src=None, out=None):
             st = model.encode_device(wav if src is None else src, lens)
-            return model.greedy_ctc_device(st, out=out)
+            r = model.greedy_ctc_device(st, out=out)
+            last["st"], last["ids"] = st, r[0]  # (what --dump-outputs writes of the last timed step)
+            return r
 
         def body(tok_v, len_v):
             if feeder is not None:
@@ -1295,6 +1362,16 @@ def main():
         elapsed = timed_loop(step, args.steps, args.warmup, barrier, finish)
         n_tok = int(sink.last[1].sum()) if sink.last is not None else 0
         assert rank != 0 or sink.delivered == args.steps + args.warmup, (sink.delivered, args.steps, args.warmup)
+        if rank == 0 and args.dump_outputs:
+            st = last["st"]
+            t = max(st.olens)
+            ids, counts = sink.last[0].copy(), sink.last[1]
+            ids[np.arange(ids.shape[1])[None, :] >= counts[:, None]] = -1  # (the record's tail past the count is not output)
+            # the encoder output of as many utterances as fit in half the dump limit (all of them at the default sizes)
+            enc = st.enc_out[:, :t]
+            n_enc = max(1, min(B, (DUMP_LIMIT_BYTES // 2) // (enc[0].numel() * 4)))
+            dump_outputs(args.dump_outputs, {"tokens": ids, "token_lens": counts, "ctc_ids": last["ids"][:, :t],
+                                             "enc_out": enc[:n_enc]})
     el = torch.tensor([elapsed], dtype=torch.float64, device="cpu" if args.dist_debug_one_gpu else dev)
     if world > 1:
         dist.all_reduce(el, op=dist.ReduceOp.MAX)
@@ -1342,7 +1419,7 @@ def main():
                          "same loop with --in-flight 1"} if pipe is not None else {"n": 1})
         out.update(extras)
     # ---- roofline of the MFMA kernel families: HIP events around every launch (on the launch stream)
-    if rank == 0 and not args.no_roofline and step_plain is not None:
+    if rank == 0 and args.full and not args.no_roofline and step_plain is not None:
         nprof = max(1, min(args.steps, 5))
         fam = profile_families(step_plain, nprof)
         bracket_us = event_bracket_us(dev, args.dtype)
@@ -1366,11 +1443,11 @@ def main():
         out["roofline"] = roofline_object(fam, nprof, bracket_us, MFMA_PEAK_TFLOPS[args.dtype], elapsed / args.steps,
                                           traffic, traffic_note, rp, rp_note, algorithmic_bytes_per_launch=alg)
         out["box_state"] = box_state(dev, out["roofline"])
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.workload == "greedy":
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline and args.workload == "greedy":
         out["cpu_baseline"] = cpu_baseline(model)
 
     # ---- the other rows of the measurement contract, as sub-objects of the one line (N = 1 only) -------------
-    if rank == 0 and world == 1 and args.workload == "greedy" and not args.quick and not inner:
+    if rank == 0 and world == 1 and args.workload == "greedy" and args.full and not args.quick and not inner:
         only = [x for x in os.environ.get("BENCH_ONLY_LEGS", "").split(",") if x]  # developer probe: run these sub-legs only
 
         def guarded(name, fn):
@@ -1577,6 +1654,7 @@ def main():
                              want_traffic=cpu,  # counters for the configs[2] leg only
                              want_oracle=not args.no_cpu_baseline)  # ... the oracle check of utterance 0 for both
                 r.pop("model")
+                r.pop("hyps")
                 el_, tok_ = r.pop("elapsed"), r.pop("tokens")
                 torch.cuda.empty_cache()
                 if cpu and not args.no_cpu_baseline:
@@ -1587,6 +1665,7 @@ def main():
                         a3.dtype, a3.in_flight = "float32", 1
                         r3 = run_beam(a3, dev, Bb, 10, 1, 1, cpu_base=False, want_traffic=False, want_oracle=True)
                         r3.pop("model")
+                        r3.pop("hyps")
                         e3 = r3.pop("elapsed")
                         r["f32_mode"] = {"value": round(Bb * AUDIO_SEC / e3, 1), "unit": "audio-s/s", "ms_per_step": round(e3 * 1e3, 2),
                                          "ms_per_search_step": r3["search"]["ms_per_search_step"],

@@ -484,3 +484,29 @@ def test_dynamic_dispatch_with_lanes_two_ranks():
         assert [s for _, s in got[r][0]] == pytest.approx(want_s)
     assert sorted(got[0][1] + got[1][1]) == list(range(n_units))  # every unit decoded exactly once
     assert len(got[0][1]) > len(got[1][1]) > 0  # the rank whose units take a quarter of the time took more of them
+
+def test_bench_dump_outputs_writes_float_arrays_within_the_limit(tmp_path):
+    """`bench.py --dump-outputs DIR`: every array as DIR/<name>.npy, floats in float32 and token ids / lengths in float64
+    (exact), hypotheses padded with -1; more than the 64 MB limit is refused before anything is written."""
+    import importlib.util
+    from pathlib import Path
+
+    import numpy as np
+    import torch
+
+    spec = importlib.util.spec_from_file_location("bench_under_test", Path(__file__).resolve().parent.parent / "bench.py")
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    tok, lens = bench.padded_tokens([[5, 4999], [], [7]])
+    enc = torch.randn(2, 3, 4).to(torch.bfloat16)
+    bench.dump_outputs(tmp_path / "d", {"tokens": tok, "token_lens": lens, "ids": torch.arange(6, dtype=torch.int32),
+                                        "enc_out": enc, "scores": [1.5, -2.25]})
+    got = {p.stem: np.load(p) for p in (tmp_path / "d").iterdir()}
+    assert sorted(got) == ["enc_out", "ids", "scores", "token_lens", "tokens"]
+    assert got["tokens"].dtype == np.float64 and got["tokens"].tolist() == [[5, 4999], [-1, -1], [7, -1]]
+    assert got["token_lens"].tolist() == [2, 0, 1] and got["ids"].dtype == np.float64
+    assert got["enc_out"].dtype == np.float32 and np.array_equal(got["enc_out"], enc.float().numpy())
+    assert got["scores"].dtype == np.float64
+    with pytest.raises(ValueError, match="more than"):
+        bench.dump_outputs(tmp_path / "big", {"x": np.zeros(bench.DUMP_LIMIT_BYTES // 4 + 1, np.float32)})
+    assert not (tmp_path / "big").exists()

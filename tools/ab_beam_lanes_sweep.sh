@@ -7,6 +7,6 @@ print('value', j.get('value'), 'ms_per_step', j.get('ms_per_step'), 'ms_per_sear
 for B in 16; do
  for IF in 8 12 16 8 12; do
   echo "== beam B=$B threaded lanes=$IF" | tee -a $out/ab.txt
-  BENCH_LANE_THREADS=1 timeout 300 python bench.py --workload beam --batch $B --steps 24 --warmup 1 --quick --no-cpu-baseline --no-traffic --in-flight $IF 2>$out/err_beam_${B}_$IF.txt | tail -1 | pr | tee -a $out/ab.txt
+  BENCH_LANE_THREADS=1 timeout 300 python bench.py --full --workload beam --batch $B --steps 24 --warmup 1 --quick --no-cpu-baseline --no-traffic --in-flight $IF 2>$out/err_beam_${B}_$IF.txt | tail -1 | pr | tee -a $out/ab.txt
  done
 done

@@ -12,7 +12,7 @@ for B in 64 32 16; do
   for V in "1 0" "0 16" "0 32" "1 0" "0 16" "0 32"; do
     set -- $V
     echo "== B=$B ESPNET_AMD_DEC_FFN_SPLIT=$1 ESPNET_AMD_DEC_FFN_ROWS=$2" | tee -a $out/ab.txt
-    ESPNET_AMD_DEC_FFN_SPLIT=$1 ESPNET_AMD_DEC_FFN_ROWS=$2 timeout 200 python bench.py --workload beam --batch $B --steps 2 --warmup 1 --quick --no-cpu-baseline --no-traffic --in-flight 1 2>$out/err_${B}_$1_$2.txt | tail -1 | pr | tee -a $out/ab.txt
+    ESPNET_AMD_DEC_FFN_SPLIT=$1 ESPNET_AMD_DEC_FFN_ROWS=$2 timeout 200 python bench.py --full --workload beam --batch $B --steps 2 --warmup 1 --quick --no-cpu-baseline --no-traffic --in-flight 1 2>$out/err_${B}_$1_$2.txt | tail -1 | pr | tee -a $out/ab.txt
   done
 done
 cd /tmp && export TMPDIR=/tmp

@@ -11,6 +11,6 @@ done
 for E in 1 4; do
  for B in 16 64; do
   echo "== beam B=$B lanes=4 threaded BENCH_ENC_IN_FLIGHT=$E" | tee -a $out/ab.txt
-  BENCH_ENC_IN_FLIGHT=$E BENCH_LANE_THREADS=1 timeout 300 python bench.py --workload beam --batch $B --steps 12 --warmup 1 --quick --no-cpu-baseline --no-traffic --in-flight 4 2>$out/err_beam_${B}_$E.txt | tail -1 | pr | tee -a $out/ab.txt
+  BENCH_ENC_IN_FLIGHT=$E BENCH_LANE_THREADS=1 timeout 300 python bench.py --full --workload beam --batch $B --steps 12 --warmup 1 --quick --no-cpu-baseline --no-traffic --in-flight 4 2>$out/err_beam_${B}_$E.txt | tail -1 | pr | tee -a $out/ab.txt
  done
 done

@@ -1,7 +1,7 @@
 set -u
 out=gpurun_out/r06ak; mkdir -p $out
 timeout 120 python tools/null_stream_probe.py 2>&1 | grep -v amdgpu.ids | tee $out/null_stream_probe.txt
-(time timeout 600 python bench.py 2>$out/bench_default.err | tail -1 > $out/bench_default.json) 2>&1 | tail -4
+(time timeout 600 python bench.py --full 2>$out/bench_default.err | tail -1 > $out/bench_default.json) 2>&1 | tail -4
 python - $out/bench_default.json <<'PY'
 import json, sys
 j = json.load(open(sys.argv[1]))

@@ -41,7 +41,7 @@ case "$what" in
     for v in new r05 new r05; do
       if [ $v = r05 ]; then export ESPNET_AMD_STREAM_FFN_SPLIT=1 ESPNET_AMD_STREAM_FUSED_MIN=8; else unset ESPNET_AMD_STREAM_FFN_SPLIT ESPNET_AMD_STREAM_FUSED_MIN; fi
       echo -n "$v: "
-      timeout 600 python bench.py --workload stream --no-cpu-baseline --steps 6 --warmup 2 2>/dev/null < /dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['value'], 'audio-s/s one stream, call median', d['config']['call_latency_ms_median'], 'ms; batch32', d.get('batch32',{}).get('value'), 'tick', d.get('batch32',{}).get('tick_latency_ms_median'), 'batch128', d.get('batch128',{}).get('value'))"
+      timeout 600 python bench.py --full --workload stream --no-cpu-baseline --steps 6 --warmup 2 2>/dev/null < /dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['value'], 'audio-s/s one stream, call median', d['config']['call_latency_ms_median'], 'ms; batch32', d.get('batch32',{}).get('value'), 'tick', d.get('batch32',{}).get('tick_latency_ms_median'), 'batch128', d.get('batch128',{}).get('value'))"
     done 2>&1 | tee "$out/ab_ffn_split.txt"
     unset ESPNET_AMD_STREAM_FFN_SPLIT ESPNET_AMD_STREAM_FUSED_MIN ;;
   r06u)  # round 6: kernel tables of the streaming call with the split FFN: one stream (hipGraph step) and the 32-stream tick
@@ -155,7 +155,7 @@ PY
     f=$(find "$out/search640_stats" -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && head -40 "$f" | cut -c1-220 > "$out/search640_kernel_stats_head.txt" ;;
   sweep640)  # label step at 640 rows under the dispatch switches that were tuned at 160 rows
     B64=${B64:-64}
-    bl() { timeout 200 python bench.py --workload beam --batch $B64 --steps 1 --warmup 1 --no-cpu-baseline --no-traffic 2>/dev/null < /dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['value'], 'audio-s/s,', d['search']['ms_per_search_step'], 'ms per label step')"; }
+    bl() { timeout 200 python bench.py --full --workload beam --batch $B64 --steps 1 --warmup 1 --no-cpu-baseline --no-traffic 2>/dev/null < /dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['value'], 'audio-s/s,', d['search']['ms_per_search_step'], 'ms per label step')"; }
     export B64
     for e in "" "ESPNET_AMD_SA_GROUP=1" "ESPNET_AMD_SA_GROUP=2" "ESPNET_AMD_SA_GROUP=3" "ESPNET_AMD_SA_GROUP=4" "ESPNET_AMD_MID_TILE=24" "ESPNET_AMD_MID_TILE=21" "ESPNET_AMD_MID_TILE=12" "ESPNET_AMD_SA_GROUP=4 ESPNET_AMD_MID_TILE=24" "ESPNET_AMD_SA_GROUP=2 ESPNET_AMD_MID_TILE=24" ""; do
       echo -n "[B=$B64 $e] "; env $e bash -c "$(declare -f bl); bl"
@@ -163,7 +163,7 @@ PY
   tree-sa)  # round 5: decoder self-attention over the union of a beam's ancestors (A/B: ESPNET_AMD_NO_SA_TREE=1)
     echo "== kernel test"; (timeout 300 python -m pytest -q -x tests/test_gpu_search.py -k "self_attention" 2>&1 | tail -5) | tee "$out/pytest_kernel.txt"
     echo "== search tests"; (timeout 600 python -m pytest -q -x tests/test_gpu_search.py tests/test_gpu_online_search.py -k "bf16 or peaked or batched or structure or very_short" 2>&1 | tail -4) | tee "$out/pytest_search.txt"
-    bl() { timeout 200 python bench.py --workload beam --batch $1 --steps 1 --warmup 1 --no-cpu-baseline --no-traffic 2>/dev/null < /dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['value'], 'audio-s/s,', d['search']['ms_per_search_step'], 'ms per label step')"; }
+    bl() { timeout 200 python bench.py --full --workload beam --batch $1 --steps 1 --warmup 1 --no-cpu-baseline --no-traffic 2>/dev/null < /dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['value'], 'audio-s/s,', d['search']['ms_per_search_step'], 'ms per label step')"; }
     for b in 64 16; do for v in 0 1 0 1; do
       if [ $v = 1 ]; then export ESPNET_AMD_NO_SA_TREE=1; else unset ESPNET_AMD_NO_SA_TREE; fi
       echo -n "[B=$b no_tree=$v] "; bl $b
@@ -177,12 +177,12 @@ PY
        -k "peaked or bf16 or midmargin or structure or lm_scorer_bf16 or restarts" > "$out/pytest_parity_full.txt" 2>&1; grep -E "^\[|passed|failed|Error|assert " "$out/pytest_parity_full.txt" | cut -c1-260 | tail -60) 2>&1 | tee "$out/pytest_parity.txt"
     echo "== large encoder B=64: kernel stats"
     stats "$out/prof_large" python "$R/bench.py" --model large --batch 64 --quick --no-traffic --no-roofline --no-cpu-baseline --in-flight 1 --steps 20 --warmup 3
-    echo "== default bench"; (time timeout 900 python bench.py 2>"$out/bench_default.err" < /dev/null | tee "$out/bench_default.json" | cut -c1-300) 2>&1 | tail -5 ;;
+    echo "== default bench"; (time timeout 900 python bench.py --full 2>"$out/bench_default.err" < /dev/null | tee "$out/bench_default.json" | cut -c1-300) 2>&1 | tail -5 ;;
   r04b)     # stream pool, RecordRing / dynamic dispatch on the GPU (two ranks on one GPU through gloo), parity prints, GEMM stage A/B
     echo "== stream pool + new parity"
     (time timeout 900 python -m pytest -q -s tests/test_gpu_streaming.py tests/test_gpu_search.py tests/test_gpu_online_search.py tests/test_gpu_fullsize.py tests/test_gpu_e2e.py \
        -k "pool or peaked or bf16 or midmargin or structure or lm_scorer_bf16 or restarts or batch_call" > "$out/pytest_parity_full.txt" 2>&1; grep -E "^\[|passed|failed|Error|assert " "$out/pytest_parity_full.txt" | cut -c1-260 | tail -60) 2>&1 | tee "$out/pytest_parity.txt"
-    echo "== bench quick (RecordRing path)"; timeout 300 python bench.py --quick --no-traffic --no-cpu-baseline --steps 600 --warmup 30 2>"$out/bench_quick.err" < /dev/null | tee "$out/bench_quick.json" | cut -c1-200
+    echo "== bench quick (RecordRing path)"; timeout 300 python bench.py --full --quick --no-traffic --no-cpu-baseline --steps 600 --warmup 30 2>"$out/bench_quick.err" < /dev/null | tee "$out/bench_quick.json" | cut -c1-200
     echo "== two ranks on one GPU (gloo): greedy ring + beam dynamic dispatch"
     timeout 300 python bench.py --gpus 2 --dist-debug-one-gpu --quick --no-traffic --no-cpu-baseline --no-roofline --steps 40 --warmup 5 2>"$out/bench_2rank.err" < /dev/null | tee "$out/bench_2rank_greedy.json" | cut -c1-260; tail -3 "$out/bench_2rank.err"
     timeout 400 python bench.py --gpus 2 --dist-debug-one-gpu --workload beam --batch 4 --no-traffic --no-cpu-baseline --steps 3 --warmup 1 2>"$out/bench_2rank_beam.err" < /dev/null | tee "$out/bench_2rank_beam.json" | cut -c1-400; tail -3 "$out/bench_2rank_beam.err"
@@ -268,24 +268,24 @@ PY
       echo "== pytest -m gpu"; (time timeout 1500 python -m pytest tests -m gpu -q 2>&1 | tail -6) 2>&1 | tee "$out/pytest_gpu.txt"
     fi
     echo "== smoke"; timeout 300 python __graft_entry__.py --smoke 2>&1 | tail -4 | tee "$out/smoke.txt"
-    echo "== default bench"; (time timeout 900 python bench.py 2>"$out/bench_default.err" < /dev/null | tee "$out/bench_default.json" | cut -c1-300) 2>&1 | tail -5
+    echo "== default bench"; (time timeout 900 python bench.py --full 2>"$out/bench_default.err" < /dev/null | tee "$out/bench_default.json" | cut -c1-300) 2>&1 | tail -5
     echo "== rocprofv3 kernel stats, greedy"
     stats "$out/prof_greedy" python "$R/bench.py" --quick --no-traffic --no-roofline --no-cpu-baseline --in-flight 1 --steps 100 --warmup 10
     if [ "$what" = full ]; then
       echo "== box state (TCC counters)"; BOX_STATE_OUT="$out/box_state" bash tools/box_state.sh 2>&1 | tail -12 | tee "$out/box_state.txt"
       echo "== rocprofv3 kernel stats, large B=64"
       stats "$out/prof_large" python "$R/bench.py" --model large --batch 64 --quick --no-traffic --no-roofline --no-cpu-baseline --in-flight 1 --steps 20 --warmup 3
-      echo "== E-Branchformer"; timeout 300 python bench.py --model ebf --quick --no-traffic --no-cpu-baseline --steps 50 --warmup 5 2>/dev/null < /dev/null | tee "$out/bench_ebf.json" | cut -c1-200
+      echo "== E-Branchformer"; timeout 300 python bench.py --full --model ebf --quick --no-traffic --no-cpu-baseline --steps 50 --warmup 5 2>/dev/null < /dev/null | tee "$out/bench_ebf.json" | cut -c1-200
       echo "== search kernel stats"; stats "$out/search_stats" python "$R/bench.py" --workload beam --in-flight 1 --steps 1 --warmup 1 --no-cpu-baseline --no-traffic
       echo "== search kernel stats, 640 rows (configs[3] per GPU)"; stats "$out/search640_stats" python "$R/bench.py" --workload beam --batch 64 --in-flight 1 --steps 1 --warmup 1 --no-cpu-baseline --no-traffic
-      echo "== configs[3] per GPU with HBM traffic of the label step"; timeout 600 python bench.py --workload beam --batch 64 --steps 1 --warmup 1 --no-cpu-baseline 2>/dev/null < /dev/null | tee "$out/bench_beam_b64.json" | cut -c1-300
+      echo "== configs[3] per GPU with HBM traffic of the label step"; timeout 600 python bench.py --full --workload beam --batch 64 --steps 1 --warmup 1 --no-cpu-baseline 2>/dev/null < /dev/null | tee "$out/bench_beam_b64.json" | cut -c1-300
     fi ;;
   sub2)
     echo "== stamps"
     EM_SUB2_STAMPS=1 timeout 120 python bench.py --quick --no-traffic --no-roofline --no-cpu-baseline --steps 3 --warmup 2 2>&1 | grep "sub2 stamps" | head -2 | tee "$out/stamps.txt"
     echo "== tests"; timeout 300 python -m pytest tests/test_gpu_kernels.py -q -x -k "sub12 or conv2d or subsampl" 2>&1 | tail -3
     echo "== kernel stats"; stats "$out/stats" python "$R/bench.py" --quick --no-traffic --no-roofline --no-cpu-baseline --steps 50 --warmup 5
-    echo "== bench"; timeout 200 python bench.py --quick --no-traffic --no-cpu-baseline --steps 600 --warmup 30 2>/dev/null < /dev/null | tee "$out/bench_quick.json" | cut -c1-260 ;;
+    echo "== bench"; timeout 200 python bench.py --full --quick --no-traffic --no-cpu-baseline --steps 600 --warmup 30 2>/dev/null < /dev/null | tee "$out/bench_quick.json" | cut -c1-260 ;;
   search-stats)
     stats "$out/search_stats" python "$R/bench.py" --workload beam --in-flight 1 --steps 1 --warmup 1 --no-cpu-baseline --no-traffic ;;
   search-pmc)
@@ -311,7 +311,7 @@ PY
       set -- $cfg
       export ESPNET_AMD_SA_SPLIT=$1 ESPNET_AMD_SA_GROUP=$2
       echo -n "split $1 group $2: "
-      timeout 300 python bench.py --workload beam --steps 2 --warmup 1 --no-cpu-baseline --no-traffic 2>/dev/null < /dev/null | beam_line
+      timeout 300 python bench.py --full --workload beam --steps 2 --warmup 1 --no-cpu-baseline --no-traffic 2>/dev/null < /dev/null | beam_line
     done ;;
   attn-stamps)
     EM_ATTN2_STAMPS=1 timeout 120 python bench.py --quick --no-traffic --no-roofline --no-cpu-baseline --steps 2 --warmup 1 2>&1 < /dev/null | grep "attn2 stamps" | sed -n "13,15p" | tee "$out/attn2_stamps.txt" ;;
@@ -338,7 +338,7 @@ PY
     echo "== streaming files with the fused layers from one block"
     (ESPNET_AMD_STREAM_FUSED_MIN=1 timeout 300 python -m pytest tests/test_gpu_streaming.py tests/test_gpu_online_search.py -q 2>&1 | tail -6) | tee "$out/pytest_stream_fused_min1.txt"
     echo "== smoke"; timeout 300 python __graft_entry__.py --smoke 2>&1 | tail -4 | tee "$out/smoke.txt"
-    echo "== default bench"; (time timeout 600 python bench.py 2>"$out/bench_default.err" < /dev/null | tee "$out/bench_default.json" | cut -c1-300) 2>&1 | tail -5
+    echo "== default bench"; (time timeout 600 python bench.py --full 2>"$out/bench_default.err" < /dev/null | tee "$out/bench_default.json" | cut -c1-300) 2>&1 | tail -5
     echo "== kernel table of the 32-stream tick"
     stats "$out/stream32_stats" python "$R/tools/stream_ab.py" batch ;;
   stream-ab2)  # the 128-stream tick (no helper workgroups there: 256 workgroups) with either attention kernel, twice each; the greedy
@@ -375,6 +375,6 @@ PY
   final)  # the suite, smoke, the default bench line
     echo "== pytest -m gpu"; (time timeout 900 python -m pytest tests -m gpu -q 2>&1 | tail -8) 2>&1 | tee "$out/pytest_gpu.txt"
     echo "== smoke"; timeout 300 python __graft_entry__.py --smoke 2>&1 | tail -4 | tee "$out/smoke.txt"
-    echo "== default bench"; (time timeout 600 python bench.py 2>"$out/bench_default.err" < /dev/null | tee "$out/bench_default.json" | cut -c1-300) 2>&1 | tail -5 ;;
+    echo "== default bench"; (time timeout 600 python bench.py --full 2>"$out/bench_default.err" < /dev/null | tee "$out/bench_default.json" | cut -c1-300) 2>&1 | tail -5 ;;
   *) echo "unknown call: $what"; exit 2 ;;
 esac

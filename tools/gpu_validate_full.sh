@@ -5,7 +5,7 @@ set -u
 tag=${1:-run}; out=gpurun_out/$tag; mkdir -p "$out"
 echo "== pytest -m gpu"; (time timeout 900 python -m pytest tests -m gpu -q 2>&1 | tail -8) 2>&1 | tee "$out/pytest_gpu.txt"
 echo "== smoke"; timeout 200 python __graft_entry__.py --smoke 2>&1 | tail -5 | tee "$out/smoke.txt"
-echo "== default bench"; (time timeout 600 python bench.py 2>"$out/bench_default.err" | tail -1 > "$out/bench_default.json") 2>&1 | tail -4
+echo "== default bench"; (time timeout 600 python bench.py --full 2>"$out/bench_default.err" | tail -1 > "$out/bench_default.json") 2>&1 | tail -4
 cut -c1-400 "$out/bench_default.json"
 python - "$out/bench_default.json" <<'PY'
 import json, sys
