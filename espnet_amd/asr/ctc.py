@@ -6,9 +6,10 @@ import os
 import torch
 
 from espnet_amd import lib as L
+from espnet_amd.packing import PackedModule
 
 
-class CTC(torch.nn.Module):
+class CTC(PackedModule):
     def __init__(self, odim: int, encoder_output_size: int, dropout_rate: float = 0.0,
                  ctc_type: str = "builtin", reduce: bool = True, ignore_nan_grad: bool = None,
                  zero_infinity: bool = True, brctc_risk_strategy: str = "exp",
@@ -20,27 +21,13 @@ class CTC(torch.nn.Module):
         self.ctc_lo = torch.nn.Linear(encoder_output_size, odim)  # parameter container
         self.ctc_type = ctc_type
         self.compute_dtype = compute_dtype
-        self._packed = None
 
     @property
     def em_dtype(self):
         return L.DTYPES[self.compute_dtype]
 
-    @property
-    def act_dtype(self):
-        return torch.bfloat16 if self.em_dtype == L.EM_BF16 else torch.float32
-
-    def invalidate(self):
-        self._packed = None
-
-    def _pack(self, device):
-        p = self._packed
-        if p is None or p["device"] != device or p["dtype"] != self.em_dtype:
-            p = dict(w=self.ctc_lo.weight.detach().float().contiguous().to(self.act_dtype).to(device),
-                     b=self.ctc_lo.bias.detach().float().contiguous().to(device), device=device,
-                     dtype=self.em_dtype)
-            self._packed = p
-        return p
+    def _build_pack(self, pk):
+        pk.weight, pk.bias = pk.A(self.ctc_lo.weight), pk.F(self.ctc_lo.bias)
 
     def _to_act(self, hs_pad: torch.Tensor) -> torch.Tensor:
         L.require_gpu(hs_pad, "hs_pad")
@@ -54,11 +41,11 @@ class CTC(torch.nn.Module):
 
     def logits_device(self, enc_act: torch.Tensor) -> torch.Tensor:
         """enc_act (B,T,d) in the compute dtype -> logits (B,T,V) f32."""
-        p = self._pack(enc_act.device)
+        p = self.packed(enc_act.device)
         B, T, d = enc_act.shape
         out = torch.empty(B, T, self.odim, dtype=torch.float32, device=enc_act.device)
-        a = L.EmGemmArgs(A=enc_act.data_ptr(), W=p["w"].data_ptr(), C=out.data_ptr(),
-                         bias=p["b"].data_ptr(), M=B * T, N=self.odim, K=d, lda=d, ldc=self.odim,
+        a = L.EmGemmArgs(A=enc_act.data_ptr(), W=p.weight.data_ptr(), C=out.data_ptr(),
+                         bias=p.bias.data_ptr(), M=B * T, N=self.odim, K=d, lda=d, ldc=self.odim,
                          scale=1.0)
         L.check(L.load().em_gemm(self.em_dtype, L.EM_EPI_STORE_F32, L.EM_A_PLAIN, a,
                                  L.current_stream_ptr()), "em_gemm(ctc_lo)")
@@ -88,10 +75,10 @@ class CTC(torch.nn.Module):
         # round 5: arg-max in the epilogue of the ctc_lo GEMM, as em_ctc_greedy has it - the logits never exist (10 MB per
         # tick of a 32-stream batch, 26.5 + 26.1 us of its 1.25 ms: profiles/r05x_stream_batch32_kernel_stats.csv); only
         # (value, column) pairs per 64 columns are written and reduced.  Same values compared, ties to the lowest column.
-        p = self._pack(dev)
+        p = self.packed(dev)
         G = 2 * ((V + 127) // 128)
         part = torch.empty(B * T * G * 2, dtype=torch.float32, device=dev)
-        a = L.EmGemmArgs(A=act.data_ptr(), W=p["w"].data_ptr(), C=part.data_ptr(), bias=p["b"].data_ptr(), M=B * T, N=V,
+        a = L.EmGemmArgs(A=act.data_ptr(), W=p.weight.data_ptr(), C=part.data_ptr(), bias=p.bias.data_ptr(), M=B * T, N=V,
                          K=d, lda=d, ldc=G, scale=1.0)
         L.check(L.load().em_gemm(self.em_dtype, L.EM_EPI_ARGMAX_PART, L.EM_A_PLAIN, a, st), "em_gemm(ctc_lo, arg-max)")
         L.check(L.load().em_argmax_partials(L.ptr(part), B * T, G, L.ptr(ids), st), "em_argmax_partials")
@@ -113,13 +100,13 @@ class CTC(torch.nn.Module):
     def greedy_device(self, enc_act: torch.Tensor, olens_dev: torch.Tensor, blank: int, sos_eos: int, out=None):
         """Fused G1 path (bin/asr_inference.py:574-575): returns (ids (B,T) i32, tokens (B,T) i32
         padded with -1, token_lens (B,) i32), all on the device, no host sync."""
-        p = self._pack(enc_act.device)
+        p = self.packed(enc_act.device)
         B, T, d = enc_act.shape
         dev = enc_act.device
         logits = torch.empty(B * T, self.odim, dtype=torch.float32, device=dev)
         ids = torch.empty(B, T, dtype=torch.int32, device=dev)
         tokens, tlens = self._token_outputs(B, T, dev, out)
-        L.check(L.load().em_ctc_greedy(self.em_dtype, L.ptr(enc_act), L.ptr(p["w"]), L.ptr(p["b"]),
+        L.check(L.load().em_ctc_greedy(self.em_dtype, L.ptr(enc_act), L.ptr(p.weight), L.ptr(p.bias),
                                        B, T, d, self.odim, L.ptr(olens_dev), blank, sos_eos,
                                        L.ptr(logits), L.ptr(ids), L.ptr(tokens), L.ptr(tlens),
                                        L.current_stream_ptr()), "em_ctc_greedy")

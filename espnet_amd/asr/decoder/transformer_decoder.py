@@ -6,7 +6,7 @@ Mirrors espnet2/asr/decoder/transformer_decoder.py:393-468 (constructor) and :19
 `output_layer`).  The torch.nn layers are parameter containers only.
 
 The arithmetic is csrc/decoder.hip + csrc/gemm.hip + csrc/norm.hip, driven per search step by
-csrc/search.hip (`em_search_steps`); `pack()` repacks the reference-layout parameters once
+csrc/search.hip (`em_search_steps`); `_build_pack()` repacks the reference-layout parameters once
 (q|k|v rows concatenated for self-attention, k|v for source attention, absolute sinusoid table).
 Inside the fused device search (espnet_amd/nets/batch_beam_search.py) the decoder step never returns to
 Python.  The reference's scorer interface (`init_state`, `batch_init_state`, `select_state`, `score`,
@@ -23,6 +23,7 @@ import torch
 from espnet_amd import lib as L
 from espnet_amd.asr.encoder.conformer_encoder import LayerNorm, _PositionwiseFeedForward
 from espnet_amd.nets.scorer_interface import BatchScorerInterface
+from espnet_amd.packing import PackedModule
 
 
 def abs_pos_table(length: int, d: int) -> torch.Tensor:
@@ -63,7 +64,9 @@ class _PosEncPlaceholder(torch.nn.Module):
     """`embed.1` of the reference (PositionalEncoding, no parameters/buffers)."""
 
 
-class TransformerDecoder(torch.nn.Module, BatchScorerInterface):
+class TransformerDecoder(PackedModule, BatchScorerInterface):
+    pe_min = 1024  # rows of the positional table a pack carries at least (more when a search needs them)
+
     def __init__(self, vocab_size: int, encoder_output_size: int, attention_heads: int = 4,
                  linear_units: int = 2048, num_blocks: int = 6, dropout_rate: float = 0.1,
                  positional_dropout_rate: float = 0.1, self_attention_dropout_rate: float = 0.0,
@@ -85,36 +88,18 @@ class TransformerDecoder(torch.nn.Module, BatchScorerInterface):
         self.output_layer = torch.nn.Linear(d, vocab_size)
         self.decoders = torch.nn.ModuleList(
             [_DecoderLayer(d, attention_heads, linear_units) for _ in range(num_blocks)])
-        self._packed = None
         self._mem = None
 
     def invalidate(self):
-        self._packed = None
+        super().invalidate()
         self._mem = None
 
     @property
     def em_dtype(self) -> int:
         return L.DTYPES[self.compute_dtype]
 
-    @property
-    def act_dtype(self) -> torch.dtype:
-        return torch.bfloat16 if self.em_dtype == L.EM_BF16 else torch.float32
-
-    def pack(self, device, pe_len: int = 1024):
-        dev = torch.device(device)
-        act = self.act_dtype
-        keep = []
-
-        def A(t):
-            t = t.detach().to(torch.float32).contiguous().to(act).to(dev)
-            keep.append(t)
-            return t
-
-        def F(t):
-            t = t.detach().to(torch.float32).contiguous().to(dev)
-            keep.append(t)
-            return t
-
+    def _build_pack(self, pk):
+        A, F, act, pe_len = pk.A, pk.F, pk.act, pk.pe_len
         w = L.EmDecoderWeights()
         w.d, w.heads, w.ff, w.num_blocks = self.d, self.heads, self.linear_units, self.num_blocks
         w.vocab, w.pe_len = self.vocab_size, pe_len
@@ -123,8 +108,7 @@ class TransformerDecoder(torch.nn.Module, BatchScorerInterface):
                    out_w=A(self.output_layer.weight), out_b=F(self.output_layer.bias))
         if act == torch.bfloat16 and self.d % 32 == 0:
             top["out_w_frag"] = A(L.pack_frag16(self.output_layer.weight.detach(), pad_rows=512))
-        for k, v in top.items():
-            setattr(w, k, v.data_ptr())
+        pk.fill(w, top)
         layers = (L.EmDecoderLayer * self.num_blocks)()
         for i, l in enumerate(self.decoders):
             sa, ca, ff = l.self_attn, l.src_attn, l.feed_forward
@@ -149,18 +133,9 @@ class TransformerDecoder(torch.nn.Module, BatchScorerInterface):
                 lt["self_wout_frag"] = A(L.pack_frag16(sa.linear_out.weight.detach()))
                 lt["src_wout_frag"] = A(L.pack_frag16(ca.linear_out.weight.detach()))
                 lt["src_wq_frag"] = A(L.pack_frag16(ca.linear_q.weight.detach()))
-            for k, v in lt.items():
-                setattr(layers[i], k, v.data_ptr())
+            pk.fill(layers[i], lt)
         w.layers = C.cast(layers, C.POINTER(L.EmDecoderLayer))
-        self._packed = dict(w=w, layers=layers, keep=keep, device=dev, dtype=self.em_dtype,
-                            pe_len=pe_len)
-        return self._packed
-
-    def ensure_packed(self, device, pe_len: int):
-        p = self._packed
-        if p is None or p["device"] != device or p["dtype"] != self.em_dtype or p["pe_len"] < pe_len:
-            p = self.pack(device, max(1024, pe_len))
-        return p
+        pk.w, pk.layers = w, layers
 
     # ------------------------------------------------------------------ scorer interface (one call per step)
     def init_state(self, x: torch.Tensor):
@@ -186,7 +161,7 @@ class TransformerDecoder(torch.nn.Module, BatchScorerInterface):
         n, T, d = xs.shape
         shared = n == 1 or xs.stride(0) == 0
         base = xs[0:1] if shared else xs
-        key = (base.data_ptr(), tuple(base.shape), base._version, base.dtype, pk["dtype"], n if not shared else 0)
+        key = (base.data_ptr(), tuple(base.shape), base._version, base.dtype, pk.dtype, n if not shared else 0)
         if self._mem is not None and self._mem["key"] == key:
             return self._mem
         dev, act = xs.device, self.act_dtype
@@ -199,7 +174,7 @@ class TransformerDecoder(torch.nn.Module, BatchScorerInterface):
                 "em_cast_f32")
         mem_kv = torch.empty(self.num_blocks, B * T, 2 * d, dtype=act, device=dev)
         mem_vT = torch.zeros(self.num_blocks, B, d, Tpad, dtype=act, device=dev)
-        L.check(lib.em_decoder_memory(self.em_dtype, C.byref(pk["w"]), L.ptr(enc), B, T, Tpad, L.ptr(mem_kv),
+        L.check(lib.em_decoder_memory(self.em_dtype, C.byref(pk.w), L.ptr(enc), B, T, Tpad, L.ptr(mem_kv),
                                       L.ptr(mem_vT), L.current_stream_ptr()), "em_decoder_memory")
         # `base` is kept alive with the entry: its address cannot be handed to another tensor meanwhile
         self._mem = dict(key=key, base=base, B=B, T=T, Tpad=Tpad, mem_kv=mem_kv, mem_vT=mem_vT, shared=shared,
@@ -215,7 +190,7 @@ class TransformerDecoder(torch.nn.Module, BatchScorerInterface):
         dev = xs.device
         n, Lc = ys.shape
         pos = Lc - 1
-        pk = self.ensure_packed(dev, pos + 2)
+        pk = self.packed(dev, pos + 2)
         mem = self._memory(xs, pk)
         B, W = (1, n) if mem["shared"] else (n, 1)
         Lmax = pos + 1
@@ -239,7 +214,7 @@ class TransformerDecoder(torch.nn.Module, BatchScorerInterface):
                                 x=L.ptr(x), xn=L.ptr(xn), qkv=L.ptr(qkv), qs=L.ptr(qs), ctx=L.ptr(ctx),
                                 hbuf=L.ptr(hbuf), logits=L.ptr(logits))
         lib = L.load()
-        L.check(lib.em_decoder_step(self.em_dtype, C.byref(pk["w"]), C.byref(a), L.current_stream_ptr()),
+        L.check(lib.em_decoder_step(self.em_dtype, C.byref(pk.w), C.byref(a), L.current_stream_ptr()),
                 "em_decoder_step")
         L.check(lib.em_log_softmax_rows_f32(L.ptr(logits), n, V, L.current_stream_ptr()), "em_log_softmax_rows_f32")
         out = kv.permute(3, 0, 1, 2, 4)  # (n, 2, layers, L, d) views of the one cache tensor
@@ -255,7 +230,7 @@ class TransformerDecoder(torch.nn.Module, BatchScorerInterface):
         dev = hs_pad.device
         B, T, d = hs_pad.shape
         Lc = ys_in_pad.size(1)
-        pk = self.ensure_packed(dev, Lc + 1)
+        pk = self.packed(dev, Lc + 1)
         act, nl, ff, V = self.act_dtype, self.num_blocks, self.linear_units, self.vocab_size
         self._mem = None
         mem = self._memory(hs_pad if B > 1 else hs_pad[0:1], pk)
@@ -276,7 +251,7 @@ class TransformerDecoder(torch.nn.Module, BatchScorerInterface):
                                     mem_kv=L.ptr(mem["mem_kv"]), mem_vT=L.ptr(mem["mem_vT"]), x=L.ptr(x),
                                     xn=L.ptr(xn), qkv=L.ptr(qkv), qs=L.ptr(qs), ctx=L.ptr(ctx), hbuf=L.ptr(hbuf),
                                     logits=L.ptr(logits))
-            L.check(lib.em_decoder_step(self.em_dtype, C.byref(pk["w"]), C.byref(a), L.current_stream_ptr()),
+            L.check(lib.em_decoder_step(self.em_dtype, C.byref(pk.w), C.byref(a), L.current_stream_ptr()),
                     "em_decoder_step")
             out[:, pos] = logits
         self._mem = None

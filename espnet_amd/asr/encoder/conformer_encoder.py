@@ -25,6 +25,7 @@ import torch
 from espnet_amd import lib as L
 from espnet_amd.nets_utils import (SUBSAMPLING_CONVS, SUBSAMPLING_MIN_FRAMES, conv2d_subsampled_lengths,
                                    conv_out_size)
+from espnet_amd.packing import PackedModule
 
 _POS_PROJ_LOCK = threading.Lock()
 # the packed weights struct carries the per-call `ctc_ids` pointer: setting it and launching the encoder is one critical
@@ -238,7 +239,7 @@ def rel_pos_table(T: int, d: int) -> torch.Tensor:
     return torch.cat([torch.flip(pe_positive, [0]), pe_negative[1:]], dim=0)
 
 
-class ConformerEncoder(torch.nn.Module):
+class ConformerEncoder(PackedModule):
     _WS_FN, _ENC_FN = "em_conformer_workspace_bytes", "em_conformer_encode"  # C-ABI entry points of forward_device
 
     @staticmethod
@@ -330,7 +331,6 @@ class ConformerEncoder(torch.nn.Module):
             [_EncoderLayer(output_size, attention_heads, linear_units, cnn_module_kernel)
              for _ in range(num_blocks)])
         self.after_norm = LayerNorm(output_size)
-        self._packed = None
         self._pos_cache = {}
         self._ws = None
         self._olens_cache = {}
@@ -345,31 +345,14 @@ class ConformerEncoder(torch.nn.Module):
     def em_dtype(self) -> int:
         return L.DTYPES[self.compute_dtype]
 
-    @property
-    def act_dtype(self) -> torch.dtype:
-        return torch.bfloat16 if self.em_dtype == L.EM_BF16 else torch.float32
-
     def invalidate(self):
-        self._packed = None
+        super().invalidate()
         self._pos_cache = {}
 
-    def pack(self, device):
-        """Repack the reference-layout parameters into the layouts the kernels consume (once)."""
-        dev = torch.device(device)
-        act = self.act_dtype
+    def _build_pack(self, pk):
+        """The reference-layout parameters in the layouts the kernels consume."""
+        A, F = pk.A, pk.F
         d, ff, Lb = self._output_size, self.linear_units, self.num_blocks
-        keep = []
-
-        def A(t):  # act-dtype matrix on the device
-            t = t.detach().to(torch.float32).contiguous().to(act).to(dev)
-            keep.append(t)
-            return t
-
-        def F(t):  # f32 vector/table on the device
-            t = t.detach().to(torch.float32).contiguous().to(dev)
-            keep.append(t)
-            return t
-
         e = self.embed
         F2 = e.out.in_features // d
         w = L.EmConformerWeights()
@@ -383,8 +366,7 @@ class ConformerEncoder(torch.nn.Module):
         t["embed_b"] = F(e.out.bias)
         t["wpos_all"] = A(torch.cat([l.self_attn.linear_pos.weight for l in self.encoders], dim=0))
         t["after_norm_g"], t["after_norm_b"] = F(self.after_norm.weight), F(self.after_norm.bias)
-        for k, v in t.items():
-            setattr(w, k, v.data_ptr())
+        pk.fill(w, t)
         layers = (L.EmConformerLayer * Lb)()
         glu_perm = torch.arange(2 * d).reshape(2, d // 16, 16).permute(1, 0, 2).reshape(-1)
         for i, l in enumerate(self.encoders):
@@ -412,11 +394,10 @@ class ConformerEncoder(torch.nn.Module):
                 ff_w1=A(l.feed_forward.w_1.weight), ff_b1=F(l.feed_forward.w_1.bias),
                 ff_w2=A(l.feed_forward.w_2.weight), ff_b2=F(l.feed_forward.w_2.bias),
             )
-            for k, v in lt.items():
-                setattr(layers[i], k, v.data_ptr())
+            pk.fill(layers[i], lt)
         if self._fusable():
-            self._pack_fused(layers, A, F)
-            self._pack_fused_ctc(w, A, F)
+            self._pack_fused(pk, layers)
+            self._pack_fused_ctc(pk, w)
         elif self.em_dtype == L.EM_BF16 and d == 512 and ff % 128 == 0 and ff >= 256 and _fused_enabled(self):
             # the 512-wide model: each feed-forward module as one row-block launch (csrc/ffn_rows.hip)
             for i, l in enumerate(self.encoders):
@@ -431,13 +412,10 @@ class ConformerEncoder(torch.nn.Module):
                 if self.heads * 64 == d:  # round 6: q | k | v walked behind the macaron launch (EmFfnRowsArgs.post_q)
                     sa = l.self_attn
                     lt["wqkvp"] = A(pack_ffn_rows_w1(torch.cat([sa.linear_q.weight, sa.linear_k.weight, sa.linear_v.weight], 0)))
-                for k, v in lt.items():
-                    setattr(layers[i], k, v.data_ptr())
-            self._pack_rows_ctc(w, A, F)
+                pk.fill(layers[i], lt)
+            self._pack_rows_ctc(pk, w)
         w.layers = C.cast(layers, C.POINTER(L.EmConformerLayer))
-        self._packed = dict(w=w, layers=layers, keep=keep, device=dev, dtype=self.em_dtype)
-        self._pos_cache = {}
-        return self._packed
+        pk.w, pk.layers = w, layers
 
     def _fusable(self) -> bool:
         """Shapes the row-block fused kernels cover (csrc/block.hip); everything else keeps the per-operator launches."""
@@ -445,10 +423,11 @@ class ConformerEncoder(torch.nn.Module):
                 and self.linear_units <= 1024 and self.cnn_module_kernel == 31
                 and not getattr(self, "legacy_relpos", False))
 
-    def _pack_fused(self, layers, A, F):
+    def _pack_fused(self, pk, layers):
         """Operands of em_conformer_block_fused (include/espnet_amd.h): pointwise_conv1 in 64-row value / gate
         granules and the bias / LayerNorm vectors of every kernel as groups of EM_BLOCK_PARAM_GROUP floats in the
         order the kernel consumes them."""
+        A, F = pk.A, pk.F
         d, G = self._output_size, L.EM_BLOCK_PARAM_GROUP
 
         def group(*vecs):
@@ -490,10 +469,9 @@ class ConformerEncoder(torch.nn.Module):
                       fp_da=F(torch.cat(d_groups + tail)))
             if i == 0:
                 lt["fp_a"] = F(torch.cat(a_groups(l)))
-            for k, v in lt.items():
-                setattr(layers[i], k, v.data_ptr())
+            pk.fill(layers[i], lt)
 
-    def _pack_fused_ctc(self, w, A, F):
+    def _pack_fused_ctc(self, pk, w):
         """The CTC head the model attached (`fused_ctc`, a espnet_amd.asr.ctc.CTC): its weight zero-padded to 64-row
         units and its bias padded with -3e38, for the arg-max stage of the last block kernel (EM_BLOCK_CTC)."""
         ctc = getattr(self, "fused_ctc", None)
@@ -507,10 +485,10 @@ class ConformerEncoder(torch.nn.Module):
         wt[:V] = ctc.ctc_lo.weight.detach().to(torch.float32).cpu()
         bt = torch.full((units * 64,), -3.0e38, dtype=torch.float32)
         bt[:V] = ctc.ctc_lo.bias.detach().to(torch.float32).cpu()
-        w.ctc_w, w.ctc_b, w.ctc_units = A(pack_k_units(wt)).data_ptr(), F(bt).data_ptr(), units
-        self._ctc_stamp = self._ctc_version(ctc)
+        pk.fill(w, dict(ctc_w=pk.A(pack_k_units(wt)), ctc_b=pk.F(bt)))
+        w.ctc_units, pk.ctc_stamp = units, self._ctc_version(ctc)
 
-    def _pack_rows_ctc(self, w, A, F):
+    def _pack_rows_ctc(self, pk, w):
         """512-wide model: the attached CTC head for the arg-max walk behind the last row-block launch (EmFfnRowsArgs.post_*):
         weight zero-padded to whole 128-row chunks in the w1p layout, bias padded with -3e38."""
         ctc = getattr(self, "fused_ctc", None)
@@ -522,13 +500,18 @@ class ConformerEncoder(torch.nn.Module):
         wt[:V] = ctc.ctc_lo.weight.detach().to(torch.float32).cpu()
         bt = torch.full((chunks * 128,), -3.0e38, dtype=torch.float32)
         bt[:V] = ctc.ctc_lo.bias.detach().to(torch.float32).cpu()
-        w.ctc_w, w.ctc_b, w.ctc_units = A(pack_ffn_rows_w1(wt)).data_ptr(), F(bt).data_ptr(), chunks
-        self._ctc_stamp = self._ctc_version(ctc)
+        pk.fill(w, dict(ctc_w=pk.A(pack_ffn_rows_w1(wt)), ctc_b=pk.F(bt)))
+        w.ctc_units, pk.ctc_stamp = chunks, self._ctc_version(ctc)
 
     @staticmethod
     def _ctc_version(ctc):
         lo = ctc.ctc_lo
         return (lo.weight.data_ptr(), lo.weight._version, lo.bias.data_ptr(), lo.bias._version)
+
+    def _pack_current(self, pk) -> bool:
+        """A pack that carries the attached CTC head is current while the head's parameters are the ones it copied."""
+        stamp = getattr(pk, "ctc_stamp", None)
+        return stamp is None or self.fused_ctc is None or stamp == self._ctc_version(self.fused_ctc)
 
     def _pack_subsampling(self, w, t, A, F):
         """conv.2 (and conv.4): [d][k*k*d] with column (kt*k + kf)*d + c_in, the implicit GEMM's K order."""
@@ -547,24 +530,16 @@ class ConformerEncoder(torch.nn.Module):
             t["conv3_w"] = A(e.conv[4].weight.permute(0, 2, 3, 1).reshape(d, 9 * d))
             t["conv3_b"] = F(e.conv[4].bias)
 
-    def _ensure_packed(self, device):
-        p = self._packed
-        if p is None or p["device"] != device or p["dtype"] != self.em_dtype:
-            p = self.pack(device)
-        return p
-
     def _pos_projected(self, T: int, device, pk, pos: torch.Tensor) -> torch.Tensor:
         """pos (2T-1 | T, d) x wpos_all^T -> (rows, num_blocks * d) in the activation dtype, through the same em_gemm
         call the encoder entry point makes without EM_ENC_POS_PROJECTED (bit-identical); kept for the last few lengths
         of the current packing."""
         cache = self.__dict__.setdefault("_pos_proj_cache", {})
         lock = _POS_PROJ_LOCK  # (concurrent batches on host threads; module-level: a lock in __dict__ is not picklable)
-        key = (T, str(device), self.em_dtype, id(pk["w"]))
+        key = (T, str(device), pk.serial)
         cur = torch.cuda.current_stream()
         with lock:
             ent = cache.get(key)
-            if ent is not None and ent[3] is not pk["w"]:  # (an id reused by a later packing: not this weight block)
-                ent = None
             if ent is not None:
                 out, ev, sid, _ = ent
                 if sid != cur.cuda_stream:  # produced on another stream (concurrent batches): order this one behind
@@ -578,14 +553,14 @@ class ConformerEncoder(torch.nn.Module):
             n = self.num_blocks * d
             # the fused 256-wide bf16 path also wants the rows fragment-major (block<ATT|C>): packed here, once per length,
             # behind the table (EM_ENC_POS_PACKED)
-            packed = (self.em_dtype == L.EM_BF16 and d == 256 and rows == 2 * T - 1 and not getattr(pk["w"], "legacy_relpos", 0))
+            packed = (self.em_dtype == L.EM_BF16 and d == 256 and rows == 2 * T - 1 and not getattr(pk.w, "legacy_relpos", 0))
             es = 2 if self.em_dtype == L.EM_BF16 else 4
             tbytes = (rows * n * es + 255) // 256 * 256
             npg = L.load().em_relpos_pos_fragments(T) if packed else 0
             flat = torch.empty(tbytes + self.num_blocks * 4 * npg * 2048, dtype=torch.uint8, device=device)
             out = flat[:rows * n * es].view(self.act_dtype).view(rows, n)
             out._em_flat, out._em_packed = flat, packed  # (keeps the block alive; read back in forward_device)
-            args = L.EmGemmArgs(A=pos.data_ptr(), W=pk["w"].wpos_all, C=out.data_ptr(), bias=None, M=rows, N=n, K=d,
+            args = L.EmGemmArgs(A=pos.data_ptr(), W=pk.w.wpos_all, C=out.data_ptr(), bias=None, M=rows, N=n, K=d,
                                 lda=d, ldc=n, scale=1.0)
             L.check(L.load().em_gemm(self.em_dtype, L.EM_EPI_STORE, L.EM_A_PLAIN, C.byref(args),
                                      L.current_stream_ptr()), "em_gemm(linear_pos)")
@@ -597,7 +572,7 @@ class ConformerEncoder(torch.nn.Module):
             with lock:
                 while len(cache) >= 8:
                     cache.pop(next(iter(cache)))
-                cache[key] = (out, ev, cur.cuda_stream, pk["w"])  # (the weight block is kept alive with its projection)
+                cache[key] = (out, ev, cur.cuda_stream, pk)  # (the pack is kept alive with its projection)
         return out
 
     def _pos_emb(self, T: int, device) -> torch.Tensor:
@@ -657,10 +632,8 @@ class ConformerEncoder(torch.nn.Module):
                 f"has {n0} frames and is too short for subsampling "
                 f"(it needs more than {lim} frames), return empty results", n0, lim, indices=short)
         dev = feats.device
-        pk = self._ensure_packed(dev)
-        ctc = getattr(self, "fused_ctc", None)
-        if ctc is not None and getattr(pk["w"], "ctc_units", 0) > 0 and self._ctc_stamp != self._ctc_version(ctc):
-            pk = self.pack(dev)  # the head's parameters were replaced after packing
+        pk = self.packed(dev)
+        w = pk.w
         lib = L.load()
         T = self.output_frames(T_f)
         if isolate:  # every utterance as if it were the whole batch: tmax = its own length
@@ -674,7 +647,7 @@ class ConformerEncoder(torch.nn.Module):
             if len(self._olens_cache) >= 8:
                 self._olens_cache.pop(next(iter(self._olens_cache)))
             self._olens_cache[okey] = olens_dev
-        need = getattr(lib, self._WS_FN)(self.em_dtype, C.byref(pk["w"]), B, T_f)
+        need = getattr(lib, self._WS_FN)(self.em_dtype, C.byref(w), B, T_f)
         # one workspace per stream: independent utterance batches may be encoded concurrently on
         # different HIP streams
         skey = torch.cuda.current_stream().cuda_stream
@@ -700,25 +673,25 @@ class ConformerEncoder(torch.nn.Module):
         # attribute): the library takes the 512-wide models' row-block launches from a smaller share of the chip then
         enc_flags |= L.EM_ENC_IN_FLIGHT(max(1, min(15, int(getattr(self, "batches_in_flight", 1) or 1))))
         pos = self._pos_emb(T, dev)
-        if self._ENC_FN == "em_conformer_encode" and getattr(pk["w"], "wpos_all", None):
+        if self._ENC_FN == "em_conformer_encode" and getattr(w, "wpos_all", None):
             # linear_pos of every block depends on T and the weights only: projected once per length, handed over ready
             pos = self._pos_projected(T, dev, pk, pos)
             enc_flags |= L.EM_ENC_POS_PROJECTED | (L.EM_ENC_POS_PACKED if getattr(pos, "_em_packed", False) else 0)
         with _ENC_CALL_LOCK:
-            if hasattr(pk["w"], "ctc_ids"):
-                pk["w"].ctc_ids = None
-                if self._ENC_FN == "em_conformer_encode" and getattr(pk["w"], "ctc_units", 0) > 0:
+            if hasattr(w, "ctc_ids"):
+                w.ctc_ids = None
+                if self._ENC_FN == "em_conformer_encode" and getattr(w, "ctc_units", 0) > 0:
                     ids = torch.empty(B, T, dtype=torch.int32, device=dev)
-                    pk["w"].ctc_ids = ids.data_ptr()
-                    plan = lib.em_conformer_encode_plan_for(self.em_dtype, C.byref(pk["w"]), enc_flags, B, T_f)
+                    w.ctc_ids = ids.data_ptr()
+                    plan = lib.em_conformer_encode_plan_for(self.em_dtype, C.byref(w), enc_flags, B, T_f)
                     if plan < 0:
                         L.check(plan, "em_conformer_encode_plan")
                     if plan & L.EM_ENC_PLAN_CTC_IDS:
                         self.last_ctc_ids = ids
                     else:
-                        pk["w"].ctc_ids = None
+                        w.ctc_ids = None
             rc = getattr(lib, self._ENC_FN)(
-                self.em_dtype, C.byref(pk["w"]), L.ptr(feats), L.ptr(mvn_partial), L.ptr(flens_dev),
+                self.em_dtype, C.byref(w), L.ptr(feats), L.ptr(mvn_partial), L.ptr(flens_dev),
                 L.ptr(olens_dev), B, T_f, L.ptr(pos), L.ptr(ws),
                 ws.numel(), L.ptr(enc_out), L.ptr(enc_act),
                 enc_flags, L.current_stream_ptr())

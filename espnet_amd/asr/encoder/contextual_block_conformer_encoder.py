@@ -30,6 +30,7 @@ from espnet_amd import lib as L
 from espnet_amd.asr.decoder.transformer_decoder import abs_pos_table
 from espnet_amd.asr.encoder.conformer_encoder import (LayerNorm, _ConvolutionModule,
                                                       _PositionwiseFeedForward)
+from espnet_amd.packing import PackedModule
 
 LN_EPS = 1e-12
 
@@ -69,7 +70,7 @@ class _ContextualBlockEncoderLayer(torch.nn.Module):
         self.norm_final = LayerNorm(size)
 
 
-class ContextualBlockConformerEncoder(torch.nn.Module):
+class ContextualBlockConformerEncoder(PackedModule):
     def __init__(self, input_size: int, output_size: int = 256, attention_heads: int = 4,
                  linear_units: int = 2048, num_blocks: int = 6, dropout_rate: float = 0.1,
                  positional_dropout_rate: float = 0.1, attention_dropout_rate: float = 0.0,
@@ -112,7 +113,6 @@ class ContextualBlockConformerEncoder(torch.nn.Module):
             [_ContextualBlockEncoderLayer(output_size, attention_heads, linear_units, cnn_module_kernel)
              for _ in range(num_blocks)])
         self.after_norm = LayerNorm(output_size)
-        self._packed = None
         self._ws = {}
         self._flen_cache = {}  # (streams, frames, device) -> per-stream frame counts on the device (_embed_device_batch)
 
@@ -123,35 +123,10 @@ class ContextualBlockConformerEncoder(torch.nn.Module):
     def em_dtype(self) -> int:
         return L.DTYPES[self.compute_dtype]
 
-    @property
-    def act_dtype(self) -> torch.dtype:
-        return torch.bfloat16 if self.em_dtype == L.EM_BF16 else torch.float32
-
-    def invalidate(self):
-        self._packed = None
-
-    def load_state_dict(self, state_dict, strict: bool = True, **kw):
-        r = super().load_state_dict(state_dict, strict=strict, **kw)
-        self.invalidate()
-        return r
-
     # ------------------------------------------------------------------ packing (load time)
-    def pack(self, device):
-        dev = torch.device(device)
-        act = self.act_dtype
+    def _build_pack(self, pk):
+        A, F = pk.A, pk.F
         d, ff, NL = self._output_size, self.linear_units, self.num_blocks
-        keep = []
-
-        def A(t):
-            t = t.detach().to(torch.float32).contiguous().to(act).to(dev)
-            keep.append(t)
-            return t
-
-        def F(t):
-            t = t.detach().to(torch.float32).contiguous().to(dev)
-            keep.append(t)
-            return t
-
         e = self.embed
         F2 = e.out.in_features // d
         w = L.EmConformerWeights()
@@ -163,8 +138,7 @@ class ContextualBlockConformerEncoder(torch.nn.Module):
                    embed_w=A(e.out.weight.reshape(d, d, F2).permute(0, 2, 1).reshape(d, F2 * d)),
                    embed_b=F(e.out.bias), after_norm_g=F(self.after_norm.weight),
                    after_norm_b=F(self.after_norm.bias))
-        for k, v in top.items():
-            setattr(w, k, v.data_ptr())
+        pk.fill(w, top)
         layers = (L.EmConformerLayer * NL)()
         glu_perm = torch.arange(2 * d).reshape(2, d // 16, 16).permute(1, 0, 2).reshape(-1)
         for i, l in enumerate(self.encoders):
@@ -192,12 +166,10 @@ class ContextualBlockConformerEncoder(torch.nn.Module):
                 ff_w2=A(l.feed_forward.w_2.weight), ff_b2=F(l.feed_forward.w_2.bias))
             if self._fusable():
                 lt.update(self._fused_layer(l, A, F))
-            for k, v in lt.items():
-                setattr(layers[i], k, v.data_ptr())
+            pk.fill(layers[i], lt)
         w.layers = C.cast(layers, C.POINTER(L.EmConformerLayer))
-        pe = abs_pos_table(5000, d).to(dev)  # StreamPositionalEncoding.extend_pe (embedding.py:357-374)
-        self._packed = dict(w=w, layers=layers, keep=keep, device=dev, dtype=self.em_dtype, pe=pe, F2=F2)
-        return self._packed
+        pk.w, pk.layers = w, layers
+        pk.pe = F(abs_pos_table(5000, d))  # StreamPositionalEncoding.extend_pe (embedding.py:357-374)
 
     def _fusable(self) -> bool:
         """Shapes the fused streaming layer covers (csrc/streaming.hip `cb_fusable`, csrc/block.hip with EM_BLOCK_RELU):
@@ -241,18 +213,11 @@ class ContextualBlockConformerEncoder(torch.nn.Module):
             fp_c=F(group(sa.linear_out.bias, l.norm_conv.weight, l.norm_conv.bias, cm.pointwise_conv1.bias[perm])),
             fp_da=F(fp_d), fp_a=F(fp_a))
 
-    def _ensure_packed(self, device):
-        p = self._packed
-        if p is None or p["device"] != device or p["dtype"] != self.em_dtype:
-            p = self.pack(device)
-        return p
-
     # ------------------------------------------------------------------ device pieces
-    def _embed_device(self, xs: torch.Tensor) -> torch.Tensor:
+    def _embed_device(self, pk, xs: torch.Tensor) -> torch.Tensor:
         """Conv2dSubsamplingWOPosEnc.forward (subsampling_without_posenc.py:44-62); xs (t, idim) f32
         on the GPU -> (t', d) f32."""
-        pk = self._ensure_packed(xs.device)
-        lib, w = L.load(), pk["w"]
+        lib, w = L.load(), pk.w
         t, nm = xs.shape
         d = self._output_size
         T1, F1 = (t - 3) // 2 + 1, (nm - 3) // 2 + 1
@@ -272,9 +237,8 @@ class ContextualBlockConformerEncoder(torch.nn.Module):
         L.check(lib.em_gemm(self.em_dtype, L.EM_EPI_SCALE_F32, L.EM_A_PLAIN, a, st), "em_gemm(embed.out)")
         return out
 
-    def _workspace(self, dev, n_blk, Lb):
-        pk = self._ensure_packed(dev)
-        need = L.load().em_cb_workspace_bytes(self.em_dtype, C.byref(pk["w"]), n_blk, Lb)
+    def _workspace(self, pk, dev, n_blk, Lb):
+        need = L.load().em_cb_workspace_bytes(self.em_dtype, C.byref(pk.w), n_blk, Lb)
         key = (torch.cuda.current_stream().cuda_stream, n_blk, Lb)
         ws = self._ws.get(key)
         if ws is None or ws.numel() < need:
@@ -282,18 +246,16 @@ class ContextualBlockConformerEncoder(torch.nn.Module):
             self._ws[key] = ws
         return ws
 
-    def _encode_blocks(self, x: torch.Tensor, mask_mode: int, past_ctx, next_ctx):
+    def _encode_blocks(self, pk, x: torch.Tensor, mask_mode: int, past_ctx, next_ctx):
         """x (n_blk, L, d) f32 in place."""
-        pk = self._ensure_packed(x.device)
         n_blk, Lb, _ = x.shape
-        ws = self._workspace(x.device, n_blk, Lb)
-        L.check(L.load().em_cb_encode_blocks(self.em_dtype, C.byref(pk["w"]), L.ptr(x), n_blk, Lb,
+        ws = self._workspace(pk, x.device, n_blk, Lb)
+        L.check(L.load().em_cb_encode_blocks(self.em_dtype, C.byref(pk.w), L.ptr(x), n_blk, Lb,
                                              mask_mode, L.ptr(past_ctx), L.ptr(next_ctx), L.ptr(ws),
                                              ws.numel(), L.current_stream_ptr()), "em_cb_encode_blocks")
 
-    def _after_norm(self, ys: torch.Tensor) -> torch.Tensor:
-        pk = self._ensure_packed(ys.device)
-        w = pk["w"]
+    def _after_norm(self, pk, ys: torch.Tensor) -> torch.Tensor:
+        w = pk.w
         L.check(L.load().em_layernorm_inplace_f32(L.ptr(ys), w.after_norm_g, w.after_norm_b,
                                                   ys.size(0), ys.size(1), LN_EPS,
                                                   L.current_stream_ptr()), "after_norm")
@@ -329,7 +291,7 @@ class ContextualBlockConformerEncoder(torch.nn.Module):
         L.require_gpu(xs_pad, "xs_pad")
         assert xs_pad.size(0) == 1
         dev = xs_pad.device
-        pk = self._ensure_packed(dev)
+        pk = self.packed(dev)
         lib = L.load()
         d, bs, hs, la, sub = self._output_size, self.block_size, self.hop_size, self.look_ahead, self.subsample
         st = prev_states or dict(prev_addin=None, buffer_before_downsampling=None, ilens_buffer=None,
@@ -351,7 +313,7 @@ class ContextualBlockConformerEncoder(torch.nn.Module):
             n_res = xs.size(0) % sub + sub * 2
             buf_before = xs[xs.size(0) - n_res:].contiguous()
             xs = xs[: n_samples * sub]
-        x = self._embed_device(xs.contiguous())
+        x = self._embed_device(pk, xs.contiguous())
         if buf_after is not None:
             x = torch.cat([buf_after, x], dim=0)
         total = x.size(0)
@@ -373,19 +335,19 @@ class ContextualBlockConformerEncoder(torch.nn.Module):
         stream = L.current_stream_ptr()
         if n_proc == 0 and total <= bs and is_final:  # short utterance (:496-505)
             xc = torch.empty(1, total, d, dtype=torch.float32, device=dev)
-            L.check(lib.em_stream_pos_enc_f32(L.ptr(x), L.ptr(pk["pe"]), 0, total, d, L.ptr(xc), stream),
+            L.check(lib.em_stream_pos_enc_f32(L.ptr(x), L.ptr(pk.pe), 0, total, d, L.ptr(xc), stream),
                     "em_stream_pos_enc_f32")
-            self._encode_blocks(xc, 0, None, None)
-            return self._after_norm(xc[0]).unsqueeze(0), self._olen_out(dev, 0), None
+            self._encode_blocks(pk, xc, 0, None, None)
+            return self._after_norm(pk, xc[0]).unsqueeze(0), self._olen_out(dev, 0), None
         chunks = torch.empty(block_num, bs + 2, d, dtype=torch.float32, device=dev)
         addin = torch.empty(d, dtype=torch.float32, device=dev)
         n_proc_dev = st.get("n_processed_blocks_dev")  # set by StreamingStepGraph only
-        L.check(lib.em_cb_build_blocks_f32(L.ptr(x), L.ptr(pk["pe"]), L.ptr(prev_addin), n_proc,
+        L.check(lib.em_cb_build_blocks_f32(L.ptr(x), L.ptr(pk.pe), L.ptr(prev_addin), n_proc,
                                            L.ptr(n_proc_dev), block_num, x.size(0), bs, hs, d,
                                            L.ptr(chunks), L.ptr(addin), stream),
                 "em_cb_build_blocks_f32")
         next_ctx = torch.empty(self.num_blocks, d, dtype=torch.float32, device=dev)
-        self._encode_blocks(chunks, 1, past_ctx, next_ctx)
+        self._encode_blocks(pk, chunks, 1, past_ctx, next_ctx)
         ys_chunk = chunks[:, 1 : bs + 1]
         offset = bs - la - hs
         if is_final:
@@ -400,7 +362,7 @@ class ContextualBlockConformerEncoder(torch.nn.Module):
             cur = i * hs + (offset if n_proc == 0 else 0)
             clen = min(bs - offset, y_len - cur) if (i == block_num - 1 and is_final) else hs
             ys[cur : cur + clen] = ys_chunk[i, offset : offset + clen]
-        ys = self._after_norm(ys).unsqueeze(0)
+        ys = self._after_norm(pk, ys).unsqueeze(0)
         olen = self._olen_out(dev, y_len)  # (f32 (1,) on the device as the reference returns it; cached per value: read-only)
         if is_final:
             return ys, olen, None
@@ -411,10 +373,9 @@ class ContextualBlockConformerEncoder(torch.nn.Module):
 
 
     # ------------------------------------------------------------------ a batch of lock-step streams
-    def _embed_device_batch(self, xs: torch.Tensor) -> torch.Tensor:
+    def _embed_device_batch(self, pk, xs: torch.Tensor) -> torch.Tensor:
         """Conv2dSubsamplingWOPosEnc.forward for S streams at once: xs (S, t, idim) f32 on the GPU -> (S, t', d)."""
-        pk = self._ensure_packed(xs.device)
-        lib, w = L.load(), pk["w"]
+        lib, w = L.load(), pk.w
         S, t, nm = xs.shape
         d = self._output_size
         T1, F1 = (t - 3) // 2 + 1, (nm - 3) // 2 + 1
@@ -452,7 +413,7 @@ class ContextualBlockConformerEncoder(torch.nn.Module):
         operators of a call see S * n_blk independent blocks - one launch sequence for all streams."""
         L.require_gpu(xs_pad, "xs_pad")
         dev = xs_pad.device
-        pk = self._ensure_packed(dev)
+        pk = self.packed(dev)
         lib = L.load()
         S = xs_pad.size(0)
         d, bs, hs, la, sub = self._output_size, self.block_size, self.hop_size, self.look_ahead, self.subsample
@@ -481,7 +442,7 @@ class ContextualBlockConformerEncoder(torch.nn.Module):
             n_res = xs.size(1) % sub + sub * 2
             buf_before = xs[:, xs.size(1) - n_res:].contiguous()
             xs = xs[:, : n_samples * sub]
-        x = self._embed_device_batch(xs.contiguous())
+        x = self._embed_device_batch(pk, xs.contiguous())
         if buf_after is not None:
             x = torch.cat([buf_after, x], dim=1)
         total = x.size(1)
@@ -503,32 +464,32 @@ class ContextualBlockConformerEncoder(torch.nn.Module):
         if n_proc == 0 and total <= bs and is_final:  # short utterances (:496-505): no context slots
             xc = torch.empty(S, total, d, dtype=torch.float32, device=dev)
             for s_ in range(S):  # (rare path: one launch per stream)
-                L.check(lib.em_stream_pos_enc_f32(L.ptr(x[s_]), L.ptr(pk["pe"]), 0, total, d, L.ptr(xc[s_]), stream),
+                L.check(lib.em_stream_pos_enc_f32(L.ptr(x[s_]), L.ptr(pk.pe), 0, total, d, L.ptr(xc[s_]), stream),
                         "em_stream_pos_enc_f32")
-            ws = self._workspace(dev, S, total)
-            L.check(lib.em_cb_encode_blocks(self.em_dtype, C.byref(pk["w"]), L.ptr(xc), S, total, 0, None, None,
+            ws = self._workspace(pk, dev, S, total)
+            L.check(lib.em_cb_encode_blocks(self.em_dtype, C.byref(pk.w), L.ptr(xc), S, total, 0, None, None,
                                             L.ptr(ws), ws.numel(), stream), "em_cb_encode_blocks")
-            return self._after_norm(xc.view(S * total, d)).view(S, total, d), total, None
+            return self._after_norm(pk, xc.view(S * total, d)).view(S, total, d), total, None
         Lb = bs + 2
         chunks = torch.empty(S, block_num, Lb, d, dtype=torch.float32, device=dev)
         addin = torch.empty(S, d, dtype=torch.float32, device=dev)
         rows_static = st.get("n_processed_blocks_dev")  # (S,) int32 on the device: set by a captured tick only (BatchTickGraph)
         if rows_static is not None:
-            L.check(lib.em_cb_build_blocks_rows_f32(L.ptr(x), L.ptr(pk["pe"]), L.ptr(prev_addin), L.ptr(rows_static), S,
+            L.check(lib.em_cb_build_blocks_rows_f32(L.ptr(x), L.ptr(pk.pe), L.ptr(prev_addin), L.ptr(rows_static), S,
                                                     block_num, x.size(1), bs, hs, d, L.ptr(chunks), L.ptr(addin), stream),
                     "em_cb_build_blocks_rows_f32")
         elif n_rows is None:
-            L.check(lib.em_cb_build_blocks_batch_f32(L.ptr(x), L.ptr(pk["pe"]), L.ptr(prev_addin), n_proc, S, block_num,
+            L.check(lib.em_cb_build_blocks_batch_f32(L.ptr(x), L.ptr(pk.pe), L.ptr(prev_addin), n_proc, S, block_num,
                                                      x.size(1), bs, hs, d, L.ptr(chunks), L.ptr(addin), stream),
                     "em_cb_build_blocks_batch_f32")
         else:
             rows_dev = torch.tensor(n_rows, dtype=torch.int32).to(dev, non_blocking=True)
-            L.check(lib.em_cb_build_blocks_rows_f32(L.ptr(x), L.ptr(pk["pe"]), L.ptr(prev_addin), L.ptr(rows_dev), S,
+            L.check(lib.em_cb_build_blocks_rows_f32(L.ptr(x), L.ptr(pk.pe), L.ptr(prev_addin), L.ptr(rows_dev), S,
                                                     block_num, x.size(1), bs, hs, d, L.ptr(chunks), L.ptr(addin), stream),
                     "em_cb_build_blocks_rows_f32")
         next_ctx = torch.empty(S, self.num_blocks, d, dtype=torch.float32, device=dev)
-        ws = self._workspace(dev, S * block_num, Lb)
-        L.check(lib.em_cb_encode_blocks_batch(self.em_dtype, C.byref(pk["w"]), L.ptr(chunks), S, block_num, Lb, 1,
+        ws = self._workspace(pk, dev, S * block_num, Lb)
+        L.check(lib.em_cb_encode_blocks_batch(self.em_dtype, C.byref(pk.w), L.ptr(chunks), S, block_num, Lb, 1,
                                               L.ptr(past_ctx), L.ptr(next_ctx), L.ptr(ws), ws.numel(), stream),
                 "em_cb_encode_blocks_batch")
         ys_chunk = chunks[:, :, 1 : bs + 1]
@@ -545,7 +506,7 @@ class ContextualBlockConformerEncoder(torch.nn.Module):
             cur = i * hs + (offset if n_proc == 0 else 0)
             clen = min(bs - offset, y_len - cur) if (i == block_num - 1 and is_final) else hs
             ys[:, cur : cur + clen] = ys_chunk[:, i, offset : offset + clen]
-        ys = self._after_norm(ys.view(S * y_len, d)).view(S, y_len, d)
+        ys = self._after_norm(pk, ys.view(S * y_len, d)).view(S, y_len, d)
         if is_final:
             return ys, y_len, None
         n_next = n_proc + block_num if n_rows is None else [v + block_num for v in n_rows]

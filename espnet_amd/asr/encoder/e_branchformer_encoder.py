@@ -131,26 +131,13 @@ class EBranchformerEncoder(ConformerEncoder):
             [_EBranchformerEncoderLayer(output_size, attention_heads, linear_units, cgmlp_linear_units,
                                         cgmlp_conv_kernel, merge_conv_kernel) for _ in range(num_blocks)])
         self.after_norm = LayerNorm(output_size)
-        self._packed, self._pos_cache, self._ws, self._olens_cache = None, {}, None, {}
+        self._pos_cache, self._ws, self._olens_cache = {}, None, {}
 
-    def pack(self, device):
-        dev = torch.device(device)
-        act = self.act_dtype
+    def _build_pack(self, pk):
+        A, F, act = pk.A, pk.F, pk.act
         d, ff, Lb, cg = self._output_size, self.linear_units, self.num_blocks, self.cgmlp_linear_units
         if (cg // 2) % (64 if self.em_dtype == L.EM_BF16 else 32):
             raise NotImplementedError("cgmlp_linear_units / 2 must be a multiple of the GEMM K step")
-        keep = []
-
-        def A(t):
-            t = t.detach().to(torch.float32).contiguous().to(act).to(dev)
-            keep.append(t)
-            return t
-
-        def F(t):
-            t = t.detach().to(torch.float32).contiguous().to(dev)
-            keep.append(t)
-            return t
-
         e = self.embed
         F2 = e.out.in_features // d
         w = L.EmEBranchformerWeights()
@@ -166,8 +153,7 @@ class EBranchformerEncoder(ConformerEncoder):
                  wpos_all=A(torch.cat([l.attn.linear_pos.weight for l in self.encoders], dim=0)),
                  after_norm_g=F(self.after_norm.weight), after_norm_b=F(self.after_norm.bias))
         self._pack_subsampling(w, t, A, F)
-        for k, v in t.items():
-            setattr(w, k, v.data_ptr())
+        pk.fill(w, t)
         layers = (L.EmEBranchformerLayer * Lb)()
         for i, l in enumerate(self.encoders):
             sa, cm = l.attn, l.cgmlp
@@ -214,12 +200,9 @@ class EBranchformerEncoder(ConformerEncoder):
             if has_mconv:
                 lt.update(merge_conv_w=F(l.depthwise_conv_fusion.weight.reshape(2 * d, -1).t()),
                           merge_conv_b=F(l.depthwise_conv_fusion.bias))
-            for k, v in lt.items():
-                setattr(layers[i], k, v.data_ptr())
+            pk.fill(layers[i], lt)
         w.layers = C.cast(layers, C.POINTER(L.EmEBranchformerLayer))
-        self._packed = dict(w=w, layers=layers, keep=keep, device=dev, dtype=self.em_dtype)
-        self._pos_cache = {}
-        return self._packed
+        pk.w, pk.layers = w, layers
 
 
 class BranchformerEncoder(EBranchformerEncoder):
@@ -289,4 +272,4 @@ class BranchformerEncoder(EBranchformerEncoder):
             [_EBranchformerEncoderLayer(output_size, attention_heads, None, cgmlp_linear_units, cgmlp_conv_kernel,
                                         None, merge_method) for _ in range(num_blocks)])
         self.after_norm = LayerNorm(output_size)
-        self._packed, self._pos_cache, self._ws, self._olens_cache = None, {}, None, {}
+        self._pos_cache, self._ws, self._olens_cache = {}, None, {}

@@ -79,11 +79,9 @@ class ESPnetASRModel(torch.nn.Module):
 
     def load_state_dict(self, state_dict, strict: bool = True, **kw):
         r = super().load_state_dict(state_dict, strict=strict, **kw)
-        for m in (self.encoder, self.ctc, self.decoder):
+        for m in (self.frontend, self.encoder, self.ctc, self.decoder):
             if m is not None and hasattr(m, "invalidate"):
                 m.invalidate()
-        if self.frontend is not None:
-            self.frontend._packed = None
         return r
 
     # ------------------------------------------------------------------ encode

@@ -12,6 +12,7 @@ import torch
 from espnet_amd import lib as L
 from espnet_amd.layers.log_mel import LogMel, pack_banded
 from espnet_amd.nets_utils import stft_frame_lengths
+from espnet_amd.packing import PackedModule
 
 
 def _parse_fs(fs: Union[int, str]) -> int:
@@ -24,7 +25,7 @@ def _parse_fs(fs: Union[int, str]) -> int:
     return int(fs)
 
 
-class DefaultFrontend(torch.nn.Module):
+class DefaultFrontend(PackedModule):
     def __init__(self, fs: Union[int, str] = 16000, n_fft: int = 512, win_length: Optional[int] = None,
                  hop_length: int = 128, window: Optional[str] = "hann", center: bool = True,
                  normalized: bool = False, onesided: bool = True, n_mels: int = 80,
@@ -45,7 +46,6 @@ class DefaultFrontend(torch.nn.Module):
         self.n_mels = n_mels
         self.frontend_type = "default"
         self.logmel = LogMel(fs=fs, n_fft=n_fft, n_mels=n_mels, fmin=fmin, fmax=fmax, htk=htk)
-        self._packed = None
 
     def output_size(self) -> int:
         return self.n_mels
@@ -63,11 +63,9 @@ class DefaultFrontend(torch.nn.Module):
         out[left:left + self.win_length] = w
         return out
 
-    def pack(self, device):
+    def _build_pack(self, pk):
         packed, lo, maxlen = pack_banded(self.logmel.melmat)
-        self._packed = dict(window=self._window_padded().to(device), mel=packed.to(device),
-                            lo=lo.to(device), maxlen=maxlen, device=torch.device(device))
-        return self._packed
+        pk.window, pk.mel, pk.lo, pk.maxlen = pk.hold(self._window_padded()), pk.hold(packed), pk.hold(lo), maxlen
 
     # ---- forward --------------------------------------------------------------------------------
     def feature_lengths(self, input_lengths) -> list:
@@ -79,17 +77,15 @@ class DefaultFrontend(torch.nn.Module):
         wlens_dev (B,) i32 sample counts: reflect-pad every utterance at its own end (the utterance
         decoded alone) instead of at the padded length N (torch.stft on the padded batch)."""
         L.require_gpu(speech, "speech")
-        if self._packed is None or self._packed["device"] != speech.device:
-            self.pack(speech.device)
-        pk = self._packed
+        pk = self.packed(speech.device)
         B, N = speech.shape
         if N <= self.n_fft // 2:
             raise ValueError(f"input of {N} samples is too short for reflect padding of {self.n_fft // 2}")
         T_f = 1 + N // self.hop_length
         feats = torch.empty(B, T_f, self.n_mels, dtype=torch.float32, device=speech.device)
         L.check(L.load().em_frontend_logmel_f32(
-            L.ptr(speech), B, N, self.hop_length, L.ptr(pk["window"]), L.ptr(pk["mel"]),
-            L.ptr(pk["lo"]), pk["maxlen"], self.n_mels, L.ptr(flens_dev), L.ptr(wlens_dev), T_f,
+            L.ptr(speech), B, N, self.hop_length, L.ptr(pk.window), L.ptr(pk.mel),
+            L.ptr(pk.lo), pk.maxlen, self.n_mels, L.ptr(flens_dev), L.ptr(wlens_dev), T_f,
             L.ptr(feats), L.current_stream_ptr()), "em_frontend_logmel_f32")
         return feats
 

@@ -44,6 +44,15 @@ def resolve_dtype(dtype: str) -> str:
 
 
 
+def pack_modules(device, modules):
+    """The weights of the modules a decode will use repacked for the kernels now, not inside the first decode call (an LM
+    after the search has aligned its compute dtype with the decoder's)."""
+    dev = torch.device(device if ":" in str(device) else f"{device}:{torch.cuda.current_device()}")
+    for m in modules:
+        if m is not None and hasattr(m, "packed"):
+            m.packed(dev)
+
+
 class Speech2Text:
     def __init__(self, asr_train_config: Union[Path, str, None] = None,
                  asr_model_file: Union[Path, str, None] = None, transducer_conf: Optional[Dict] = None,
@@ -69,10 +78,6 @@ class Speech2Text:
             asr_train_config, asr_model_file, device, compute_dtype=dtype)
         self.asr_model = asr_model
         self.asr_train_args = asr_train_args
-        for m in (asr_model.frontend, asr_model.encoder):  # repack the weights for the kernels now, not
-            pk = getattr(m, "_ensure_packed", None)        # inside the first decode call
-            if pk is not None:
-                pk(torch.device(device if ":" in str(device) else f"{device}:{torch.cuda.current_device()}"))
         self.device, self.dtype = device, dtype
         self.beam_size, self.ctc_weight, self.penalty = beam_size, ctc_weight, penalty
         self.maxlenratio, self.minlenratio, self.nbest = maxlenratio, minlenratio, nbest
@@ -103,6 +108,8 @@ class Speech2Text:
                 asr_model, beam_size=beam_size, ctc_weight=ctc_weight, penalty=penalty,
                 lm_weight=lm_weight if lm is not None else 0.0, token_list=token_list,
                 normalize_length=normalize_length, lm=lm)
+        m = asr_model
+        pack_modules(device, [m.frontend, m.encoder, m.ctc] + ([] if ctc_greedy else [m.decoder, self.lm]))
 
     # ------------------------------------------------------------------ single utterance (reference API)
     @torch.no_grad()

@@ -53,7 +53,7 @@ class Speech2TextStreaming:
         if not str(device).startswith("cuda"):
             raise RuntimeError("espnet_amd runs on an MI355X only (device='cuda'); no CPU fallback")
         assert batch_size == 1
-        from espnet_amd.bin.asr_inference import resolve_dtype
+        from espnet_amd.bin.asr_inference import pack_modules, resolve_dtype
 
         dtype = resolve_dtype(dtype)
         asr_model, args = ASRTask.build_model_from_file(asr_train_config, asr_model_file, device,
@@ -97,6 +97,8 @@ class Speech2TextStreaming:
                 vocab_size=len(token_list), token_list=token_list,
                 pre_beam_score_key=None if ctc_weight == 1.0 else "full", normalize_length=normalize_length,
                 disable_repetition_detection=disable_repetition_detection)
+        m = asr_model
+        pack_modules(device, [m.frontend, m.encoder, m.ctc] + ([] if search == "greedy" else [m.decoder, lm]))
         token_type = token_type if token_type is not None else getattr(args, "token_type", None)
         bpemodel = bpemodel if bpemodel is not None else getattr(args, "bpemodel", None)
         self.tokenizer = (None if token_type is None or (token_type == "bpe" and bpemodel is None)

@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <mutex>
+
 #include "../../include/espnet_amd.h"
 
 typedef __bf16 bf16;
@@ -166,16 +168,22 @@ static inline int em_cdiv(int a, int b) { return (a + b - 1) / b; }
 // Dynamic-LDS opt-in (hipFuncAttributeMaxDynamicSharedMemorySize) of ONE kernel: the attribute is per DEVICE, so the
 // high-water mark is kept per device (a per-process flag would leave the second GPU of a process at the 64 KB default and
 // its launches would fail).  Raised only when a launch needs more than the device has been given: no runtime API call
-// on later launches, which keeps them legal inside a stream capture.  Concurrent first launches may both set it (idempotent).
+// on later launches, which keeps them legal inside a stream capture.  hipFuncSetAttribute SETS the cap (it does not take
+// the maximum), so host threads that raise it at once with different sizes are serialised: re-check, set, store under
+// one mutex, or a smaller set landing last would leave the recorded cap above the device's and later launches would fail.
 struct EmLdsCap {
   int bytes[64];
 };
+inline std::mutex em_lds_cap_mu;
 static inline int em_raise_lds_cap(const void* fn, size_t bytes, EmLdsCap* cap) {
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return EM_ERR_LAUNCH;
   if ((int)bytes > __atomic_load_n(&cap->bytes[dev], __ATOMIC_ACQUIRE)) {
-    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess) return EM_ERR_LAUNCH;
-    __atomic_store_n(&cap->bytes[dev], (int)bytes, __ATOMIC_RELEASE);
+    std::lock_guard<std::mutex> lk(em_lds_cap_mu);
+    if ((int)bytes > __atomic_load_n(&cap->bytes[dev], __ATOMIC_RELAXED)) {
+      if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess) return EM_ERR_LAUNCH;
+      __atomic_store_n(&cap->bytes[dev], (int)bytes, __ATOMIC_RELEASE);
+    }
   }
   return EM_OK;
 }

@@ -16,12 +16,13 @@ import torch
 
 from espnet_amd import lib as L
 from espnet_amd.nets.scorer_interface import BatchScorerInterface
+from espnet_amd.packing import PackedModule
 
 
 _KINDS = {"LSTM": L.EM_LM_LSTM, "GRU": L.EM_LM_GRU, "RNN_TANH": L.EM_LM_RNN_TANH, "RNN_RELU": L.EM_LM_RNN_RELU}
 
 
-class SequentialRNNLM(torch.nn.Module, BatchScorerInterface):
+class SequentialRNNLM(PackedModule, BatchScorerInterface):
     def __init__(self, vocab_size: int, unit: int = 650, nhid: Optional[int] = None, nlayers: int = 2,
                  dropout_rate: float = 0.0, tie_weights: bool = False, rnn_type: str = "lstm",
                  ignore_id: int = 0, compute_dtype: str = "bfloat16"):
@@ -45,19 +46,10 @@ class SequentialRNNLM(torch.nn.Module, BatchScorerInterface):
             if nhid != unit:
                 raise ValueError("When using the tied flag, nhid must be equal to emsize")
             self.decoder.weight = self.encoder.weight
-        self._packed = None
 
     @property
     def em_dtype(self) -> int:
         return L.DTYPES[self.compute_dtype]
-
-    def invalidate(self):
-        self._packed = None
-
-    def load_state_dict(self, state_dict, strict: bool = True, **kw):
-        r = super().load_state_dict(state_dict, strict=strict, **kw)
-        self.invalidate()
-        return r
 
     @staticmethod
     def _pad(v: int) -> int:
@@ -76,34 +68,21 @@ class SequentialRNNLM(torch.nn.Module, BatchScorerInterface):
         return dict(lm_e=(n, eu), lm_logp=(n, V), rnn_hs=(3, self.nlayers, n, d), rnn_cs=(3, self.nlayers, n, d),
                     rnn_hin=(self.nlayers, n, d), rnn_gates=(n, self.gate_blocks * self.nhid), run_slm=(n,), end_slm=(B, cap))
 
-    def pack(self, device, pe_len: int = 0):
-        dev = torch.device(device)
-        act = torch.bfloat16 if self.em_dtype == L.EM_BF16 else torch.float32
+    def _build_pack(self, pk):
+        A, F = pk.A, pk.F
         d, eu, nh = self._pad(self.nhid), self._pad(self.unit), self.nhid
-        keep = []
 
         def padk(t, k):  # zero-pad the contraction dimension
             out = torch.zeros(t.size(0), k, dtype=torch.float32)
             out[:, : t.size(1)] = t.detach().to(torch.float32)
             return out
 
-        def A(t):
-            t = t.contiguous().to(act).to(dev)
-            keep.append(t)
-            return t
-
-        def F(t):
-            t = t.detach().to(torch.float32).contiguous().to(dev)
-            keep.append(t)
-            return t
-
         w = L.EmLmWeights()
         w.kind, w.d, w.nhid, w.embed_unit, w.num_blocks, w.vocab = _KINDS[self.rnn_type], d, nh, eu, self.nlayers, self.vocab_size
         w.heads = w.ff = 0
         top = dict(embed=F(padk(self.encoder.weight, eu)), out_w=A(padk(self.decoder.weight, d)),
                    out_b=F(self.decoder.bias))
-        for k, v in top.items():
-            setattr(w, k, v.data_ptr())
+        pk.fill(w, top)
         layers = (L.EmRnnLayer * self.nlayers)()
         for l in range(self.nlayers):
             w_ih, w_hh = (getattr(self.rnn, f"weight_{k}_l{l}").detach().float().cpu() for k in ("ih", "hh"))
@@ -117,18 +96,9 @@ class SequentialRNNLM(torch.nn.Module, BatchScorerInterface):
                 b = torch.cat([b_ih[: 2 * nh] + b_hh[: 2 * nh], b_ih[2 * nh:], b_hh[2 * nh:]])
             else:
                 b = b_ih + b_hh
-            lt = dict(w_ih=A(padk(w_ih, eu if l == 0 else d)), w_hh=A(padk(w_hh, d)), bias=F(b))
-            for k, v in lt.items():
-                setattr(layers[l], k, v.data_ptr())
+            pk.fill(layers[l], dict(w_ih=A(padk(w_ih, eu if l == 0 else d)), w_hh=A(padk(w_hh, d)), bias=F(b)))
         w.rnn = C.cast(layers, C.POINTER(L.EmRnnLayer))
-        self._packed = dict(w=w, layers=layers, keep=keep, device=dev, dtype=self.em_dtype, pe_len=1 << 30)
-        return self._packed
-
-    def ensure_packed(self, device, pe_len: int = 0):
-        p = self._packed
-        if p is None or p["device"] != device or p["dtype"] != self.em_dtype:
-            p = self.pack(device)
-        return p
+        pk.w, pk.layers = w, layers
 
     # ------------------------------------------------------------------ scorer interface (one call per step)
     @torch.no_grad()
@@ -141,7 +111,7 @@ class SequentialRNNLM(torch.nn.Module, BatchScorerInterface):
         L.require_gpu(xs, "xs")
         dev = xs.device
         n = ys.size(0)
-        act = torch.bfloat16 if self.em_dtype == L.EM_BF16 else torch.float32
+        act = self.act_dtype
         d = self._pad(self.nhid)
         hs = torch.zeros(3, self.nlayers, n, d, dtype=act, device=dev)
         cs = torch.zeros(3, self.nlayers, n, d, dtype=torch.float32, device=dev)
@@ -164,7 +134,7 @@ class SequentialRNNLM(torch.nn.Module, BatchScorerInterface):
         L.require_gpu(input, "input")
         dev = input.device
         n, Lc = input.shape
-        act = torch.bfloat16 if self.em_dtype == L.EM_BF16 else torch.float32
+        act = self.act_dtype
         d = self._pad(self.nhid)
         out = torch.empty(n, Lc, self.vocab_size, dtype=torch.float32, device=dev)
         states = hidden

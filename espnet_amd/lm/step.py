@@ -14,9 +14,9 @@ _ACT = {"lm_e", "lm_xn", "lm_qkv", "lm_ctx", "lm_h", "lm_k", "lm_v", "rnn_hs", "
 def lm_step(lm, dev, n: int, Lmax: int, i: int, tok: torch.Tensor, preset: dict, log_softmax: bool = True):
     """tok [Lmax][n] int32 token table (row i = the tokens consumed now); preset = already filled buffers
     (lm_k / lm_v or rnn_hs / rnn_cs).  Returns (log-probs (n, V) f32, dict of all buffers)."""
-    pk = lm.ensure_packed(dev, Lmax + 1)
+    pk = lm.packed(dev, Lmax + 1)
     V = lm.vocab_size
-    act = torch.bfloat16 if lm.em_dtype == L.EM_BF16 else torch.float32
+    act = pk.act
     t = dict(preset)
     for name, shp in lm.search_buffers(n, V, Lmax, 1, 1).items():
         if name in t or name in ("run_slm", "end_slm"):
@@ -31,9 +31,9 @@ def lm_step(lm, dev, n: int, Lmax: int, i: int, tok: torch.Tensor, preset: dict,
     bs = L.EmSearchBuffers()
     for name, v in t.items():
         setattr(bs, name, v.data_ptr())
-    bs.lm = C.addressof(pk["w"])
+    bs.lm = C.addressof(pk.w)
     lib = L.load()
-    L.check(lib.em_lm_step(lm.em_dtype, C.byref(p), C.byref(bs), i, L.current_stream_ptr()), "em_lm_step")
+    L.check(lib.em_lm_step(pk.dtype, C.byref(p), C.byref(bs), i, L.current_stream_ptr()), "em_lm_step")
     logp = t["lm_logp"]
     if log_softmax:
         L.check(lib.em_log_softmax_rows_f32(L.ptr(logp), n, V, L.current_stream_ptr()),

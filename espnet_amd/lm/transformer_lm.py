@@ -17,6 +17,7 @@ from espnet_amd import lib as L
 from espnet_amd.asr.decoder.transformer_decoder import abs_pos_table
 from espnet_amd.asr.encoder.conformer_encoder import LayerNorm, _PositionwiseFeedForward
 from espnet_amd.nets.scorer_interface import BatchScorerInterface
+from espnet_amd.packing import PackedModule
 
 
 class _MultiHeadedAttention(torch.nn.Module):
@@ -51,7 +52,9 @@ class _Encoder(torch.nn.Module):
         self.after_norm = LayerNorm(d)
 
 
-class TransformerLM(torch.nn.Module, BatchScorerInterface):
+class TransformerLM(PackedModule, BatchScorerInterface):
+    pe_min = 1024  # rows of the positional table a pack carries at least (more when a search needs them)
+
     def __init__(self, vocab_size: int, pos_enc: Optional[str] = None, embed_unit: int = 128,
                  att_unit: int = 256, head: int = 2, unit: int = 1024, layer: int = 4,
                  dropout_rate: float = 0.1, positional_dropout_rate: float = 0.1,
@@ -67,19 +70,10 @@ class TransformerLM(torch.nn.Module, BatchScorerInterface):
         self.embed = torch.nn.Embedding(vocab_size, embed_unit)
         self.encoder = _Encoder(embed_unit, att_unit, unit, layer)
         self.decoder = torch.nn.Linear(att_unit, vocab_size)
-        self._packed = None
 
     @property
     def em_dtype(self) -> int:
         return L.DTYPES[self.compute_dtype]
-
-    def invalidate(self):
-        self._packed = None
-
-    def load_state_dict(self, state_dict, strict: bool = True, **kw):
-        r = super().load_state_dict(state_dict, strict=strict, **kw)
-        self.invalidate()
-        return r
 
     def search_key(self):
         return ("transformer", self.att_unit, self.unit, self.layer, self.embed_unit)
@@ -91,24 +85,11 @@ class TransformerLM(torch.nn.Module, BatchScorerInterface):
                     lm_x=(n, dl), lm_logp=(n, V), lm_k=(self.layer, Lmax, n, dl), lm_v=(self.layer, Lmax, n, dl),
                     run_slm=(n,), end_slm=(B, cap))
 
-    def pack(self, device, pe_len: int = 1024):
-        dev = torch.device(device)
-        act = torch.bfloat16 if self.em_dtype == L.EM_BF16 else torch.float32
+    def _build_pack(self, pk):
+        A, F = pk.A, pk.F
         kmult = 64 if self.em_dtype == L.EM_BF16 else 32
         if self.embed_unit % kmult:
             raise NotImplementedError(f"embed_unit must be a multiple of {kmult} in {self.compute_dtype} mode")
-        keep = []
-
-        def A(t):
-            t = t.detach().to(torch.float32).contiguous().to(act).to(dev)
-            keep.append(t)
-            return t
-
-        def F(t):
-            t = t.detach().to(torch.float32).contiguous().to(dev)
-            keep.append(t)
-            return t
-
         w = L.EmLmWeights()
         w.d, w.heads, w.ff, w.num_blocks = self.att_unit, self.head, self.unit, self.layer
         w.vocab, w.embed_unit = self.vocab_size, self.embed_unit
@@ -118,9 +99,8 @@ class TransformerLM(torch.nn.Module, BatchScorerInterface):
                    after_norm_g=F(e.after_norm.weight), after_norm_b=F(e.after_norm.bias),
                    out_w=A(self.decoder.weight), out_b=F(self.decoder.bias))
         if self.pos_enc == "sinusoidal":
-            top["pe"] = F(abs_pos_table(pe_len, self.att_unit))
-        for k, v in top.items():
-            setattr(w, k, v.data_ptr())
+            top["pe"] = F(abs_pos_table(pk.pe_len, self.att_unit))
+        pk.fill(w, top)
         layers = (L.EmLmLayer * self.layer)()
         for i, l in enumerate(e.encoders):
             sa, ff = l.self_attn, l.feed_forward
@@ -130,17 +110,9 @@ class TransformerLM(torch.nn.Module, BatchScorerInterface):
                       bqkv=F(torch.cat([sa.linear_q.bias, sa.linear_k.bias, sa.linear_v.bias], 0)),
                       wout=A(sa.linear_out.weight), bout=F(sa.linear_out.bias),
                       w1=A(ff.w_1.weight), b1=F(ff.w_1.bias), w2=A(ff.w_2.weight), b2=F(ff.w_2.bias))
-            for k, v in lt.items():
-                setattr(layers[i], k, v.data_ptr())
+            pk.fill(layers[i], lt)
         w.layers = C.cast(layers, C.POINTER(L.EmLmLayer))
-        self._packed = dict(w=w, layers=layers, keep=keep, device=dev, dtype=self.em_dtype, pe_len=pe_len)
-        return self._packed
-
-    def ensure_packed(self, device, pe_len: int):
-        p = self._packed
-        if p is None or p["device"] != device or p["dtype"] != self.em_dtype or p["pe_len"] < pe_len:
-            p = self.pack(device, max(1024, pe_len))
-        return p
+        pk.w, pk.layers = w, layers
 
     # ------------------------------------------------------------------ scorer interface (one call per step)
     @torch.no_grad()
@@ -154,7 +126,7 @@ class TransformerLM(torch.nn.Module, BatchScorerInterface):
         dev = xs.device
         n, Lc = ys.shape
         pos, Lmax = Lc - 1, Lc + 1
-        act = torch.bfloat16 if self.em_dtype == L.EM_BF16 else torch.float32
+        act = self.act_dtype
         kv = torch.zeros(2, self.layer, Lmax, n, self.att_unit, dtype=act, device=dev)
         if pos > 0:
             if states is None or any(s is None for s in states):
@@ -176,7 +148,7 @@ class TransformerLM(torch.nn.Module, BatchScorerInterface):
         L.require_gpu(input, "input")
         dev = input.device
         n, Lc = input.shape
-        act = torch.bfloat16 if self.em_dtype == L.EM_BF16 else torch.float32
+        act = self.act_dtype
         kv = torch.zeros(2, self.layer, Lc + 1, n, self.att_unit, dtype=act, device=dev)
         tok = torch.zeros(Lc + 1, n, dtype=torch.int32, device=dev)
         tok[:Lc] = input.t().to(torch.int32)

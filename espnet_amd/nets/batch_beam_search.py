@@ -66,6 +66,10 @@ class BeamSearch:
         self.normalize_length = normalize_length
         if not any(k in self.scorers for k in ("decoder", "ctc", "lm")):
             raise ValueError("beam search needs the decoder, the ctc and/or the lm scorer")
+        dec, ctc_sc, lm = self.scorers.get("decoder"), self.scorers.get("ctc"), self.scorers.get("lm")
+        head = dec if dec is not None else (ctc_sc.ctc if ctc_sc is not None else None)
+        if lm is not None and head is not None and lm.em_dtype != head.em_dtype:
+            lm.compute_dtype = "bfloat16" if head.em_dtype == L.EM_BF16 else "float32"  # the search runs in ONE dtype
         self._bufs = {}
         self._graphs = {}
         self.max_live_shapes = 3  # buffer sets (and their captured graphs) kept for recurring batch shapes
@@ -92,6 +96,14 @@ class BatchBeamSearch(BeamSearch):
         c = copy.copy(self)
         c._bufs, c._graphs = {}, {}
         return c
+
+    def _serials(self, *packs):
+        """Serials of the packs a graph is captured against (the last element of its `_graphs` key).  Graphs captured
+        against other packs - superseded ones - are dropped: they, and the packs they hold, are never replayed again."""
+        ser = tuple(pk.serial if pk is not None else 0 for pk in packs)
+        for gk in [gk for gk in self._graphs if gk[-1] != ser]:
+            del self._graphs[gk]
+        return ser
 
     # ------------------------------------------------------------------ buffers
     def _alloc(self, dev, act, B, W, V, T, Tpad, NC, Lmax, cap, d, ff, nl, lm=None, online=False):
@@ -185,9 +197,6 @@ class BatchBeamSearch(BeamSearch):
         ctc_sc = self.scorers.get("ctc")
         lm = self.scorers.get("lm")
         em_dtype = dec.em_dtype if dec is not None else (ctc_sc.ctc.em_dtype if ctc_sc is not None else lm.em_dtype)
-        if lm is not None and lm.em_dtype != em_dtype:
-            lm.compute_dtype = "bfloat16" if em_dtype == L.EM_BF16 else "float32"
-            lm.invalidate()
         act = torch.bfloat16 if em_dtype == L.EM_BF16 else torch.float32
         enc_act = enc_act.to(act).contiguous()
         # length bounds per utterance (beam_search.py:414-429 with inp.shape[0] = olens[b])
@@ -221,7 +230,11 @@ class BatchBeamSearch(BeamSearch):
         bufs["xlens"].copy_(torch.tensor(olens, dtype=torch.int32))
         bufs["maxlens"].copy_(torch.tensor(maxlens, dtype=torch.int32))
         bufs["minlens"].copy_(torch.tensor(minlens, dtype=torch.int32))
-        ctc_pk = ctc_sc.ctc._pack(dev) if ctc_sc is not None else None
+        # the packs this search reads, held until it ends (a module may build newer ones meanwhile)
+        ctc_pk = ctc_sc.ctc.packed(dev) if ctc_sc is not None else None
+        lm_pk = lm.packed(dev, Lmax) if lm is not None else None
+        dec_pk = dec.packed(dev, Lmax) if dec is not None else None
+        _check_lm_dtype(lm_pk, em_dtype)
         p = L.EmSearchParams(B=B, W=W, V=V, T=T, Tpad=Tpad, S=S, NC=NC, Lmax=Lmax, end_cap=cap,
                              sos=self.sos, eos=self.eos, blank=0,
                              use_end_detect=1 if maxlenratio == 0.0 else 0,
@@ -235,17 +248,15 @@ class BatchBeamSearch(BeamSearch):
             setattr(bs, name, bufs[name].data_ptr() if name in bufs else None)
         if not self.use_hipgraph:
             bs.step = None
-        lmw = lm.ensure_packed(dev, Lmax)["w"] if lm is not None else None
-        if lmw is not None:
-            bs.lm = C.addressof(lmw)
-        dw = dec.ensure_packed(dev, Lmax)["w"] if dec is not None else None
-        dwp = C.byref(dw) if dw is not None else None
+        if lm_pk is not None:
+            bs.lm = C.addressof(lm_pk.w)
+        dwp = C.byref(dec_pk.w) if dec_pk is not None else None
         stream = L.current_stream_ptr()
 
         def init():
             L.check(lib.em_search_init(em_dtype, C.byref(p), dwp, C.byref(bs), L.ptr(enc_act), d,
-                                       L.ptr(ctc_pk["w"]) if ctc_pk else None,
-                                       L.ptr(ctc_pk["b"]) if ctc_pk else None,
+                                       L.ptr(ctc_pk.weight) if ctc_pk else None,
+                                       L.ptr(ctc_pk.bias) if ctc_pk else None,
                                        L.current_stream_ptr()), "em_search_init")
 
         def steps(i0, i1):
@@ -257,9 +268,8 @@ class BatchBeamSearch(BeamSearch):
         if self.use_hipgraph:
             # One hipGraph = K search steps (~75 launches each).  Every step-dependent kernel reads the
             # step index from device memory, so the same graph is replayed ceil(imax / K) times; steps
-            # past the end are no-ops.  The graph is tied to the buffer set and the parameter block.
-            gkey = (id(bufs), bytes(p), em_dtype, id(dec._packed) if dec is not None else 0,
-                    id(lm._packed) if lm is not None else 0)
+            # past the end are no-ops.  The graph is tied to the buffer set and the packs.
+            gkey = (id(bufs), bytes(p), em_dtype, self._serials(dec_pk, lm_pk))
             g = self._graphs.get(gkey)
             if g is None:
                 steps(0, 1)  # warm-up outside capture (one-time attribute calls, lazy module loads)
@@ -267,7 +277,7 @@ class BatchBeamSearch(BeamSearch):
                 g = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(g):
                     steps(0, K)
-                self._graphs[gkey] = (g, p, bs, lmw)  # keep the argument blocks alive with the graph
+                self._graphs[gkey] = (g, p, bs, dec_pk, lm_pk)  # keep the argument blocks and packs alive with the graph
                 init()  # the warm-up step advanced the search state: start over
             else:
                 g = g[0]
@@ -353,6 +363,11 @@ class BatchBeamSearch(BeamSearch):
         return nbest
 
     __call__ = forward
+
+
+def _check_lm_dtype(lm_pk, em_dtype):
+    if lm_pk is not None and lm_pk.dtype != em_dtype:  # (aligned where the search is built: BeamSearch.__init__)
+        raise ValueError("the LM's compute_dtype differs from the decoder's: build the search after setting it")
 
 
 class SearchLanes:

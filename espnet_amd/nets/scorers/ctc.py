@@ -57,11 +57,11 @@ class CTCPrefixScorer(BatchPartialScorerInterface):
         ctc = self.ctc
         T, d = x.shape
         act = ctc._to_act(x.unsqueeze(0))
-        p = ctc._pack(x.device)
+        p = ctc.packed(x.device)
         V = ctc.odim
         lpT = torch.empty(V, T, dtype=torch.float32, device=x.device)
         lib = L.load()
-        L.check(lib.em_ctc_log_probs_t(ctc.em_dtype, L.ptr(act), 1, T, d, L.ptr(p["w"]), L.ptr(p["b"]), V,
+        L.check(lib.em_ctc_log_probs_t(ctc.em_dtype, L.ptr(act), 1, T, d, L.ptr(p.weight), L.ptr(p.bias), V,
                                        L.ptr(lpT), L.current_stream_ptr()), "em_ctc_log_probs_t")
         xlens = torch.tensor([T], dtype=torch.int32, device=x.device)
         r0 = torch.empty(1, T, 2, dtype=torch.float32, device=x.device)

@@ -259,7 +259,7 @@ def test_ebranchformer_512_row_block_ffn_matches_per_operator_and_oracle():
             os.environ[k] = v
         lib.em_dev_switches_reload()
         try:
-            model.encoder._packed = None  # (pack again: nothing is cached across the switch)
+            model.encoder.invalidate()  # (pack again: nothing is cached across the switch)
             st = model.encode_device(wav, lens)
             return st.enc_out.float().cpu(), st.olens
         finally:

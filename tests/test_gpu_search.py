@@ -297,7 +297,10 @@ def test_search_lanes_equal_searches_run_alone(dtype):
     """Round 6, SearchLanes: several joint searches in flight on as many HIP streams (each lane its own buffer set and
     hipGraph over the SAME scorers) return, bit for bit, what each search returns run alone - five different ragged
     batches dealt over two lanes and over three, more batches than lanes (a lane is reused), searches of different lengths
-    in flight together (the short one finishes while the long one is mid-way); the same with a host thread per lane (two and four)."""
+    in flight together (the short one finishes while the long one is mid-way); the same with a host thread per lane (two and four).
+    Then the decode CLI's set-up: threaded lanes over a freshly built search (nothing packed yet) and its clones, all started
+    before any is waited for, one of them with a batch longer than the decoder's 1 024-row positional table - its search packs
+    the decoder again while the other lanes' searches are in flight on the previous pack."""
     from espnet_amd.nets.batch_beam_search import SearchLanes
 
     g = load_golden("tiny_beam4_early_eos")
@@ -331,14 +334,31 @@ def test_search_lanes_equal_searches_run_alone(dtype):
                         got[r[0]] = r[1]
                         unit_of[k] = None
         for u, want in enumerate(alone):
-            assert len(got[u]) == len(want)
-            for hw, hg in zip(want, got[u]):
-                assert len(hw) == len(hg) > 0
-                for a, b in zip(hw, hg):
-                    assert a.yseq.tolist() == b.yseq.tolist()
-                    assert float(a.score) == float(b.score)
-                    assert {k: float(v) for k, v in a.scores.items()} == {k: float(v) for k, v in b.scores.items()}
+            _same_nbest(want, got[u])
         lanes.close()
+    work = batches[:3] + [((torch.randn(1, 1056, d) * 0.5).to(batches[0][0].dtype).cuda(), [1056])]  # Lmax = 1 058
+    alone = [build_search(g, sd, dtype).search_batch(e, l) for e, l in work]
+    torch.cuda.synchronize()
+    bs = build_search(g, sd, dtype)
+    lanes = SearchLanes([bs] + [bs.clone() for _ in work[1:]], torch.device("cuda"), threaded=True)
+    for k, (e, l) in enumerate(work):
+        lanes.start(k, e, l, tag=k)
+    for k, want in enumerate(alone):
+        tag, nbest = lanes.wait(k)
+        assert tag == k
+        _same_nbest(want, nbest)
+    lanes.close()
+
+
+def _same_nbest(want, got):
+    """The n-best lists of a batch, bit for bit: tokens, total and per-scorer scores."""
+    assert len(got) == len(want)
+    for hw, hg in zip(want, got):
+        assert len(hw) == len(hg) > 0
+        for a, b in zip(hw, hg):
+            assert a.yseq.tolist() == b.yseq.tolist()
+            assert float(a.score) == float(b.score)
+            assert {k: float(v) for k, v in a.scores.items()} == {k: float(v) for k, v in b.scores.items()}
 
 
 def test_search_structure_invariants():

@@ -23,7 +23,7 @@ def main():
         input_size=80, compute_dtype="bfloat16", output_size=256, attention_heads=4, linear_units=2048, num_blocks=12,
         input_layer="conv2d", normalize_before=True, activation_type="swish", macaron_style=True, use_cnn_module=True,
         cnn_module_kernel=15, block_size=40, hop_size=16, look_ahead=16, init_average=True, ctx_pos_enc=True).to(dev).eval()
-    pk = enc._ensure_packed(dev)
+    pk = enc.packed(dev)
     lib = L.load()
     Lb, d = 42, 256
 
@@ -33,11 +33,11 @@ def main():
         x = x0.clone()
         past = torch.randn(n, 12, d, device=dev) * 0.1
         nxt = torch.empty_like(past)
-        ws = enc._workspace(dev, n, Lb)
+        ws = enc._workspace(pk, dev, n, Lb)
         st = L.current_stream_ptr()
 
         def call():
-            L.check(lib.em_cb_encode_blocks_batch(enc.em_dtype, C.byref(pk["w"]), L.ptr(x), n, 1, Lb, 1, L.ptr(past), L.ptr(nxt),
+            L.check(lib.em_cb_encode_blocks_batch(enc.em_dtype, C.byref(pk.w), L.ptr(x), n, 1, Lb, 1, L.ptr(past), L.ptr(nxt),
                                                   L.ptr(ws), ws.numel(), st), "em_cb_encode_blocks_batch")
 
         for _ in range(5):
