@@ -67,8 +67,8 @@ class Speech2Text:
         for k, v in unsupported.items():
             if v not in (None, False, {}, [], 0.99, 5, -1, ["Linear"], "qint8"):
                 raise NotImplementedError(f"Speech2Text({k}={v!r}) is outside the MI355X hot path")
-        if transducer_conf is not None or ngram_file is not None or streaming:
-            raise NotImplementedError("transducer / n-gram scorers and streaming=True (use Speech2TextStreaming): "
+        if transducer_conf is not None or streaming:
+            raise NotImplementedError("transducer scorers and streaming=True (use Speech2TextStreaming): "
                                       "SURVEY.md §8(f) 'next' rows")
         if not str(device).startswith("cuda"):
             raise RuntimeError("espnet_amd.Speech2Text runs on an MI355X only (device='cuda'); no CPU fallback")
@@ -94,7 +94,8 @@ class Speech2Text:
             self.tokenizer = build_tokenizer(token_type=token_type, bpemodel=bpemodel)
         self.converter = TokenIDConverter(token_list=token_list)
         self.beam_search = None
-        if not ctc_greedy:
+        self.lm = self.ngram = None
+        if not ctc_greedy:  # (greedy CTC decodes without scorers: an n-gram does not apply there)
             from espnet_amd.nets.batch_beam_search import build_beam_search
 
             lm = None
@@ -104,12 +105,18 @@ class Speech2Text:
                 lm_model, _ = LMTask.build_model_from_file(lm_train_config, lm_file, device, compute_dtype=dtype)
                 lm = lm_model.lm
             self.lm = lm
+            if ngram_file is not None:  # asr_inference.py:193-207
+                from espnet_amd.nets.scorers.ngram import NgramFullScorer, NgramPartScorer
+
+                cls = NgramFullScorer if ngram_scorer == "full" else NgramPartScorer
+                self.ngram = cls(ngram_file, token_list)
             self.beam_search = build_beam_search(
                 asr_model, beam_size=beam_size, ctc_weight=ctc_weight, penalty=penalty,
                 lm_weight=lm_weight if lm is not None else 0.0, token_list=token_list,
-                normalize_length=normalize_length, lm=lm)
+                normalize_length=normalize_length, lm=lm, ngram=self.ngram,
+                ngram_weight=ngram_weight if self.ngram is not None else 0.0)
         m = asr_model
-        pack_modules(device, [m.frontend, m.encoder, m.ctc] + ([] if ctc_greedy else [m.decoder, self.lm]))
+        pack_modules(device, [m.frontend, m.encoder, m.ctc] + ([] if ctc_greedy else [m.decoder, self.lm, self.ngram]))
 
     # ------------------------------------------------------------------ single utterance (reference API)
     @torch.no_grad()

@@ -212,3 +212,20 @@ int em_gemm_mid_frag(int epilogue, int frag, const EmGemmArgs* p, void* stream);
 // em_dec_self_attention)
 int em_dec_self_attention_tree_bf16(const void* qkv, void* kc, void* vc, const int* anc, const int* anc_odd, int n, int d,
                                     int heads, int Lmax, int pos, const int* pos_dev, int W, void* ctx, void* stream);
+
+// csrc/ngram.hip: the n-gram scorer inside the fused search (csrc/search.hip).  ngram_search_step: the rows of step i advance
+// their context nodes from their parents' (st_a / st_b by step parity) and, in full mode (logp != NULL), score all V tokens;
+// ngram_search_part: part mode, the pre-beam candidates' scores (cand_ngram) and their rebuilt totals (cand_total).
+struct NgSearchArgs {
+  int32_t n, W, V, Lmax, S, NC;
+  float w_ctc, w_ngram;
+  const int32_t* step;  // graph-mode step counter, or NULL (then i is the host's)
+  const int32_t *tok, *parent, *alive, *done;
+  int32_t *st_a, *st_b;
+  float* logp;
+  const int32_t* cand_tok;
+  const float *cand_full, *cand_psi, *s_prev, *run_score;
+  float *cand_ngram, *cand_total;
+};
+int ngram_search_step(const EmNgramModel* m, const NgSearchArgs& a, int i, void* stream);
+int ngram_search_part(const EmNgramModel* m, const NgSearchArgs& a, int i, void* stream);

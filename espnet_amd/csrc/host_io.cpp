@@ -577,3 +577,299 @@ extern "C" int em_wav_load_rows(const char* const* paths, const EmWavInfo* info,
   });
   return worst.load();
 }
+
+// ---------------------------------------------------------------------------------------------- ARPA (n-gram LM)
+// Plain-text ARPA back-off language model (the format kenlm's lmplz / build_binary read and asr.sh's `use_ngram` stage
+// writes beside the binary), read into the sorted trie of EmNgramModel: order-1 entry i is word id i (file order of the
+// 1-grams, <unk> appended with log10 p = -100 when the file has none, as kenlm does); the entries of order k + 1 are sorted
+// by (index of their k-word prefix in order k, word id), so the successors of an entry are one contiguous range.
+// Values are parsed from their decimal text to f32 (strtof), a missing back-off column reads as 0.
+#include <stdlib.h>
+
+#include <algorithm>
+#include <string>
+#include <string_view>
+#include <unordered_map>
+
+#define EM_TRY_HOST(expr)           \
+  do {                              \
+    const int rc__ = (expr);        \
+    if (rc__ != EM_OK) return rc__; \
+  } while (0)
+
+namespace {
+
+struct ArpaText {
+  std::vector<char> buf;  // the whole file, NUL-terminated
+  const char* p = nullptr;
+  const char* end = nullptr;
+  int open(const char* path) {
+    FILE* f = fopen(path, "rb");
+    if (!f) return EM_ERR_IO;
+    if (fseek(f, 0, SEEK_END) != 0) {
+      fclose(f);
+      return EM_ERR_IO;
+    }
+    const long n = ftell(f);
+    if (n < 0 || fseek(f, 0, SEEK_SET) != 0) {
+      fclose(f);
+      return EM_ERR_IO;
+    }
+    buf.resize((size_t)n + 1);
+    const size_t got = n > 0 ? fread(buf.data(), 1, (size_t)n, f) : 0;
+    fclose(f);
+    if (got != (size_t)n) return EM_ERR_IO;
+    buf[(size_t)n] = 0;
+    p = buf.data();
+    end = p + n;
+    // kenlm's binary format ("mmap lm ..." magic) and gzip are not plain text
+    if ((n >= 8 && memcmp(p, "mmap lm ", 8) == 0) || (n >= 2 && (unsigned char)p[0] == 0x1f && (unsigned char)p[1] == 0x8b))
+      return EM_ERR_UNSUPPORTED;
+    return EM_OK;
+  }
+  // next line with surrounding whitespace trimmed; false at the end of the file
+  bool line(const char*& b, const char*& e) {
+    if (p >= end) return false;
+    const char* q = (const char*)memchr(p, '\n', (size_t)(end - p));
+    const char* le = q ? q : end;
+    b = p;
+    e = le;
+    p = q ? q + 1 : end;
+    while (b < e && (*b == ' ' || *b == '\t' || *b == '\r')) ++b;
+    while (e > b && (e[-1] == ' ' || e[-1] == '\t' || e[-1] == '\r')) --e;
+    return true;
+  }
+};
+
+inline bool is_ws(char c) { return c == ' ' || c == '\t'; }
+
+inline bool line_is(const char* b, const char* e, const char* s) {
+  const size_t n = strlen(s);
+  return (size_t)(e - b) == n && memcmp(b, s, n) == 0;
+}
+
+struct ArpaHeader {
+  int order = 0;
+  int64_t count[EM_NGRAM_MAX_ORDER + 1] = {};
+};
+
+// "\data\" and its "ngram k=count" lines; leaves t at the first section header
+int arpa_header(ArpaText& t, ArpaHeader& h) {
+  const char *b, *e;
+  bool seen = false;
+  while (t.line(b, e)) {
+    if (line_is(b, e, "\\data\\")) {
+      seen = true;
+      break;
+    }
+  }
+  if (!seen) return EM_ERR_UNSUPPORTED;  // not an ARPA file
+  const char* mark = t.p;
+  while (t.line(b, e)) {
+    if (b == e) {
+      mark = t.p;
+      continue;
+    }
+    if (e - b < 6 || memcmp(b, "ngram ", 6) != 0) {
+      t.p = mark;
+      break;
+    }
+    char* q;
+    const long k = strtol(b + 6, &q, 10);
+    if (q >= e || *q != '=') return EM_ERR_BAD_ARG;
+    const long long c = strtoll(q + 1, nullptr, 10);
+    if (k < 1 || c < 0 || c > 0x7ffffff0LL) return EM_ERR_BAD_ARG;
+    if (k > EM_NGRAM_MAX_ORDER) return EM_ERR_UNSUPPORTED;  // kenlm's default maximum order
+    h.count[k] = c;
+    if (k > h.order) h.order = (int)k;
+    mark = t.p;
+  }
+  if (h.order < 1) return EM_ERR_BAD_ARG;
+  return EM_OK;
+}
+
+// advance to the "\k-grams:" header of order k
+int arpa_section(ArpaText& t, int k) {
+  char want[32];
+  snprintf(want, sizeof want, "\\%d-grams:", k);
+  const char *b, *e;
+  while (t.line(b, e)) {
+    if (b == e) continue;
+    return line_is(b, e, want) ? EM_OK : EM_ERR_BAD_ARG;
+  }
+  return EM_ERR_BAD_ARG;
+}
+
+// one entry line: prob, k words (as views), optional back-off
+struct ArpaEntry {
+  float prob, bow;
+  std::string_view w[EM_NGRAM_MAX_ORDER];
+};
+int arpa_entry(ArpaText& t, int k, ArpaEntry& en) {
+  const char *b, *e;
+  do {
+    if (!t.line(b, e)) return EM_ERR_BAD_ARG;
+  } while (b == e);
+  char* q;
+  en.prob = strtof(b, &q);
+  if (q == b || q > e) return EM_ERR_BAD_ARG;
+  const char* s = q;
+  for (int j = 0; j < k; ++j) {
+    while (s < e && is_ws(*s)) ++s;
+    const char* w0 = s;
+    while (s < e && !is_ws(*s)) ++s;
+    if (s == w0) return EM_ERR_BAD_ARG;
+    en.w[j] = std::string_view(w0, (size_t)(s - w0));
+  }
+  while (s < e && is_ws(*s)) ++s;
+  en.bow = 0.f;
+  if (s < e) {
+    en.bow = strtof(s, &q);
+    if (q == s) return EM_ERR_BAD_ARG;
+  }
+  return EM_OK;
+}
+
+// successor of node `e` of order k (0-based index k) with word w, or -1
+inline int32_t arpa_find(int32_t* const* wid, int32_t* const* next, int k, int32_t e, int32_t w) {
+  int32_t lo = next[k][e], hi = next[k][e + 1];
+  const int32_t* a = wid[k + 1];
+  while (lo < hi) {
+    const int32_t mid = lo + ((hi - lo) >> 1);
+    if (a[mid] < w) lo = mid + 1;
+    else hi = mid;
+  }
+  return (lo < next[k][e + 1] && a[lo] == w) ? lo : -1;
+}
+
+int arpa_count(const char* path, int32_t* order, int32_t* counts, int64_t* vocab_bytes) {
+  ArpaText t;
+  EM_TRY_HOST(t.open(path));
+  ArpaHeader h;
+  EM_TRY_HOST(arpa_header(t, h));
+  EM_TRY_HOST(arpa_section(t, 1));
+  int64_t bytes = 0;
+  bool unk = false;
+  ArpaEntry en;
+  for (int64_t i = 0; i < h.count[1]; ++i) {
+    EM_TRY_HOST(arpa_entry(t, 1, en));
+    bytes += (int64_t)en.w[0].size() + 1;
+    unk |= en.w[0] == "<unk>";
+  }
+  *order = h.order;
+  for (int k = 0; k < EM_NGRAM_MAX_ORDER; ++k) counts[k] = k < h.order ? (int32_t)h.count[k + 1] : 0;
+  if (!unk) {
+    counts[0] += 1;
+    bytes += 6;
+  }
+  *vocab_bytes = bytes;
+  return EM_OK;
+}
+
+int arpa_load(const char* path, int32_t order, const int32_t* counts, char* vocab, int32_t* const* wid,
+              float* const* prob, float* const* bow, int32_t* const* next) {
+  ArpaText t;
+  EM_TRY_HOST(t.open(path));
+  ArpaHeader h;
+  EM_TRY_HOST(arpa_header(t, h));
+  if (h.order != order) return EM_ERR_BAD_ARG;
+  EM_TRY_HOST(arpa_section(t, 1));
+  const int64_t n1 = h.count[1];
+  if (counts[0] != n1 && counts[0] != n1 + 1) return EM_ERR_BAD_ARG;
+  std::unordered_map<std::string_view, int32_t> ids;
+  ids.reserve((size_t)counts[0] * 2);
+  ArpaEntry en;
+  char* v = vocab;
+  for (int32_t i = 0; i < (int32_t)n1; ++i) {
+    EM_TRY_HOST(arpa_entry(t, 1, en));
+    if (!ids.emplace(en.w[0], i).second) return EM_ERR_BAD_ARG;  // a word twice
+    wid[0][i] = i;
+    prob[0][i] = en.prob;
+    bow[0][i] = en.bow;
+    memcpy(v, en.w[0].data(), en.w[0].size());
+    v += en.w[0].size();
+    *v++ = 0;
+  }
+  if (ids.find("<unk>") == ids.end()) {  // kenlm: "<unk>" missing -> log10 p = -100
+    if (counts[0] != n1 + 1) return EM_ERR_BAD_ARG;
+    wid[0][n1] = (int32_t)n1;
+    prob[0][n1] = -100.f;
+    bow[0][n1] = 0.f;
+    memcpy(v, "<unk>", 6);
+  } else if (counts[0] != n1) {
+    return EM_ERR_BAD_ARG;
+  }
+  std::vector<int32_t> ctx, w;
+  std::vector<float> pr, bo;
+  std::vector<uint64_t> key;
+  std::vector<int32_t> perm;
+  for (int k = 2; k <= order; ++k) {
+    const int32_t c = counts[k - 1];
+    if (c != h.count[k]) return EM_ERR_BAD_ARG;
+    EM_TRY_HOST(arpa_section(t, k));
+    ctx.resize((size_t)c);
+    w.resize((size_t)c);
+    pr.resize((size_t)c);
+    bo.resize((size_t)c);
+    key.resize((size_t)c);
+    bool sorted = true;
+    int32_t ids_k[EM_NGRAM_MAX_ORDER];
+    for (int32_t i = 0; i < c; ++i) {
+      EM_TRY_HOST(arpa_entry(t, k, en));
+      for (int j = 0; j < k; ++j) {
+        const auto it = ids.find(en.w[j]);
+        if (it == ids.end()) return EM_ERR_BAD_ARG;  // a word that is no unigram
+        ids_k[j] = it->second;
+      }
+      int32_t node = ids_k[0];  // the (k-1)-word prefix: a walk down the orders already built
+      for (int j = 1; j < k - 1 && node >= 0; ++j) node = arpa_find(wid, next, j - 1, node, ids_k[j]);
+      if (node < 0) return EM_ERR_BAD_ARG;  // its prefix is missing from the file
+      ctx[i] = node;
+      w[i] = ids_k[k - 1];
+      pr[i] = en.prob;
+      bo[i] = en.bow;
+      key[i] = ((uint64_t)(uint32_t)node << 32) | (uint32_t)w[i];
+      if (i > 0 && key[i] <= key[i - 1]) sorted = false;
+    }
+    const int32_t np = counts[k - 2];
+    int32_t* nx = next[k - 2];
+    for (int32_t e = 0; e <= np; ++e) nx[e] = 0;
+    for (int32_t i = 0; i < c; ++i) ++nx[ctx[i] + 1];
+    for (int32_t e = 0; e < np; ++e) nx[e + 1] += nx[e];
+    auto put = [&](int32_t dst, int32_t src) {
+      wid[k - 1][dst] = w[src];
+      prob[k - 1][dst] = pr[src];
+      bow[k - 1][dst] = bo[src];
+    };
+    if (sorted) {
+      for (int32_t i = 0; i < c; ++i) put(i, i);
+    } else {
+      perm.resize((size_t)c);
+      for (int32_t i = 0; i < c; ++i) perm[i] = i;
+      std::sort(perm.begin(), perm.end(), [&](int32_t a, int32_t b) { return key[a] < key[b]; });
+      for (int32_t i = 0; i < c; ++i) {
+        if (i > 0 && key[perm[i]] == key[perm[i - 1]]) return EM_ERR_BAD_ARG;  // an n-gram twice
+        put(i, perm[i]);
+      }
+    }
+  }
+  return EM_OK;
+}
+
+}  // namespace
+
+extern "C" int em_arpa_count(const char* path, int32_t* order, int32_t* counts, int64_t* vocab_bytes) {
+  if (!path || !order || !counts || !vocab_bytes) return EM_ERR_BAD_ARG;
+  return arpa_count(path, order, counts, vocab_bytes);
+}
+
+extern "C" int em_arpa_load(const char* path, int32_t order, const int32_t* counts, char* vocab, int32_t* const* wid,
+                            float* const* prob, float* const* bow, int32_t* const* next) {
+  if (!path || order < 1 || order > EM_NGRAM_MAX_ORDER || !counts || !vocab || !wid || !prob || !bow) return EM_ERR_BAD_ARG;
+  if (order > 1 && !next) return EM_ERR_BAD_ARG;
+  for (int k = 0; k < order; ++k) {
+    if (counts[k] < 0 || (counts[k] > 0 && (!wid[k] || !prob[k] || !bow[k]))) return EM_ERR_BAD_ARG;
+    if (k < order - 1 && !next[k]) return EM_ERR_BAD_ARG;
+  }
+  return arpa_load(path, order, counts, vocab, wid, prob, bow, next);
+}

@@ -71,6 +71,7 @@ __global__ void search_init_rows_kernel(Ctx c) {
   c.b.run_sctc[r] = 0.f;
   c.b.run_slen[r] = 0.f;
   if (c.b.run_slm) c.b.run_slm[r] = 0.f;
+  if (c.b.run_sngram) c.b.run_sngram[r] = 0.f;
   c.b.s_prev[r] = 0.f;
   c.b.tok[r] = c.p.sos;
   c.b.parent[r] = -1;
@@ -190,6 +191,12 @@ __global__ __launch_bounds__(256) void logsoftmax_prebeam_kernel(Ctx c, int i_ho
 #pragma unroll
     for (int k = 0; k < NV; ++k)
       if (tid + 256 * k < V) w[k] += c.p.w_lm * l[k];
+  }
+  if (c.p.w_ngram != 0.f && !c.p.ngram_part) {  // (full n-gram scorer: log10 scores of csrc/ngram.hip, after the LM)
+    const float* ng = c.b.ngram_logp + (size_t)r * V;
+#pragma unroll
+    for (int k = 0; k < NV; ++k)
+      if (tid + 256 * k < V) w[k] += c.p.w_ngram * ng[tid + 256 * k];
   }
   if (S >= V) return;
   // the <eos> slot's full score (always scored, :186-187), before the rounds knock values out
@@ -484,12 +491,14 @@ __global__ __launch_bounds__(256) void candidate_kernel(Ctx c, int i_host) {
     if (c.p.w_dec != 0.f) f = c.p.w_dec * c.b.dec_logp[(size_t)r * V + t];
     if (c.p.w_len != 0.f) f += c.p.w_len * 1.0f;
     if (c.p.w_lm != 0.f) f += c.p.w_lm * c.b.lm_logp[(size_t)r * V + t];
+    if (c.p.w_ngram != 0.f && !c.p.ngram_part) f += c.p.w_ngram * c.b.ngram_logp[(size_t)r * V + t];
     return f;
   };
   if (allv) {
     tokc = s;
     full = full_score(s);
     if (lane == 0) c.b.cand_tok[(size_t)r * NC + s] = s;
+    if (lane == 0 && c.p.ngram_part) c.b.cand_full[(size_t)r * NC + s] = full;  // (the part n-gram rebuilds the total)
   } else if (s < S) {
     tokc = c.b.cand_tok[(size_t)r * NC + s];
     full = c.b.cand_full[(size_t)r * NC + s];
@@ -776,7 +785,7 @@ __global__ __launch_bounds__(64) void update_kernel(Ctx c, int i_host) {
   const bool was_done = c.b.done[b] != 0;
   const int maxlen = c.b.maxlens[b], minlen = c.b.minlens[b];
 
-  float n_score = -INFINITY, n_sdec = 0.f, n_sctc = 0.f, n_slen = 0.f, n_sprev = 0.f, n_slm = 0.f;
+  float n_score = -INFINITY, n_sdec = 0.f, n_sctc = 0.f, n_slen = 0.f, n_sprev = 0.f, n_slm = 0.f, n_sng = 0.f;
   if (lane < W) {
     const int rnew = b * W + lane;
     const int sel = was_done ? -1 : c.b.sel_idx[rnew];
@@ -789,6 +798,8 @@ __global__ __launch_bounds__(64) void update_kernel(Ctx c, int i_host) {
       if (c.p.w_dec != 0.f) n_sdec = c.b.run_sdec[prow] + c.b.dec_logp[(size_t)prow * V + tk];
       if (c.p.w_len != 0.f) n_slen = c.b.run_slen[prow] + 1.0f;
       if (c.p.w_lm != 0.f) n_slm = c.b.run_slm[prow] + c.b.lm_logp[(size_t)prow * V + tk];
+      if (c.p.w_ngram != 0.f)
+        n_sng = c.b.run_sngram[prow] + (c.p.ngram_part ? c.b.cand_ngram[(size_t)prow * NC + s] : c.b.ngram_logp[(size_t)prow * V + tk]);
       if (c.p.w_ctc != 0.f) {
         const float psi = c.b.cand_psi[(size_t)prow * NC + s];
         n_sctc = c.b.run_sctc[prow] + (psi - c.b.s_prev[prow]);
@@ -825,6 +836,7 @@ __global__ __launch_bounds__(64) void update_kernel(Ctx c, int i_host) {
     c.b.run_sctc[rnew] = n_sctc;
     c.b.run_slen[rnew] = n_slen;
     if (c.b.run_slm) c.b.run_slm[rnew] = n_slm;
+    if (c.b.run_sngram) c.b.run_sngram[rnew] = n_sng;
     c.b.s_prev[rnew] = n_sprev;
     // stash for the serial ended-list pass
     c.b.sel_total[rnew] = n_score;
@@ -856,6 +868,7 @@ __global__ __launch_bounds__(64) void update_kernel(Ctx c, int i_host) {
         c.b.end_sctc[e] = c.b.run_sctc[rnew];
         c.b.end_slen[e] = c.b.run_slen[rnew];
         if (c.b.end_slm) c.b.end_slm[e] = c.b.run_slm[rnew];
+        if (c.b.end_sngram) c.b.end_sngram[e] = c.b.run_sngram[rnew];
         ++cnt;
       }
       if (sc > c.b.best_all[b]) c.b.best_all[b] = sc;
@@ -890,7 +903,7 @@ __global__ __launch_bounds__(64) void update_kernel(Ctx c, int i_host) {
 __global__ __launch_bounds__(1024) void tail_kernel(Ctx c, int i_host, int lt_cap) {
   extern __shared__ float tail_lds[];  // per wave: s_xn, s_xb, s_phi [lt_cap] + s_out [lt_cap] float2
   __shared__ int s_prev_row[64], s_tok[64], s_valid[64], s_end[64], s_sel[64];
-  __shared__ float s_seltot[64], s_rec[4][64], s_wpsi[64];
+  __shared__ float s_seltot[64], s_rec[5][64], s_wpsi[64];
   __shared__ int s_wtok[64];
   const int i = c.b.step ? *c.b.step : i_host;
   const int tid = threadIdx.x, lane = tid & 63;
@@ -913,7 +926,7 @@ __global__ __launch_bounds__(1024) void tail_kernel(Ctx c, int i_host, int lt_ca
   }
   __syncthreads();
   // ---- the new rows' records (batch_beam_search.py:317-357), wave 0, a lane per row
-  float n_score = -INFINITY, n_sdec = 0.f, n_sctc = 0.f, n_slen = 0.f, n_sprev = 0.f, n_slm = 0.f;
+  float n_score = -INFINITY, n_sdec = 0.f, n_sctc = 0.f, n_slen = 0.f, n_sprev = 0.f, n_slm = 0.f, n_sng = 0.f;
   if (wave == 0 && lane < W) {
     const int sel = was_done ? -1 : s_sel[lane];
     int valid = sel >= 0, prow = b * W, tk = c.p.eos;
@@ -925,6 +938,9 @@ __global__ __launch_bounds__(1024) void tail_kernel(Ctx c, int i_host, int lt_ca
       if (c.p.w_dec != 0.f) n_sdec = c.b.run_sdec[prow] + c.b.dec_logp[(size_t)prow * V + tk];
       if (c.p.w_len != 0.f) n_slen = c.b.run_slen[prow] + 1.0f;
       if (c.p.w_lm != 0.f) n_slm = c.b.run_slm[prow] + c.b.lm_logp[(size_t)prow * V + tk];
+      if (c.p.w_ngram != 0.f)
+        n_sng = c.b.run_sngram[prow] + (c.p.ngram_part ? c.b.cand_ngram[(size_t)prow * NC + (sel - pk * NC)]
+                                                       : c.b.ngram_logp[(size_t)prow * V + tk]);
       if (c.p.w_ctc != 0.f) {
         const float psi = s_wpsi[lane];
         n_sctc = c.b.run_sctc[prow] + (psi - c.b.s_prev[prow]);
@@ -974,6 +990,7 @@ __global__ __launch_bounds__(1024) void tail_kernel(Ctx c, int i_host, int lt_ca
       c.b.run_sctc[rnew] = n_sctc;
       c.b.run_slen[rnew] = n_slen;
       if (c.b.run_slm) c.b.run_slm[rnew] = n_slm;
+      if (c.b.run_sngram) c.b.run_sngram[rnew] = n_sng;
       c.b.s_prev[rnew] = n_sprev;
       c.b.sel_total[rnew] = n_score;  // (what update_kernel leaves there)
       s_seltot[lane] = n_score;
@@ -981,6 +998,7 @@ __global__ __launch_bounds__(1024) void tail_kernel(Ctx c, int i_host, int lt_ca
       s_rec[1][lane] = n_sctc;
       s_rec[2][lane] = n_slen;
       s_rec[3][lane] = n_slm;
+      s_rec[4][lane] = n_sng;
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
@@ -1017,6 +1035,7 @@ __global__ __launch_bounds__(1024) void tail_kernel(Ctx c, int i_host, int lt_ca
           c.b.end_sctc[e] = s_rec[1][k];
           c.b.end_slen[e] = s_rec[2][k];
           if (c.b.end_slm) c.b.end_slm[e] = s_rec[3][k];
+          if (c.b.end_sngram) c.b.end_sngram[e] = s_rec[4][k];
           ++cnt;
         }
         if (sc > c.b.best_all[b]) c.b.best_all[b] = sc;
@@ -1186,9 +1205,13 @@ int check(const EmSearchParams* p, const EmSearchBuffers* b) {
   if (p->S <= 0 || p->NC <= 0 || p->end_cap <= 0) return EM_ERR_BAD_ARG;
   if (p->S >= p->V ? p->NC != p->V : p->NC != p->S + 1) return EM_ERR_BAD_ARG;
   if (p->w_dec == 0.f && p->w_ctc == 0.f && p->w_lm == 0.f) return EM_ERR_BAD_ARG;
-  if (p->w_dec == 0.f && p->w_lm == 0.f && p->w_len == 0.f && p->S < p->V)
+  const bool ng_full = p->w_ngram != 0.f && !p->ngram_part;
+  if (p->w_dec == 0.f && p->w_lm == 0.f && p->w_len == 0.f && !ng_full && p->S < p->V)
     return EM_ERR_BAD_ARG;  // no full scorer -> no pre-beam
   if (p->w_lm != 0.f && (!b->lm_logp || !b->run_slm || !b->end_slm || !b->lm)) return EM_ERR_BAD_ARG;
+  if (p->w_ngram != 0.f && (!b->ngram || !b->ng_st_a || !b->ng_st_b || !b->run_sngram || !b->end_sngram ||
+                            (ng_full ? !b->ngram_logp : !b->cand_ngram)))
+    return EM_ERR_BAD_ARG;
   return EM_OK;
 }
 
@@ -1424,6 +1447,19 @@ int decoder_step(int dtype, const EmDecoderWeights* dw, const DecStep& a, void* 
                  a.logits, a.xn, n, V, d, stream);
 }
 
+// the n-gram scorer's view of the search state (csrc/ngram.hip)
+NgSearchArgs ngram_args(const EmSearchParams* p, const EmSearchBuffers* b) {
+  NgSearchArgs a = {};
+  a.n = p->B * p->W; a.W = p->W; a.V = p->V; a.Lmax = p->Lmax; a.S = p->S; a.NC = p->NC;
+  a.w_ctc = p->w_ctc; a.w_ngram = p->w_ngram;
+  a.step = b->step; a.tok = b->tok; a.parent = b->parent; a.alive = b->alive; a.done = b->done;
+  a.st_a = b->ng_st_a; a.st_b = b->ng_st_b;
+  a.logp = p->ngram_part ? nullptr : b->ngram_logp;
+  a.cand_tok = b->cand_tok; a.cand_full = b->cand_full; a.cand_psi = b->cand_psi; a.s_prev = b->s_prev;
+  a.run_score = b->run_score; a.cand_ngram = b->cand_ngram; a.cand_total = b->cand_total;
+  return a;
+}
+
 // One label step up to the per-utterance top-W selection: decoder (+ LM) step for the n rows,
 // log-softmax + pre-beam, CTC prefix scores of the candidates, selection.  Nothing of the search
 // state (tree, ancestor tables, running scores, r) is modified; the decoder / LM K/V caches get
@@ -1440,10 +1476,12 @@ int search_core(int dtype, const EmSearchParams* p, const EmDecoderWeights* dw, 
     EM_TRY(decoder_step(dtype, dw, a, stream));
   }
   if (p->w_lm != 0.f) EM_TRY(lm_step(dtype, p, b, i, stream));
+  const NgSearchArgs ng = ngram_args(p, b);
+  if (p->w_ngram != 0.f) EM_TRY(ngram_search_step(b->ngram, ng, i, stream));
   bool cand_done = false;  // the fused row kernel also produced the candidate totals
-  if (p->w_dec != 0.f || p->w_lm != 0.f || p->w_len != 0.f) {
+  if (p->w_dec != 0.f || p->w_lm != 0.f || p->w_len != 0.f || (p->w_ngram != 0.f && !p->ngram_part)) {
     if ((p->S > PREBEAM_SMAX && p->S < V) || V > 256 * 40) {
-      if (p->w_lm != 0.f || p->w_dec == 0.f) return EM_ERR_UNSUPPORTED;  // needs the fused row kernel
+      if (p->w_lm != 0.f || p->w_ngram != 0.f || p->w_dec == 0.f) return EM_ERR_UNSUPPORTED;  // needs the fused row kernel
       EM_TRY(em_log_softmax_rows_f32(b->dec_logp, n, V, stream));
       if (p->S < V)
         hipLaunchKernelGGL(prebeam_kernel, dim3(n), dim3(64), (size_t)V * sizeof(float), s, c);
@@ -1462,6 +1500,7 @@ int search_core(int dtype, const EmSearchParams* p, const EmDecoderWeights* dw, 
     const long waves = (long)n * p->NC;
     hipLaunchKernelGGL(candidate_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, c, i);
   }
+  if (p->w_ngram != 0.f && p->ngram_part) EM_TRY(ngram_search_part(b->ngram, ng, i, stream));
   if (with_select) hipLaunchKernelGGL(select_kernel, dim3(p->B), dim3(64), 0, s, c);
   return EM_OK;
 }
@@ -1586,6 +1625,7 @@ int check_online(const EmSearchParams* p, const EmSearchBuffers* b) {
   // step[0], which the HOST writes before each em_search_online_core / _commit - nothing advances it on the device (the
   // select / online kernels have no step_advance) - so one captured launch sequence serves every step of a block.
   if (p->B != 1) return EM_ERR_BAD_ARG;
+  if (p->w_ngram != 0.f) return EM_ERR_UNSUPPORTED;  // (no n-gram scorer in the streaming search)
   if (!b->online_best || !b->online_psi || !b->online_snap) return EM_ERR_BAD_ARG;
   if (p->ldT < p->T) return EM_ERR_BAD_ARG;
   return EM_OK;

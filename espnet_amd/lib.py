@@ -181,7 +181,19 @@ class EmDecoderStepArgs(C.Structure):
 class EmSearchParams(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("B", "W", "V", "T", "Tpad", "S", "NC", "Lmax", "end_cap",
                                          "sos", "eos", "blank", "use_end_detect")] + \
-               [(n, C.c_float) for n in ("w_dec", "w_ctc", "w_len", "w_lm")] + [("ldT", C.c_int32)]
+               [(n, C.c_float) for n in ("w_dec", "w_ctc", "w_len", "w_lm")] + [("ldT", C.c_int32)] + \
+               [("w_ngram", C.c_float), ("ngram_part", C.c_int32)]
+
+
+EM_NGRAM_MAX_ORDER = 6
+
+
+class EmNgramModel(C.Structure):
+    """include/espnet_amd.h EmNgramModel (csrc/ngram.hip; built by espnet_amd/lm/ngram.py)."""
+    _fields_ = [(n, C.c_int32) for n in ("order", "vocab", "unk", "bos", "n_alias")] + \
+               [("count", C.c_int32 * EM_NGRAM_MAX_ORDER)] + \
+               [(n, C.c_void_p * EM_NGRAM_MAX_ORDER) for n in ("wid", "prob", "bow", "next")] + \
+               [(n, C.c_void_p) for n in ("tok2word", "word2tok", "alias")]
 
 
 _LM_LAYER_PTRS = ["norm1_g", "norm1_b", "norm2_g", "norm2_b", "wqkv", "bqkv", "wout", "bout", "w1", "b1",
@@ -215,7 +227,8 @@ SEARCH_BUFFERS = ["xlens", "maxlens", "minlens", "ctc_lpT", "tok", "parent", "an
                   "ctx", "hbuf", "dec_logp", "self_k", "self_v", "mem_kv", "mem_vT",
                   "lm", "lm_e", "lm_xn", "lm_qkv", "lm_ctx", "lm_h", "lm_x", "lm_logp", "lm_k", "lm_v",
                   "run_slm", "end_slm", "rnn_hs", "rnn_cs", "rnn_hin", "rnn_gates",
-                  "online_best", "online_psi", "online_snap", "mem_kf", "mem_vf"]
+                  "online_best", "online_psi", "online_snap", "mem_kf", "mem_vf",
+                  "ngram", "ng_st_a", "ng_st_b", "ngram_logp", "cand_ngram", "run_sngram", "end_sngram"]
 
 
 class EmSearchBuffers(C.Structure):
@@ -327,6 +340,9 @@ _SIGNATURES = {
     "em_conformer_encode_plan": (C.c_int, [C.c_int, C.POINTER(EmConformerWeights), _i32]),
     "em_conformer_encode_plan_for": (C.c_int, [C.c_int, C.POINTER(EmConformerWeights), _i32, _i32, _i32]),
     "em_ctc_prefix_extend": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _i32, _vp, _vp]),
+    "em_ngram_score": (C.c_int, [C.POINTER(EmNgramModel), _i32, _vp, _vp, _vp, _vp, _i32, _vp, _vp]),
+    "em_arpa_count": (C.c_int, [C.c_char_p, _vp, _vp, _vp]),
+    "em_arpa_load": (C.c_int, [C.c_char_p, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "em_ctc_greedy": (C.c_int, [C.c_int, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _i32,
                                 _vp, _vp, _vp, _vp, _vp]),
 }

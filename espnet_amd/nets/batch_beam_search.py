@@ -8,8 +8,9 @@ list`), with BatchBeamSearch's step semantics (legacy/nets/batch_beam_search.py:
 `search_batch` is the utterance-batched entry the MI355X path adds; `forward` keeps the
 reference's single-utterance signature.
 
-Supported scorers: "decoder" (TransformerDecoder), "ctc" (CTCPrefixScorer), "length_bonus" and
-"lm" (espnet_amd.lm.transformer_lm.TransformerLM).  An n-gram scorer is SURVEY.md §8(f) "next".
+Supported scorers: "decoder" (TransformerDecoder), "ctc" (CTCPrefixScorer), "length_bonus", "lm"
+(espnet_amd.lm.transformer_lm.TransformerLM, SequentialRNNLM) and "ngram" (espnet_amd.nets.scorers.ngram: NgramFullScorer
+takes part in the pre-beam, NgramPartScorer scores the pre-beam candidates after it).
 """
 import ctypes as C
 import logging
@@ -22,11 +23,12 @@ from espnet_amd import lib as L
 from espnet_amd.nets.beam_search import Hypothesis
 from espnet_amd.nets.scorers.ctc import CTCPrefixScorer
 from espnet_amd.nets.scorers.length_bonus import LengthBonus
+from espnet_amd.nets.scorers.ngram import NgramFullScorer, NgramPartScorer
 
 logger = logging.getLogger(__name__)
 
 _I32 = {"xlens", "maxlens", "minlens", "tok", "parent", "anc_a", "anc_b", "alive", "cand_tok",
-        "sel_idx", "end_count", "end_pos", "end_slot", "end_forced", "done", "step"}
+        "sel_idx", "end_count", "end_pos", "end_slot", "end_forced", "done", "step", "ng_st_a", "ng_st_b"}
 _ACT = {"xn", "qkv", "qs", "ctx", "hbuf", "self_k", "self_v", "mem_kv", "mem_vT", "mem_kf", "mem_vf", "lm_e", "lm_xn",
         "lm_qkv", "lm_ctx", "lm_h", "lm_k", "lm_v", "rnn_hs", "rnn_hin"}
 _ZERO = {"mem_vT", "rnn_hs", "rnn_cs", "rnn_hin"}  # pad columns / tails that must read as zero
@@ -46,10 +48,12 @@ class BeamSearch:
             w = weights.get(k, 0)
             if w == 0 or v is None:
                 continue
-            if k not in ("decoder", "ctc", "length_bonus", "lm"):
-                raise NotImplementedError(f"scorer {k!r}: SURVEY.md §8(f) 'next' (n-gram)")
+            if k not in ("decoder", "ctc", "length_bonus", "lm", "ngram"):
+                raise NotImplementedError(f"scorer {k!r} is outside the MI355X search")
+            if k == "ngram" and not isinstance(v, (NgramFullScorer, NgramPartScorer)):
+                raise NotImplementedError("the 'ngram' scorer must be espnet_amd.nets.scorers.ngram.Ngram{Full,Part}Scorer")
             self.scorers[k] = v
-            (self.part_scorers if isinstance(v, CTCPrefixScorer) else self.full_scorers)[k] = v
+            (self.part_scorers if isinstance(v, (CTCPrefixScorer, NgramPartScorer)) else self.full_scorers)[k] = v
         self.sos, self.eos = sos, eos
         self.token_list = token_list
         self.pre_beam_size = int(pre_beam_ratio * beam_size)
@@ -106,9 +110,9 @@ class BatchBeamSearch(BeamSearch):
         return ser
 
     # ------------------------------------------------------------------ buffers
-    def _alloc(self, dev, act, B, W, V, T, Tpad, NC, Lmax, cap, d, ff, nl, lm=None, online=False):
+    def _alloc(self, dev, act, B, W, V, T, Tpad, NC, Lmax, cap, d, ff, nl, lm=None, online=False, ngram=None):
         key = (str(dev), act, B, W, V, T, Tpad, NC, Lmax, cap, d, ff, nl,
-               None if lm is None else lm.search_key(), online)
+               None if lm is None else lm.search_key(), online, None if ngram is None else ngram.search_key())
         if key in self._bufs:
             self._bufs[key] = self._bufs.pop(key)  # most recently used last
             return self._bufs[key]
@@ -139,6 +143,9 @@ class BatchBeamSearch(BeamSearch):
                 shapes.update(mem_kf=(nl, B, d, Tpad), mem_vf=(nl, B, d, Tpad))
         if lm is not None:
             shapes.update(lm.search_buffers(n, V, Lmax, B, cap))
+        if ngram is not None:  # csrc/ngram.hip: context nodes by step parity, scores, running / ended sums
+            shapes.update(ng_st_a=(n, ngram.state_len), ng_st_b=(n, ngram.state_len), run_sngram=(n,), end_sngram=(B, cap))
+            shapes.update(dict(cand_ngram=(n, NC)) if ngram.part else dict(ngram_logp=(n, V)))
         if online:  # em_search_online_* (batch_beam_search_online.py)
             shapes.update(online_best=(n, 8), online_psi=(n,), online_snap=(n, 8))
         t = {}
@@ -196,6 +203,7 @@ class BatchBeamSearch(BeamSearch):
         dec = self.scorers.get("decoder")
         ctc_sc = self.scorers.get("ctc")
         lm = self.scorers.get("lm")
+        ng = self.scorers.get("ngram")
         em_dtype = dec.em_dtype if dec is not None else (ctc_sc.ctc.em_dtype if ctc_sc is not None else lm.em_dtype)
         act = torch.bfloat16 if em_dtype == L.EM_BF16 else torch.float32
         enc_act = enc_act.to(act).contiguous()
@@ -226,7 +234,7 @@ class BatchBeamSearch(BeamSearch):
         Tpad = T
         nl = dec.num_blocks if dec is not None else 0
         ff = dec.linear_units if dec is not None else 0
-        bufs = self._alloc(dev, act, B, W, V, T, Tpad, NC, Lmax, cap, d, ff, nl, lm)
+        bufs = self._alloc(dev, act, B, W, V, T, Tpad, NC, Lmax, cap, d, ff, nl, lm, ngram=ng)
         bufs["xlens"].copy_(torch.tensor(olens, dtype=torch.int32))
         bufs["maxlens"].copy_(torch.tensor(maxlens, dtype=torch.int32))
         bufs["minlens"].copy_(torch.tensor(minlens, dtype=torch.int32))
@@ -234,6 +242,7 @@ class BatchBeamSearch(BeamSearch):
         ctc_pk = ctc_sc.ctc.packed(dev) if ctc_sc is not None else None
         lm_pk = lm.packed(dev, Lmax) if lm is not None else None
         dec_pk = dec.packed(dev, Lmax) if dec is not None else None
+        ng_pk = ng.packed(dev) if ng is not None else None
         _check_lm_dtype(lm_pk, em_dtype)
         p = L.EmSearchParams(B=B, W=W, V=V, T=T, Tpad=Tpad, S=S, NC=NC, Lmax=Lmax, end_cap=cap,
                              sos=self.sos, eos=self.eos, blank=0,
@@ -242,7 +251,9 @@ class BatchBeamSearch(BeamSearch):
                              w_ctc=float(self.weights.get("ctc", 0.0)) if ctc_sc is not None else 0.0,
                              w_len=float(self.weights.get("length_bonus", 0.0))
                              if "length_bonus" in self.scorers else 0.0,
-                             w_lm=float(self.weights.get("lm", 0.0)) if lm is not None else 0.0)
+                             w_lm=float(self.weights.get("lm", 0.0)) if lm is not None else 0.0,
+                             w_ngram=float(self.weights.get("ngram", 0.0)) if ng is not None else 0.0,
+                             ngram_part=1 if ng is not None and ng.part else 0)
         bs = L.EmSearchBuffers()
         for name in L.SEARCH_BUFFERS:
             setattr(bs, name, bufs[name].data_ptr() if name in bufs else None)
@@ -250,6 +261,8 @@ class BatchBeamSearch(BeamSearch):
             bs.step = None
         if lm_pk is not None:
             bs.lm = C.addressof(lm_pk.w)
+        if ng_pk is not None:
+            bs.ngram = C.addressof(ng_pk.w)
         dwp = C.byref(dec_pk.w) if dec_pk is not None else None
         stream = L.current_stream_ptr()
 
@@ -269,7 +282,7 @@ class BatchBeamSearch(BeamSearch):
             # One hipGraph = K search steps (~75 launches each).  Every step-dependent kernel reads the
             # step index from device memory, so the same graph is replayed ceil(imax / K) times; steps
             # past the end are no-ops.  The graph is tied to the buffer set and the packs.
-            gkey = (id(bufs), bytes(p), em_dtype, self._serials(dec_pk, lm_pk))
+            gkey = (id(bufs), bytes(p), em_dtype, self._serials(dec_pk, lm_pk, ng_pk))
             g = self._graphs.get(gkey)
             if g is None:
                 steps(0, 1)  # warm-up outside capture (one-time attribute calls, lazy module loads)
@@ -277,7 +290,7 @@ class BatchBeamSearch(BeamSearch):
                 g = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(g):
                     steps(0, K)
-                self._graphs[gkey] = (g, p, bs, dec_pk, lm_pk)  # keep the argument blocks and packs alive with the graph
+                self._graphs[gkey] = (g, p, bs, dec_pk, lm_pk, ng_pk)  # keep the argument blocks and packs alive with the graph
                 init()  # the warm-up step advanced the search state: start over
             else:
                 g = g[0]
@@ -307,7 +320,7 @@ class BatchBeamSearch(BeamSearch):
 
         cpu = {k: bufs[k].cpu().numpy() for k in ("end_count", "end_pos", "end_slot", "end_forced",
                                                   "end_score", "end_sdec", "end_sctc", "end_slen",
-                                                  "end_slm", "tok", "parent") if k in bufs}
+                                                  "end_slm", "end_sngram", "tok", "parent") if k in bufs}
         tok, parent = cpu["tok"], cpu["parent"]
         counts = cpu["end_count"]
         bi = np.repeat(np.arange(B), counts)
@@ -324,8 +337,8 @@ class BatchBeamSearch(BeamSearch):
         forced = cpu["end_forced"][bi, ei].astype(bool)
         ys[np.arange(E)[forced], pos[forced] + 1] = self.eos
         lens = pos + 1 + forced
-        keys = [k for k in ("decoder", "ctc", "length_bonus", "lm") if k in self.scorers]
-        col = dict(decoder="end_sdec", ctc="end_sctc", length_bonus="end_slen", lm="end_slm")
+        keys = [k for k in ("decoder", "ctc", "length_bonus", "lm", "ngram") if k in self.scorers]
+        col = dict(decoder="end_sdec", ctc="end_sctc", length_bonus="end_slen", lm="end_slm", ngram="end_sngram")
         out, off = [], 0
         for b in range(B):
             hyps = []
@@ -521,15 +534,18 @@ class SearchLanes:
 
 
 def build_beam_search(asr_model, beam_size: int, ctc_weight: float, penalty: float,
-                      lm_weight: float = 0.0, token_list=None, normalize_length: bool = False, lm=None):
+                      lm_weight: float = 0.0, token_list=None, normalize_length: bool = False, lm=None,
+                      ngram=None, ngram_weight: float = 0.0):
     """Scorer / weight set-up of Speech2Text (espnet2/bin/asr_inference.py:168-176, 310-316,
-    353-381)."""
+    353-381).  `ngram`: an NgramFullScorer / NgramPartScorer (asr_inference.py:193-207), summed after the LM."""
     scorers = dict(decoder=asr_model.decoder,
                    ctc=CTCPrefixScorer(ctc=asr_model.ctc, eos=asr_model.eos) if asr_model.ctc is not None else None,
                    length_bonus=LengthBonus(len(token_list)))
     if lm is not None:
         scorers["lm"] = lm  # asr_inference.py:179-191 (scorers["lm"] = lm.lm)
-    weights = dict(decoder=1.0 - ctc_weight, ctc=ctc_weight, lm=lm_weight, length_bonus=penalty)
+    if ngram is not None:
+        scorers["ngram"] = ngram
+    weights = dict(decoder=1.0 - ctc_weight, ctc=ctc_weight, lm=lm_weight, ngram=ngram_weight, length_bonus=penalty)
     return BatchBeamSearch(beam_size=beam_size, weights=weights, scorers=scorers, sos=asr_model.sos,
                            eos=asr_model.eos, vocab_size=len(token_list), token_list=token_list,
                            pre_beam_score_key=None if ctc_weight == 1.0 else "full",

@@ -774,7 +774,31 @@ typedef struct EmSearchParams {
   float w_lm;                /* language-model scorer weight (lm_weight), 0 = no LM */
   int32_t ldT;               /* frame stride of ctc_lpT / r_a / r_b; 0 = T.  A stream (B == 1) whose
                                 visible length T grows block by block keeps a fixed capacity here */
+  float w_ngram;             /* n-gram scorer weight (ngram_weight), 0 = no n-gram */
+  int32_t ngram_part;        /* 0: NgramFullScorer (all V tokens, before the pre-beam); 1: NgramPartScorer (the pre-beam
+                                candidates only, added after the pre-beam like the CTC score) */
 } EmSearchParams;
+
+/* Back-off n-gram LM (ARPA) as a search scorer (espnet2/legacy/nets/scorers/ngram.py, kenlm's FullScore): a sorted trie,
+ * one array set per order k = 1 .. order (index k-1).  Order-1 entry i is word id i.  The entries of order k+1 that
+ * extend entry e of order k (its successors) are next[k-1][e] .. next[k-1][e+1]-1, sorted by word id.  Scores are
+ * log10, as in the file.  Every array is device memory.                                                            */
+#define EM_NGRAM_MAX_ORDER 6
+typedef struct EmNgramModel {
+  int32_t order;                       /* N, 1 .. EM_NGRAM_MAX_ORDER */
+  int32_t vocab;                       /* V: token ids of the search */
+  int32_t unk;                         /* word id of <unk> (the reader adds it with log10 p = -100 when absent) */
+  int32_t bos;                         /* word id of <s>, or -1 */
+  int32_t n_alias;                     /* tokens that are not the primary token of their word (see alias) */
+  int32_t count[EM_NGRAM_MAX_ORDER];   /* entries of order k+1 */
+  const int32_t* wid[EM_NGRAM_MAX_ORDER];  /* [count[k]] word id of the entry's last word */
+  const float* prob[EM_NGRAM_MAX_ORDER];   /* [count[k]] log10 probability */
+  const float* bow[EM_NGRAM_MAX_ORDER];    /* [count[k]] log10 back-off weight (0 where the file has none) */
+  const int32_t* next[EM_NGRAM_MAX_ORDER]; /* [count[k] + 1] first successor in order k+2 (k < order - 1; else NULL) */
+  const int32_t* tok2word;             /* [V] word id of every token (<unk> for tokens that are no unigram) */
+  const int32_t* word2tok;             /* [count[0]] the lowest token id mapped to the word, or -1 */
+  const int32_t* alias;                /* [n_alias] tokens whose word's primary token is another one (<unk>'s included) */
+} EmNgramModel;
 
 /* TransformerLM used as a full scorer (espnet2/lm/transformer_lm.py:12-137):
  * nn.Embedding -> Encoder(input_layer="linear") -> nn.Linear head.  "act" = dtype of the call.  */
@@ -878,6 +902,14 @@ typedef struct EmSearchBuffers {
    * mem_kv / mem_vT: mem_kf act [layers][B][heads][Tpad/16][2][64][8], mem_vf act [layers][B][heads][4][Tpad/32][64][8]
    * (B * d * Tpad elements per layer each), zero for frames >= T                                                              */
   void *mem_kf, *mem_vf;
+  /* n-gram scorer (all NULL when w_ngram == 0) */
+  const EmNgramModel* ngram;                /* host struct */
+  int32_t *ng_st_a, *ng_st_b;               /* [n][max(order-1, 1)] trie node of every context length 1 .. order-1 of
+                                               the row's history (-1: not in the model), double buffered by step parity */
+  float* ngram_logp;                        /* [n][V] full mode: log10 score of every token */
+  float* cand_ngram;                        /* [n][NC] part mode: log10 score of every candidate slot (0 outside the
+                                               pre-beam) */
+  float *run_sngram, *end_sngram;           /* [n], [B][end_cap] accumulated n-gram score */
 } EmSearchBuffers;
 
 /*   Projects the encoder memory (enc_act [B][T][d_model] act) to per-layer K | V and V^T, computes
@@ -983,6 +1015,15 @@ int em_search_online_commit(int dtype, const EmSearchParams* p, const EmSearchBu
 /*   running_hyps = prev_hyps (:484-487); the caller decrements its position.                          */
 int em_search_online_rewind(const EmSearchParams* p, const EmSearchBuffers* b, void* stream);
 
+/* ---- n-gram scorer (Ngrambase.score / score_partial of espnet2/legacy/nets/scorers/ngram.py on kenlm) ----------------
+ *   One call per search step for n hypotheses: every row advances its context by its last token (kenlm BaseScore(state,
+ *   y[-1], out_state); last_tok[r] < 0 = the first step, context <s> alone: BeginSentenceWrite) and scores the next token:
+ *   prev_state / out_state [n][max(order-1, 1)] i32 trie nodes (prev_state is not read for rows that start; it may be
+ *   NULL when all do), scores log10 with kenlm's back-off.  cand == NULL: out [n][V] (full scorer); else cand [n][n_cand]
+ *   token ids and out [n][n_cand] (part scorer).  m: device arrays, host struct.                                      */
+int em_ngram_score(const EmNgramModel* m, int32_t n, const int32_t* prev_state, const int32_t* last_tok,
+                   int32_t* out_state, const int32_t* cand, int32_t n_cand, float* out, void* stream);
+
 /* ---- A16: streaming (contextual block) Conformer encoder step
  *      (ContextualBlockConformerEncoder.forward_infer, espnet2/asr/encoder/
  *      contextual_block_conformer_encoder.py:386-600; ContextualBlockEncoderLayer.forward_infer,
@@ -1081,6 +1122,18 @@ int em_wav_probe(const char* const* paths, int32_t n, EmWavInfo* info, int32_t t
 /*   out [n][ld] f32: row i <- the info[i].frames samples of file i, zero filled up to ld (>= every frames).   */
 int em_wav_load_rows(const char* const* paths, const EmWavInfo* info, int32_t n, float* out, int64_t ld,
                      int32_t threads);
+
+/* ---- host ARPA reader of the n-gram scorer (host code only, no GPU needed).  Plain-text ARPA: the \data\ counts, the
+ *      \k-grams: sections, optional back-off columns; values parsed from their decimal text to f32 (strtof).  Two passes
+ *      over the file: em_arpa_count, then em_arpa_load into caller-owned host arrays laid out as EmNgramModel.
+ *      EM_ERR_UNSUPPORTED: not a plain-text ARPA file (kenlm binary, gzip) or order > EM_NGRAM_MAX_ORDER;
+ *      EM_ERR_IO: unreadable; EM_ERR_BAD_ARG: malformed (counts that do not match, an n-gram whose prefix is missing). */
+/*   order, counts [EM_NGRAM_MAX_ORDER] (entries per order; <unk> counted when the reader adds it), vocab_bytes (the
+ *   unigram words, NUL-terminated, in word-id order).                                                                  */
+int em_arpa_count(const char* path, int32_t* order, int32_t* counts, int64_t* vocab_bytes);
+/*   vocab [vocab_bytes]; wid / prob / bow [order] arrays of counts[k] entries; next [order - 1] arrays of counts[k] + 1. */
+int em_arpa_load(const char* path, int32_t order, const int32_t* counts, char* vocab, int32_t* const* wid,
+                 float* const* prob, float* const* bow, int32_t* const* next);
 
 #ifdef __cplusplus
 }
