@@ -112,7 +112,9 @@ __device__ __forceinline__ float rsqrt_nr(float var) {
 // POST 1: the CTC head's arg-max walk behind the launch (the last launch of the stack), see the end of the kernel.
 // POST 2 (round 6): the attention's q | k | v projections walked behind a ln_mode 1 launch (macaron FFN + residual + norm_mha):
 // their per-head operands (csrc/attention2.hip) written straight from the walk, LN(x) itself never stored.
-template <int LNMODE, int PRE, int MAIN, int POST = 0>
+// ACT: the feed-forward module's activation, EM_ROWS_ACT_SWISH (the Conformer / E-Branchformer) or EM_ROWS_ACT_RELU (the
+// Transformer encoder's PositionwiseFeedForward default, csrc/transformer.hip).
+template <int LNMODE, int PRE, int MAIN, int POST = 0, int ACT = EM_ROWS_ACT_SWISH>
 __global__ __launch_bounds__(NT, 1) void ffn_rows_kernel(const EmFfnRowsArgs a, long long* __restrict__ stamps) {
   using MM = Mma<bf16>;
   extern __shared__ __attribute__((aligned(1024))) unsigned char smem[];
@@ -276,7 +278,10 @@ __global__ __launch_bounds__(NT, 1) void ffn_rows_kernel(const EmFfnRowsArgs a, 
   float hv[4];
   auto swish_piece = [&](int rf, int r, int buf) {
     const float bias = r == 0 ? bia.x : r == 1 ? bia.y : r == 2 ? bia.z : bia.w;
-    hv[r] = swishf_(acc1[rf][r] + bias);
+    if constexpr (ACT == EM_ROWS_ACT_RELU)
+      hv[r] = fmaxf(acc1[rf][r] + bias, 0.f);
+    else
+      hv[r] = swishf_(acc1[rf][r] + bias);
     if (r == 3) {
       const bf16x4 hb = {(bf16)hv[0], (bf16)hv[1], (bf16)hv[2], (bf16)hv[3]};
       *(bf16x4*)(smem + hwr + buf * 16384 + rf * 1024) = hb;
@@ -753,6 +758,10 @@ extern "C" int em_ffn_rows_fused(const EmFfnRowsArgs* a, void* stream) {
   }
   const bool glu = a->main == EM_ROWS_GLU;
   if (a->main != EM_ROWS_FFN && !glu) return EM_ERR_BAD_ARG;
+  if (a->act != EM_ROWS_ACT_SWISH && a->act != EM_ROWS_ACT_RELU) return EM_ERR_BAD_ARG;
+  // ReLU: the plain feed-forward module with LN(x) as input and ln_mode 1 (csrc/transformer.hip) - no projection, no walk
+  const bool relu = a->act == EM_ROWS_ACT_RELU;
+  if (relu && (glu || pre || lnin || post_qkv || a->post_w || a->ln_mode != 1)) return EM_ERR_UNSUPPORTED;
   if (glu && !pre) return EM_ERR_BAD_ARG;
   if (glu && a->ff != 2 * D) return EM_ERR_UNSUPPORTED;
   if (!glu && a->ln_mode != 1 && a->ln_mode != 2) return EM_ERR_BAD_ARG;
@@ -764,8 +773,8 @@ extern "C" int em_ffn_rows_fused(const EmFfnRowsArgs* a, void* stream) {
   if (want_stamps && hipMemsetAsync(stamps, 0, 64 * sizeof(long long), (hipStream_t)stream) != hipSuccess) return EM_ERR_LAUNCH;
   long long* const st = want_stamps ? stamps : nullptr;
   typedef void (*kern_t)(const EmFfnRowsArgs, long long*);
-  static EmLdsCap caps[9] = {};
-  const int which = lnin ? 8 : post_qkv ? 7 : glu ? 4 : a->post_w ? 5 + (pre ? 1 : 0) : (a->ln_mode - 1) * 2 + (pre ? 1 : 0);
+  static EmLdsCap caps[10] = {};
+  const int which = relu ? 9 : lnin ? 8 : post_qkv ? 7 : glu ? 4 : a->post_w ? 5 + (pre ? 1 : 0) : (a->ln_mode - 1) * 2 + (pre ? 1 : 0);
   const kern_t kern = which == 0   ? ffn_rows_kernel<1, 0, EM_ROWS_FFN>
                       : which == 1 ? ffn_rows_kernel<1, 1, EM_ROWS_FFN>
                       : which == 2 ? ffn_rows_kernel<2, 0, EM_ROWS_FFN>
@@ -774,7 +783,8 @@ extern "C" int em_ffn_rows_fused(const EmFfnRowsArgs* a, void* stream) {
                       : which == 5 ? ffn_rows_kernel<2, 0, EM_ROWS_FFN, 1>
                       : which == 6 ? ffn_rows_kernel<2, 1, EM_ROWS_FFN, 1>
                       : which == 7 ? ffn_rows_kernel<1, 0, EM_ROWS_FFN, 2>
-                                   : ffn_rows_kernel<2, 2, EM_ROWS_FFN>;
+                      : which == 8 ? ffn_rows_kernel<2, 2, EM_ROWS_FFN>
+                                   : ffn_rows_kernel<1, 0, EM_ROWS_FFN, 0, EM_ROWS_ACT_RELU>;
   if (em_raise_lds_cap((const void*)kern, SMEM_BYTES, &caps[which]) != EM_OK) return EM_ERR_LAUNCH;
   const bool rec = em_prof_begin(stream);
   hipLaunchKernelGGL(kern, grid, dim3(NT), SMEM_BYTES, (hipStream_t)stream, *a, st);

@@ -86,6 +86,7 @@ class EmBlockArgs(C.Structure):
 
 
 EM_ROWS_FFN, EM_ROWS_GLU = 0, 1
+EM_ROWS_ACT_SWISH, EM_ROWS_ACT_RELU = 0, 1
 
 
 class EmFfnRowsArgs(C.Structure):
@@ -95,7 +96,8 @@ class EmFfnRowsArgs(C.Structure):
                [(n, C.c_int32) for n in ("M", "d", "ff", "ln_mode")] + [("scale", C.c_float), ("eps", C.c_float)] + \
                [(n, C.c_void_p) for n in ("pre_in", "pre_w", "pre_b", "pre_g", "pre_be")] + [("main", C.c_int32)] + \
                [(n, C.c_void_p) for n in ("post_w", "post_b", "post_ids")] + [("post_chunks", C.c_int32), ("post_vocab", C.c_int32)] + \
-               [(n, C.c_void_p) for n in ("post_q", "post_k", "post_vt")] + [("post_T", C.c_int32), ("post_Tpad", C.c_int32)]
+               [(n, C.c_void_p) for n in ("post_q", "post_k", "post_vt")] + [("post_T", C.c_int32), ("post_Tpad", C.c_int32)] + \
+               [("act", C.c_int32)]
 
 
 class EmConformerWeights(C.Structure):
@@ -133,6 +135,22 @@ class EmEBranchformerWeights(C.Structure):
                 ("subsample", C.c_int32), ("conv3_w", C.c_void_p), ("conv3_b", C.c_void_p),
                 ("legacy_relpos", C.c_int32), ("merge_method", C.c_int32), ("conv1_wf", C.c_void_p),
                 ("conv2_wf", C.c_void_p)]
+
+
+# order of include/espnet_amd.h EmTransformerLayer
+_TRF_LAYER_PTRS = ["norm1_g", "norm1_b", "norm2_g", "norm2_b", "wqkv", "bqkv", "wout", "bout", "ff_w1", "ff_w2", "ff_b1",
+                   "ff_b2", "ff_w1p", "ff_w2p"]
+
+
+class EmTransformerLayer(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in _TRF_LAYER_PTRS]
+
+
+class EmTransformerWeights(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("d", "heads", "ff", "num_blocks", "n_mels", "subsample")] + \
+               [(n, C.c_void_p) for n in ("conv1_w", "conv1_b", "conv2_w", "conv2_b", "conv3_w", "conv3_b", "embed_w",
+                                          "embed_b", "after_norm_g", "after_norm_b")] + \
+               [("layers", C.POINTER(EmTransformerLayer)), ("conv1_wf", C.c_void_p), ("conv2_wf", C.c_void_p)]
 
 
 class EmWavInfo(C.Structure):
@@ -263,6 +281,11 @@ _SIGNATURES = {
     "em_ebranchformer_workspace_bytes": (_sz, [C.c_int, C.POINTER(EmEBranchformerWeights), _i32, _i32]),
     "em_ebranchformer_encode": (C.c_int, [C.c_int, C.POINTER(EmEBranchformerWeights), _vp, _vp, _vp, _vp,
                                           _i32, _i32, _vp, _vp, _sz, _vp, _vp, _i32, _vp]),
+    "em_abs_attention_bf16": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "em_abs_attention": (C.c_int, [C.c_int, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "em_transformer_workspace_bytes": (_sz, [C.c_int, C.POINTER(EmTransformerWeights), _i32, _i32]),
+    "em_transformer_encode": (C.c_int, [C.c_int, C.POINTER(EmTransformerWeights), _vp, _vp, _vp, _vp,
+                                        _i32, _i32, _vp, _vp, _sz, _vp, _vp, _i32, _vp]),
     "em_wav_probe": (C.c_int, [C.POINTER(C.c_char_p), _i32, C.POINTER(EmWavInfo), _i32]),
     "em_wav_load_rows": (C.c_int, [C.POINTER(C.c_char_p), C.POINTER(EmWavInfo), _i32, _vp, C.c_int64, _i32]),
     "em_branch_learned_ave": (C.c_int, [C.c_int, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

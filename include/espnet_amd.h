@@ -484,7 +484,7 @@ int em_relpos_pack_pos_bf16(const void* pall, int32_t ldp, int32_t T, int32_t L,
  *      PositionwiseFeedForward.forward (transformer/positionwise_feed_forward.py:30-32) with its residual
  *      (conformer/encoder_layer.py:111-121, :160-168) and the LayerNorm(s) that follow it (:124 norm_mha; :170-171
  *      norm_final + the next block's :112 norm_ff_macaron, or ConformerEncoder's after_norm), 64 rows per workgroup:
- *        ln_mode 1:  x += scale * (W2 . swish(W1 . xn_in + b1) + b2);      xn_out = LN(x; g1, be1)
+ *        ln_mode 1:  x += scale * (W2 . swish(W1 . xn_in + b1) + b2);      xn_out = LN(x; g1, be1)   (ReLU: act below)
  *        ln_mode 2:  x  = LN(x + scale * (...); g1, be1);                  xn_out = LN(x; g2, be2)  (+ out_f32)
  *      The [M][ff] hidden activation is never written; x is read and written once.  xn_out may alias xn_in.
  *   w1p: W1 [ff][512] in 128-row chunks of 16 x 8 MFMA operand fragments of 1 KiB (the eight waves' fragments adjacent):
@@ -536,9 +536,15 @@ typedef struct EmFfnRowsArgs {
    * LayerNorm of the same rows, LN(x; g2, be2) (E-Branchformer's norm_mlp beside norm_mha, e_branchformer_encoder.py:138-139).   */
   void *post_q, *post_k, *post_vt;
   int32_t post_T, post_Tpad;
+  /* the feed-forward module's activation: EM_ROWS_ACT_SWISH (0, the Conformer / E-Branchformer) or EM_ROWS_ACT_RELU
+   * (PositionwiseFeedForward's default, the Transformer encoder).  ReLU is taken for the plain module only: ln_mode 1,
+   * xn_in given, no projection in front and no walk behind (EM_ERR_UNSUPPORTED otherwise).                         */
+  int32_t act;
 } EmFfnRowsArgs;
 #define EM_ROWS_FFN 0
 #define EM_ROWS_GLU 1
+#define EM_ROWS_ACT_SWISH 0
+#define EM_ROWS_ACT_RELU 1
 int em_ffn_rows_fused(const EmFfnRowsArgs* args, void* stream);
 
 /* ---- A7, LDS-resident form (bf16, d_k = 64): RelPositionMultiHeadedAttention.forward core
@@ -549,6 +555,61 @@ int em_ffn_rows_fused(const EmFfnRowsArgs* args, void* stream);
 int em_relpos_attention2_bf16(const void* qh, const void* kh, const void* vt, const void* p, int32_t ldp,
                               const float* pos_u, const float* pos_v, const int32_t* klens, int32_t B,
                               int32_t T, int32_t Tpad, int32_t h, void* ctx, void* stream);
+
+/* ---- Plain (absolute-position) multi-head self-attention over whole utterances (csrc/abs_attn.hip):
+ *      MultiHeadedAttention.forward (transformer/attention.py) after the projections, eval mode, key-padding mask:
+ *      ctx_i = sum_j softmax_j(q_i . k_j / sqrt(64)) v_j over keys j < klens[b] (masked probabilities 0); any T >= 1.
+ *   em_abs_attention_bf16: bf16 MFMA, f32 accumulate / softmax, over the per-head operands of EM_EPI_QK_HEADS /
+ *     EM_EPI_VT_HEADS: qh / kh [B][H][Tpad][64], vt [B][H][64][Tpad] bf16 (Tpad % 256 == 0, Tpad >= T; frames >= T
+ *     are never read as keys); ctx [B*T][H*64] bf16 out.
+ *   em_abs_attention: f32 arithmetic over q | k | v rows, qkv [B*T][3 H dk] act (dk must be 64), ctx [B*T][H dk] act:
+ *     the EM_F32 (parity) kernel, and the bf16 fall-back where the per-head operands would not fit.              */
+int em_abs_attention_bf16(const void* qh, const void* kh, const void* vt, const int32_t* klens, int32_t B, int32_t T,
+                          int32_t Tpad, int32_t h, void* ctx, void* stream);
+int em_abs_attention(int dtype, const void* qkv, const int32_t* klens, int32_t B, int32_t T, int32_t h, int32_t dk,
+                     void* ctx, void* stream);
+
+/* ---- Transformer encoder (espnet2/asr/encoder/transformer_encoder.py, TransformerEncoder) for input_layer conv2d /
+ *      conv2d6 / conv2d8, normalize_before, concat_after = False, linear position-wise FFN with ReLU, d_k = 64:
+ *        x = Conv2dSubsampling(feats) * sqrt(d) + pe[:T];  per layer  x += MHA(norm1(x));  x += w_2(relu(w_1(norm2(x))));
+ *        out = after_norm(x).                                                                                      */
+typedef struct EmTransformerLayer {
+  const float *norm1_g, *norm1_b, *norm2_g, *norm2_b;
+  const void* wqkv; /* [3d][d] act (linear_q | linear_k | linear_v) */
+  const float* bqkv;
+  const void* wout; /* [d][d] act */
+  const float* bout;
+  const void *ff_w1, *ff_w2; /* [ff][d], [d][ff] act */
+  const float *ff_b1, *ff_b2;
+  /* bf16, d = 512, ff % 128 == 0: the operand streams of em_ffn_rows_fused (host: pack_ffn_rows_w1 / _w2) - the FFN +
+   * residual + the next LayerNorm as one row-block launch when its rounds fill the chip - or NULL                  */
+  const void *ff_w1p, *ff_w2p;
+} EmTransformerLayer;
+
+typedef struct EmTransformerWeights {
+  int32_t d, heads, ff, num_blocks, n_mels;
+  int32_t subsample; /* as EmConformerWeights.subsample */
+  const float *conv1_w, *conv1_b;
+  const void* conv2_w;
+  const float* conv2_b;
+  const void* conv3_w;
+  const float* conv3_b;
+  const void* embed_w;
+  const float* embed_b;
+  const float *after_norm_g, *after_norm_b;
+  const EmTransformerLayer* layers;
+  const void* conv1_wf; /* as EmConformerWeights: operands of the fused conv1 + conv2 kernel (bf16, d = 256 / 512), or NULL */
+  const void* conv2_wf;
+} EmTransformerWeights;
+
+size_t em_transformer_workspace_bytes(int dtype, const EmTransformerWeights* w, int32_t B, int32_t T_f);
+/*   Arguments as em_conformer_encode; pos_emb is PositionalEncoding's table pe[:T] [T][d] f32 (embedding.py extend_pe),
+ *   T = the subsampled length.  The attention masks keys j >= olens[b]; with EM_ENC_ISOLATE_UTTS the caller passes each
+ *   utterance's own olens (no operator of this encoder mixes frames other than the attention).                   */
+int em_transformer_encode(int dtype, const EmTransformerWeights* w, const float* feats, const float* mvn_partial,
+                          const int32_t* flens, const int32_t* olens, int32_t B, int32_t T_f, const void* pos_emb,
+                          void* workspace, size_t workspace_bytes, float* enc_out, void* enc_act, int32_t flags,
+                          void* stream);
 
 /* ---- §8(f) rank 4: E-Branchformer encoder (espnet2/asr/encoder/e_branchformer_encoder.py:55-520) for
  *      input_layer=conv2d, rel_pos / rel_selfattn (latest), use_ffn + macaron_ffn, swish FFN,
