@@ -26,8 +26,8 @@ import numpy as np
 import torch
 
 from espnet_amd import lib as L
-from espnet_amd.asr.encoder.contextual_block_conformer_encoder import (
-    ContextualBlockConformerEncoder, StreamingStepGraph)
+from espnet_amd.asr.encoder._contextual_block_base import ContextualBlockEncoderBase
+from espnet_amd.asr.encoder.contextual_block_conformer_encoder import StreamingStepGraph
 from espnet_amd.nets.beam_search import Hypothesis
 from espnet_amd.tasks.asr import ASRTask
 from espnet_amd.text.token_id_converter import TokenIDConverter, build_tokenizer
@@ -58,8 +58,9 @@ class Speech2TextStreaming:
         dtype = resolve_dtype(dtype)
         asr_model, args = ASRTask.build_model_from_file(asr_train_config, asr_model_file, device,
                                                         compute_dtype=dtype)
-        if not isinstance(asr_model.encoder, ContextualBlockConformerEncoder):
-            raise NotImplementedError("Speech2TextStreaming needs encoder: contextual_block_conformer")
+        if not isinstance(asr_model.encoder, ContextualBlockEncoderBase):
+            raise NotImplementedError("Speech2TextStreaming needs encoder: contextual_block_conformer or "
+                                      "contextual_block_transformer")
         self.asr_model, self.asr_train_args = asr_model, args
         self.device, self.dtype = device, dtype
         self.maxlenratio, self.minlenratio, self.nbest = maxlenratio, minlenratio, nbest

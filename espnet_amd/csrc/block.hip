@@ -143,7 +143,7 @@ __global__ __launch_bounds__(NT, 1) void block_kernel(const EmBlockArgs a_in, lo
   const void *ffm_w1 = a_in.ffm_w1, *ffm_w2 = a_in.ffm_w2, *ff_w1 = a_in.ff_w1, *ff_w2 = a_in.ff_w2;
   const float *ffm_b1g = a_in.ffm_b1g, *ff_b1g = a_in.ff_b1g;
   int nsplit = 1;
-  if constexpr (RELU && (MODE & (EM_BLOCK_A | EM_BLOCK_D)) != 0) {  // (the launches with an FFN)
+  if constexpr (RELU && (MODE & (EM_BLOCK_A | EM_BLOCK_D | EM_BLOCK_T)) != 0) {  // (the launches with an FFN)
     nsplit = a_in.ffn_split > 1 ? a_in.ffn_split : 1;
     if (nsplit > 1) {
       const int nch_all = ((a_in.ff >> 6) + 1) & ~1, nch_s = nch_all / nsplit, sidx = blockIdx.z;
@@ -164,7 +164,11 @@ __global__ __launch_bounds__(NT, 1) void block_kernel(const EmBlockArgs a_in, lo
   constexpr bool CTC = (MODE & EM_BLOCK_CTC) != 0;
   constexpr bool FOLD = HAS_C && HAS_D;  // the C part computed in this launch, for 64 frames (round 4)
   constexpr bool ATT = (MODE & EM_BLOCK_ATT) != 0;  // the attention of the workgroup's 32 queries in front of the C part (round 6)
-  static_assert(!ATT || (HAS_C && !HAS_D && !HAS_A && !FINAL), "block<ATT|C> is the only instantiation with the attention phase");
+  // The contextual-block streaming TRANSFORMER layer (include/espnet_amd.h, EM_BLOCK_T / EM_BLOCK_Q): T = attention + linear_out +
+  // residual + norm2 + FFN + residual, Q = norm1 + q / k / v per head (of the NEXT layer when it follows T in one launch)
+  constexpr bool HAS_T = (MODE & EM_BLOCK_T) != 0, HAS_Q = (MODE & EM_BLOCK_Q) != 0;
+  static_assert(!(HAS_T || HAS_Q) || (RELU && !HAS_C && !HAS_D && !HAS_A && !FINAL && !CTC && ATT == HAS_T), "block<ATT|T>, block<Q>, block<ATT|T|Q>");
+  static_assert(!ATT || ((HAS_C != HAS_T) && !HAS_D && !HAS_A && !FINAL), "block<ATT|C> and block<ATT|T..> are the instantiations with the attention phase");
   static_assert(!FOLD || KWT == 31, "the folded C part is written for the 15-frame halo of k = 31");
   extern __shared__ __attribute__((aligned(1024))) unsigned char smem[];
   unsigned char* const abuf = smem + ABUF_OFF;
@@ -453,7 +457,8 @@ __global__ __launch_bounds__(NT, 1) void block_kernel(const EmBlockArgs a_in, lo
     const int worker = (int)((blockIdx.y * gridDim.x + blockIdx.x) >> 3) * 4 + wave;
     const unsigned dst = TOUCH_OFF + wave * 256;
     const int loff = lane * 128;
-    int total = (HAS_C ? 48 : 0) + (HAS_D ? 16 + 8 * nch : 0) + (HAS_A ? 48 + 8 * nch : 0);  // 8 KiB chunks of the launch
+    int total = (HAS_C ? 48 : 0) + (HAS_D ? 16 + 8 * nch : 0) + (HAS_A ? 48 + 8 * nch : 0) + (HAS_T ? 16 + 8 * nch : 0) +
+                (HAS_Q ? 48 : 0);  // 8 KiB chunks of the launch
     if (CTC) total += a.ctc_units * 4;
 #pragma unroll 1
     for (int i = 0; i < MAXT && worker + i * nworker < total; ++i) {
@@ -479,6 +484,12 @@ __global__ __launch_bounds__(NT, 1) void block_kernel(const EmBlockArgs a_in, lo
         take(ffm_w2, nch * 4);
         take(a.wqkv, 48);
       }
+      if (HAS_T) {
+        take(a.wout, 16);
+        take(ff_w1, nch * 4);
+        take(ff_w2, nch * 4);
+      }
+      if (HAS_Q) take(a.wqkv, 48);
       if (CTC) take(a.ctc_w, a.ctc_units * 4);
       // LDS-DMA (global_load_lds_dword: the word goes to LDS at M0 + 4 * lane, no destination register that a
       // late return could clobber), from inline asm: a C++ load with no use is dropped, one with a use only at
@@ -740,7 +751,7 @@ __global__ __launch_bounds__(NT, 1) void block_kernel(const EmBlockArgs a_in, lo
         // order: deterministic); the others are done.  Nobody waits for anybody: no deadlock whatever the residency.
         // (MI355X_MICROARCH.md, "valid forms": plain stores -> __syncthreads -> lane-0 release fence -> drained -> relaxed
         // agent atomic; consumer: one agent acquire -> __syncthreads -> plain loads.)
-        const int wg = b * (int)gridDim.x + (int)blockIdx.x;
+        const int wg = b * (int)gridDim.x + (ATT ? t0 / BM : (int)blockIdx.x);  // (ATT: the workgroups of a group of eight blocks are dealt anew, see the top)
         float4* const part = (float4*)a.ffn_part + ((size_t)wg * nsplit) * 8 * NT;
         float4* const mine = part + (size_t)blockIdx.z * 8 * NT + tid;
         // Developer builds (profiles/r06u_stream_seam_ab*.txt): EM_BLOCK_VAR & 8192 = agent-scope (sc1) stores and no release
@@ -872,7 +883,12 @@ __global__ __launch_bounds__(NT, 1) void block_kernel(const EmBlockArgs a_in, lo
   // travel while the conv computes: per-wave stamps (profiles/r03a_block_stamps_fine.txt) showed the workgroup
   // sitting 7 500 cycles in the ISSUE of one 240 KiB burst (every CU of the chip asks at once: ~33 B/clk per CU)
   // before the conv could start on the 64 KiB it actually needs.
-  constexpr int NG = HAS_D ? (HAS_A ? 4 : 3) : (HAS_C ? 1 : 2);
+  constexpr int NG = (HAS_T || HAS_Q) ? (HAS_T && HAS_Q ? 2 : 1) : HAS_D ? (HAS_A ? 4 : 3) : (HAS_C ? 1 : 2);
+  if constexpr (HAS_T && HAS_Q) {
+    // (the hand-over's row - the previous call's context vector of this layer, slot 0 behind the FFN - goes to the third
+    // group's place with the parameter lines: in LDS long before it is wanted, no load in the chain behind the FFN)
+    dma_lines(a.row0_src + (size_t)b * a.row_stride, PAR_OFF + 2 * PAR_BYTES, std::integral_constant<int, 1>{});
+  }
   if (FOLD) {
     dma_lines(a.params_c, CPAR_OFF, std::integral_constant<int, PAR_BYTES / 1024>{});  // the C part's group goes first
   } else if (HAS_D) {
@@ -886,7 +902,8 @@ __global__ __launch_bounds__(NT, 1) void block_kernel(const EmBlockArgs a_in, lo
   const float* const pb2 = par + 2 * PAR_FLOATS;
   const float* const pb3 = par + 3 * PAR_FLOATS;
 
-  if (HAS_C && !HAS_D) {
+  // (a lambda: block<ATT|C|RELU> and the streaming Transformer's block<ATT|T..> open with it)
+  auto att_plain = [&]() __attribute__((always_inline)) {
     if constexpr (ATT && RELU) {
       // ---- Round 6, streaming layers: the plain multi-head attention over a block's slots (contextual_block_encoder_layer.py:
       // 236-262; attention.py:100-151) IN this launch - what csrc/streaming.hip `cb_mha_heads_mfma_kernel` did in a launch of
@@ -999,6 +1016,11 @@ __global__ __launch_bounds__(NT, 1) void block_kernel(const EmBlockArgs a_in, lo
       bar(0);  // the context tile is complete; the parameter groups are in LDS
       load_act();
       stamp(4);
+    }
+  };
+  if (HAS_C && !HAS_D) {
+    if constexpr (ATT && RELU) {
+      att_plain();
     } else if constexpr (ATT) {
       // ---- Round 6: the relative-position self-attention of the workgroup's 32 queries, IN this launch
       // (RelPositionMultiHeadedAttention.forward, attention.py:416-459; rel_shift :391-408; forward_attention :121-151):
@@ -1826,8 +1848,8 @@ __global__ __launch_bounds__(NT, 1) void block_kernel(const EmBlockArgs a_in, lo
       touch_done();
       return;
     }
-  } else {
-    // (A alone.  One block per stream and call of the streaming layers: slot 0 is the previous call's context vector of the
+  } else if (!HAS_T) {
+    // (A alone - or Q alone, the streaming Transformer's.  One block per stream and call of the streaming layers: slot 0 is the previous call's context vector of the
     // layer in front, read from where that call left it - EmBlockArgs.row0_src - instead of a hand-over launch copying it
     // into x first; a select on the address, no branch around the loads)
     const bool ctx_slot = a.row0_src != nullptr && t0 == 0 && lr == 0;
@@ -1838,38 +1860,10 @@ __global__ __launch_bounds__(NT, 1) void block_kernel(const EmBlockArgs a_in, lo
     for (int f = 0; f < 4; ++f) xr[1][f] = *(const float4*)(a.x + mrow[1] * D + 64 * f + ncol);
   }
 
-  if (HAS_A) {
-    // GA (buffer 0): [norm_ff_macaron g 256][b 256][ffm b1 1024][ffm b2 256]
-    // GA+1 (buffer 1): [norm_mha g 256][b 256][bq | bk | bv 768]
-    // norm_ff_macaron.  After a D part, buffer 1 still holds G1 (norm_final read it just before this
-    // LayerNorm's first barrier): its successor may come in at this LayerNorm's last barrier.
-    stamp(30);
-    const float* const pa0 = HAS_D ? pb2 : pb0;  // GA
-    const float* const pa1 = HAS_D ? pb3 : pb1;  // GA + 1
-    if constexpr (HAS_D) {  // (the macaron module's first units were requested by the feed-forward module in front of it)
-      ln_to_act(pa0, 0, 256, 0);
-    } else {
-      touch();
-      ln_to_act_pre(pa0, 0, 256, 0,
-                    [&] { read_unit(ffm_w1, 0, ring[0]); read_unit(ffm_w1, 1, ring[1]); read_w2(ffm_w2, 0, 0, ring[2]); }, std::integral_constant<int, 24>{},
-                    [&] { read_w2(ffm_w2, 0, 1, ring[3]); }, std::integral_constant<int, 8>{});
-    }
-    stamp(15);
-    // x += 0.5 * FFN_macaron(norm_ff_macaron(x))  (encoder_layer.py:108-121); the ring goes over to the q / k / v projections
-    ffn(pa0, 512, 1536, 0.5f, ffm_w1, ffm_w2, true, ffm_b1g, a.wqkv, [&] { read_unit(a.wqkv, 2, ring[2]); });
-    if constexpr (RELU) {
-      if (ffn_exit) return;
-    }
-    stamp(22);
-    // (x is stored at the very END of the kernel, from its LDS parking place: its eight 16-byte stores per lane, issued
-    // in front of the q / k / v weight requests, sat in the same in-order count the waits for those requests use and
-    // their slow acknowledgement from L2 stalled the stream - norm_mha took 4 300 cycles to its first barrier against
-    // 3 100 for the other LayerNorms.  The q / k / v stores themselves stay inside the stream: batched behind it they
-    // cost MORE, a store-issue tail of 3 300 cycles that the stream otherwise hides; profiles/r03c_*)
-    ln_to_act(pa1, 0, 256, 0);                     // norm_mha (encoder_layer.py:123-127)
-    stamp(15);
-    // q / k / v projections (attention.py:91-97), written per head: Q, K as [B][H][Tpad][64], V transposed
-    // as [B][H][64][Tpad] (computed with the MFMA operands swapped so a lane holds 4 consecutive frames).
+  // q / k / v projections (attention.py:91-97), written per head: Q, K as [B][H][Tpad][64], V transposed
+  // as [B][H][64][Tpad] (computed with the MFMA operands swapped so a lane holds 4 consecutive frames).
+  // (a lambda: the A part and the streaming Transformer's Q part end with it; pa1: [norm g | b | bq bk bv], qo / ko / vo: where to)
+  auto qkv_proj = [&](const float* pa1, void* qo, void* ko, void* vo) __attribute__((always_inline)) {
     const int H = D / 64;
     stream_k(a.wqkv, std::integral_constant<int, 12>{}, [&](const WF& cur, int u) {
       const int which = u >> 2, head = u & 3;
@@ -1914,25 +1908,139 @@ __global__ __launch_bounds__(NT, 1) void block_kernel(const EmBlockArgs a_in, lo
       // a.kv_frag (round 6, for block<ATT|C>): K and V^T go out FRAGMENT-MAJOR per 64-key tile, the order in which the
       // attention's MFMAs take them (EmBlockArgs.kv_frag in the header) - the same 16-byte pieces at other addresses
       if (which == 0 || (which == 1 && !a.kv_frag)) {
-        bf16* const dst = (bf16*)(which ? a.kh : a.qh) + (bh * a.Tpad + t0 + odd * 16 + lr) * 64 + nf * 16 + (lg & ~1) * 4;
+        bf16* const dst = (bf16*)(which ? ko : qo) + (bh * a.Tpad + t0 + odd * 16 + lr) * 64 + nf * 16 + (lg & ~1) * 4;
         *(u32x4*)dst = o;
       } else if (which == 1) {
         const int j = t0 + odd * 16 + lr, jl = j & 63;                                  // key, columns 16 nf + 4 (lg & ~1) .. + 7
         const int n = 2 * (jl >> 5) + ((jl >> 2) & 1), lrk = 4 * ((jl >> 3) & 3) + (jl & 3);  // fragment and row of key jl of a tile
         const int lgk = (nf & 1) * 2 + (lg >> 1);                                        // k-slice of the 32-deep step nf >> 1
-        unsigned char* const dst = (unsigned char*)a.kh + bh * a.Tpad * 128 + (size_t)(j >> 6) * 8192 + n * 2048 + (nf >> 1) * 1024 +
+        unsigned char* const dst = (unsigned char*)ko + bh * a.Tpad * 128 + (size_t)(j >> 6) * 8192 + n * 2048 + (nf >> 1) * 1024 +
                                    (16 * lgk + lrk) * 16;
         *(u32x4*)dst = o;
       } else if (!a.kv_frag) {
-        bf16* const dst = (bf16*)a.vt + (bh * 64 + nf * 16 + lr) * a.Tpad + t0 + odd * 16 + (lg & ~1) * 4;
+        bf16* const dst = (bf16*)vo + (bh * 64 + nf * 16 + lr) * a.Tpad + t0 + odd * 16 + (lg & ~1) * 4;
         *(u32x4*)dst = o;
       } else {
         const int j = t0 + odd * 16 + (lg & ~1) * 4, jl = j & 63;                        // eight consecutive keys of row 16 nf + lr
-        unsigned char* const dst = (unsigned char*)a.vt + bh * 64 * (size_t)a.Tpad * 2 + (size_t)(j >> 6) * 8192 + nf * 2048 +
+        unsigned char* const dst = (unsigned char*)vo + bh * 64 * (size_t)a.Tpad * 2 + (size_t)(j >> 6) * 8192 + nf * 2048 +
                                    (jl >> 5) * 1024 + (16 * ((jl & 31) >> 3) + lr) * 16;
         *(u32x4*)dst = o;
       }
     });
+  };
+  if constexpr (HAS_T || HAS_Q) {
+    // ---- The contextual-block streaming TRANSFORMER layer (transformer/contextual_block_encoder_layer.py forward_infer,
+    // normalize_before, no concat_after):  x += self_attn(norm1(x), mask);  x += w_2(relu(w_1(norm2(x)))).  Less than the
+    // Conformer layer's three launches hold - no macaron module, no convolution module, no norm_final - so: block<Q> (norm1 +
+    // q / k / v per head) and block<ATT|T> (attention, linear_out + residual, norm2, FFN + residual), or block<ATT|T|Q> with
+    // the NEXT layer's norm1 + q / k / v behind the FFN (one block per stream: nothing crosses workgroups there).
+    const float* const pq = HAS_T ? pb1 : pb0;  // the Q part's group: [norm1 g 256][b 256][bq | bk | bv 768]
+    if constexpr (HAS_T) {
+      att_plain();  // (requests linear_out's first units and the residual rows; the context tile is in `act`)
+      // G0: [bout 256][norm2 g 256][b 256][ff b2 256]
+      // linear_out + residual (attention.py:151); the ring goes over to the feed-forward module
+      proj_resid(pb0, 0, a.wout, [&](int j) {
+        if (j == 0) read_unit(ff_w1, 0, ring[0]);
+        else if (j == 1) read_unit(ff_w1, 1, ring[1]);
+        else if (j == 2) read_w2(ff_w2, 0, 0, ring[2]);
+        else read_w2(ff_w2, 0, 1, ring[3]);
+      });
+      stamp(50);
+      ln_to_act(pb0, 256, 512, 0);  // norm2
+      stamp(15);
+      // x += FFN(norm2(x)), scale 1; with a Q part behind it the ring goes over to the next layer's q / k / v projections
+      if constexpr (HAS_Q)
+        ffn(pb0, 0, 768, 1.0f, ff_w1, ff_w2, true, ff_b1g, a.wqkv, [&] { read_unit(a.wqkv, 2, ring[2]); });
+      else
+        ffn(pb0, 0, 768, 1.0f, ff_w1, ff_w2, false, ff_b1g, nullptr, [] {});
+      if (ffn_exit) return;  // (split FFN: another share of this row block carries the rows on)
+      stamp(22);
+      // (one block per stream and call: the block's last slot is this call's context vector of the layer, EmBlockArgs.last_dst)
+      if (a.last_dst) {
+        float* const dst = a.last_dst + (size_t)b * a.row_stride;
+#pragma unroll
+        for (int mi = 0; mi < 2; ++mi)
+          if (t0 + mi * 16 + lr == T - 1) {
+#pragma unroll
+            for (int f = 0; f < 4; ++f) *(float4*)(dst + 64 * f + ncol) = xr[mi][f];
+          }
+      }
+      if constexpr (!HAS_Q) {
+        store_x();
+        touch_done();
+        return;
+      } else {
+        // the hand-over (contextual_block_encoder_layer.py, the end of forward_infer): slot 0 := the previous call's context
+        // vector of this layer, from its LDS copy - in the registers the next layer's norm1 reads and in the parked copy
+        // that is stored at the end
+        if (t0 == 0 && lr == 0) {
+          float4* const xpk = (float4*)(smem + TILE_OFF) + tid;
+#pragma unroll
+          for (int f = 0; f < 4; ++f) {
+            xr[0][f] = *(const float4*)(pb2 + 64 * f + ncol);
+            xpk[f * NT] = xr[0][f];
+          }
+        }
+        ln_to_act(pq, 0, 256, 0);  // the next layer's norm1
+      }
+    } else {
+      // (Q alone: slot 0 came from row0_src above - keep it in x, the launch behind this one reads its residual rows there)
+      if (a.row0_src != nullptr && t0 == 0 && lr == 0) {
+#pragma unroll
+        for (int f = 0; f < 4; ++f) *(float4*)(a.x + mrow[0] * D + 64 * f + ncol) = xr[0][f];
+      }
+      touch();
+      ln_to_act_pre(pq, 0, 256, 0,
+                    [&] { read_unit(a.wqkv, 0, ring[0]); read_unit(a.wqkv, 1, ring[1]); read_unit(a.wqkv, 2, ring[2]); }, std::integral_constant<int, 24>{},
+                    no_pre, std::integral_constant<int, 0>{});
+    }
+    stamp(15);
+    if constexpr (HAS_T) {
+      qkv_proj(pq, a.qh_out, a.kh_out, a.vt_out);
+      const float4* const xp = (const float4*)(smem + TILE_OFF) + tid;
+#pragma unroll
+      for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+        for (int f = 0; f < 4; ++f) xr[mi][f] = xp[(mi * 4 + f) * NT];
+      store_x();
+    } else {
+      qkv_proj(pq, a.qh, a.kh, a.vt);
+    }
+    stamp(40);
+    touch_done();
+    return;
+  }
+  if (HAS_A) {
+    // GA (buffer 0): [norm_ff_macaron g 256][b 256][ffm b1 1024][ffm b2 256]
+    // GA+1 (buffer 1): [norm_mha g 256][b 256][bq | bk | bv 768]
+    // norm_ff_macaron.  After a D part, buffer 1 still holds G1 (norm_final read it just before this
+    // LayerNorm's first barrier): its successor may come in at this LayerNorm's last barrier.
+    stamp(30);
+    const float* const pa0 = HAS_D ? pb2 : pb0;  // GA
+    const float* const pa1 = HAS_D ? pb3 : pb1;  // GA + 1
+    if constexpr (HAS_D) {  // (the macaron module's first units were requested by the feed-forward module in front of it)
+      ln_to_act(pa0, 0, 256, 0);
+    } else {
+      touch();
+      ln_to_act_pre(pa0, 0, 256, 0,
+                    [&] { read_unit(ffm_w1, 0, ring[0]); read_unit(ffm_w1, 1, ring[1]); read_w2(ffm_w2, 0, 0, ring[2]); }, std::integral_constant<int, 24>{},
+                    [&] { read_w2(ffm_w2, 0, 1, ring[3]); }, std::integral_constant<int, 8>{});
+    }
+    stamp(15);
+    // x += 0.5 * FFN_macaron(norm_ff_macaron(x))  (encoder_layer.py:108-121); the ring goes over to the q / k / v projections
+    ffn(pa0, 512, 1536, 0.5f, ffm_w1, ffm_w2, true, ffm_b1g, a.wqkv, [&] { read_unit(a.wqkv, 2, ring[2]); });
+    if constexpr (RELU) {
+      if (ffn_exit) return;
+    }
+    stamp(22);
+    // (x is stored at the very END of the kernel, from its LDS parking place: its eight 16-byte stores per lane, issued
+    // in front of the q / k / v weight requests, sat in the same in-order count the waits for those requests use and
+    // their slow acknowledgement from L2 stalled the stream - norm_mha took 4 300 cycles to its first barrier against
+    // 3 100 for the other LayerNorms.  The q / k / v stores themselves stay inside the stream: batched behind it they
+    // cost MORE, a store-issue tail of 3 300 cycles that the stream otherwise hides; profiles/r03c_*)
+    ln_to_act(pa1, 0, 256, 0);                     // norm_mha (encoder_layer.py:123-127)
+    stamp(15);
+    qkv_proj(pa1, a.qh, a.kh, a.vt);
     {
       const float4* const xp = (const float4*)(smem + TILE_OFF) + tid;
 #pragma unroll
@@ -1956,7 +2064,7 @@ int launch_block(const EmBlockArgs* a, hipStream_t s) {
   static int ncu_of[64];  // compute units per device (asked once: no runtime call on later launches, legal under stream capture)
   const int gx = em_cdiv(a->T, BM);
   // grid z: the shares of a split FFN (streaming launches with an FFN; EmBlockArgs.ffn_split)
-  const int zs = (RELU && (MODE & (EM_BLOCK_A | EM_BLOCK_D)) != 0 && a->ffn_split > 1) ? a->ffn_split : 1;
+  const int zs = (RELU && (MODE & (EM_BLOCK_A | EM_BLOCK_D | EM_BLOCK_T)) != 0 && a->ffn_split > 1) ? a->ffn_split : 1;
   int helper_rows = 0;
   if (!no_helpers) {
     int dev = 0, ncu = 256;
@@ -2021,11 +2129,22 @@ extern "C" int em_conformer_block_fused(int mode, const EmBlockArgs* a, void* st
   if (a->d != D || a->ff <= 0 || a->ff % 64 != 0 || a->ff > 4096) return EM_ERR_UNSUPPORTED;
   hipStream_t s = (hipStream_t)stream;
   const bool need_a = (mode & EM_BLOCK_A) != 0, need_d = (mode & EM_BLOCK_D) != 0;
+  const bool need_t = (mode & EM_BLOCK_T) != 0, need_q = (mode & EM_BLOCK_Q) != 0;  // the streaming Transformer layer
   // the first FFN bias lives in the 7 KiB parameter group up to ff = 1024; wider FFNs hand it over in global memory
   if (!relu && a->ff > 1024 && (need_a || need_d)) return EM_ERR_UNSUPPORTED;  // (the C part has no FFN)
+  if (need_t || need_q) {
+    if (!relu || (mode != EM_BLOCK_Q && mode != (EM_BLOCK_ATT | EM_BLOCK_T) && mode != (EM_BLOCK_ATT | EM_BLOCK_T | EM_BLOCK_Q))) return EM_ERR_UNSUPPORTED;
+    if (!a->qh || !a->kh || !a->vt || a->kv_frag || a->T > 64 || a->Tpad % 64 != 0 || a->Tpad < em_cdiv(a->T, BM) * BM) return EM_ERR_BAD_ARG;
+    if (need_t && (!a->wout || !a->ff_w1 || !a->ff_w2 || !a->ff_b1g)) return EM_ERR_BAD_ARG;
+    if (need_q && !a->wqkv) return EM_ERR_BAD_ARG;
+    if (need_t && need_q) {  // the next layer's q / k / v go to buffers of their own; the hand-over rides in the launch
+      if (!a->qh_out || !a->kh_out || !a->vt_out || a->qh_out == a->qh || a->kh_out == a->kh || a->vt_out == a->vt) return EM_ERR_BAD_ARG;
+      if (!a->row0_src || !a->last_dst) return EM_ERR_BAD_ARG;
+    }
+  }
   if (relu && ((need_a && !a->ffm_b1g) || (need_d && !a->ff_b1g))) return EM_ERR_BAD_ARG;  // (these instantiations always read it there)
-  if (relu && mode != EM_BLOCK_A && mode != EM_BLOCK_D && mode != (EM_BLOCK_ATT | EM_BLOCK_C)) return EM_ERR_UNSUPPORTED;  // (the instantiations that exist)
-  if (a->ffn_split > 1 && (need_a || need_d)) {  // split FFN (streaming instantiations): whole pairs of 64-wide chunks per share; a launch without an FFN ignores it
+  if (relu && !need_t && !need_q && mode != EM_BLOCK_A && mode != EM_BLOCK_D && mode != (EM_BLOCK_ATT | EM_BLOCK_C)) return EM_ERR_UNSUPPORTED;  // (the instantiations that exist)
+  if (a->ffn_split > 1 && (need_a || need_d || need_t)) {  // split FFN (streaming instantiations): whole pairs of 64-wide chunks per share; a launch without an FFN ignores it
     const int nch_all = ((a->ff >> 6) + 1) & ~1;
     if (!relu || a->ffn_split > 16 || nch_all % (2 * a->ffn_split) != 0 || !a->ffn_part || !a->ffn_ticket) return EM_ERR_BAD_ARG;
   }
@@ -2039,7 +2158,7 @@ extern "C" int em_conformer_block_fused(int mode, const EmBlockArgs* a, void* st
     if (a->kernel != (relu ? 15 : 31)) return EM_ERR_UNSUPPORTED;
   }
   if (mode == EM_BLOCK_C && (!a->ctx || !a->glu || !a->wout || !a->pw1f)) return EM_ERR_BAD_ARG;
-  if (mode & EM_BLOCK_ATT) {  // attention + the C part in one launch (round 6)
+  if ((mode & EM_BLOCK_ATT) && !need_t) {  // attention + the C part in one launch (round 6)
     if (mode != (EM_BLOCK_ATT | EM_BLOCK_C)) return EM_ERR_UNSUPPORTED;
     if (!a->glu || !a->wout || !a->pw1f || !a->qh || !a->kh || !a->vt) return EM_ERR_BAD_ARG;
     if (a->Tpad % 64 != 0 || a->Tpad < em_cdiv(a->T, BM) * BM) return EM_ERR_BAD_ARG;
@@ -2065,11 +2184,16 @@ extern "C" int em_conformer_block_fused(int mode, const EmBlockArgs* a, void* st
   if (mode & EM_BLOCK_ATT) flops += 6.0 * a->B * 4 * (double)a->T * a->T * 64;
   if (mode & EM_BLOCK_D) flops += 2.0 * M * D * (D + 2.0 * a->ff);
   if (mode & EM_BLOCK_A) flops += 2.0 * M * D * (2.0 * a->ff + 3 * D);
+  if (need_t) flops += 2.0 * M * D * (D + 2.0 * a->ff);
+  if (need_q) flops += 2.0 * M * D * 3 * D;
   if (mode & EM_BLOCK_CTC) flops += 2.0 * M * D * 64.0 * a->ctc_units;
   const bool rec = em_prof_begin(stream);
   int rc = EM_ERR_BAD_ARG;
   if (relu) {
-    if (mode == EM_BLOCK_A) rc = launch_block<EM_BLOCK_A, 31, true>(a, s);
+    if (mode == EM_BLOCK_Q) rc = launch_block<EM_BLOCK_Q, 31, true>(a, s);
+    else if (mode == (EM_BLOCK_ATT | EM_BLOCK_T)) rc = launch_block<EM_BLOCK_ATT | EM_BLOCK_T, 31, true>(a, s);
+    else if (mode == (EM_BLOCK_ATT | EM_BLOCK_T | EM_BLOCK_Q)) rc = launch_block<EM_BLOCK_ATT | EM_BLOCK_T | EM_BLOCK_Q, 31, true>(a, s);
+    else if (mode == EM_BLOCK_A) rc = launch_block<EM_BLOCK_A, 31, true>(a, s);
     else if (mode == (EM_BLOCK_ATT | EM_BLOCK_C)) rc = launch_block<EM_BLOCK_ATT | EM_BLOCK_C, 31, true>(a, s);
     else rc = launch_block<EM_BLOCK_D, 15, true>(a, s);
     if (rec) em_prof_end(stream, flops, EM_PROF_BLOCK);

@@ -599,6 +599,17 @@ extern "C" int em_cb_propagate_ctx_f32(float* x, const float* past_ctx, float* n
   return EM_OK;
 }
 
+// The same for n_streams lock-step streams of n_blk blocks each: x [n_streams][n_blk][L][d], the context vectors of stream s at
+// past_ctx / next_ctx + s * ctx_stride floats (the launch em_cb_encode_blocks_batch makes between layers; csrc/streaming_tf.hip)
+extern "C" int em_cb_propagate_ctx_batch_f32(float* x, const float* past_ctx, float* next_ctx, int32_t n_streams,
+                                             int32_t n_blk, int32_t L, int32_t d, int32_t ctx_stride, void* stream) {
+  if (!x || n_streams <= 0 || n_blk <= 0 || L < 2 || d <= 0 || ctx_stride < 0) return EM_ERR_BAD_ARG;
+  hipLaunchKernelGGL(cb_propagate_ctx_kernel, dim3(n_blk, n_streams), dim3(256), 0, (hipStream_t)stream, x, past_ctx, next_ctx,
+                     n_blk, L, d, ctx_stride);
+  EM_CHECK_LAUNCH();
+  return EM_OK;
+}
+
 extern "C" size_t em_cb_workspace_bytes(int dtype, const EmConformerWeights* w, int32_t n_blk,
                                         int32_t L) {
   if (!w || n_blk <= 0 || L <= 0) return 0;

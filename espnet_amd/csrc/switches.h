@@ -22,7 +22,8 @@ struct EmSwitches {
   int stream_fused_min;                                              // ESPNET_AMD_STREAM_FUSED_MIN (default 1; 8 in rounds 4 - 5)
   bool stream_split_att;                                             // ESPNET_AMD_STREAM_SPLIT_ATT
   int stream_ffn_split;                                              // ESPNET_AMD_STREAM_FFN_SPLIT (0: automatic; 1: off; n: forced)
-  bool no_sub12;                                                     // ESPNET_AMD_NO_SUB12
+  int stream_tf_merge;                                               // ESPNET_AMD_STREAM_TF_MERGE (streaming Transformer: 1 = a layer's second launch also runs the next layer's norm1 + q / k / v; 0 = two launches per layer; -1: the default, csrc/streaming_tf.hip)
+  bool no_sub12;                                                   // ESPNET_AMD_NO_SUB12
   int ffn_rows_min_fill;                                             // ESPNET_AMD_FFN_ROWS_MIN_FILL (percent of the CUs a round of 64-row workgroups must fill; 0 = automatic: 72 / batches in flight)
   int dec_ffn_rows;                                                  // ESPNET_AMD_DEC_FFN_ROWS (16 | 32 rows per workgroup of ln_frag_gemm_kernel; 0: automatic, 32 from 320 rows)
   int dec_ffn_split;                                                 // ESPNET_AMD_DEC_FFN_SPLIT (0: automatic; 1: off - LayerNorm + two projections; n: forced)

@@ -21,6 +21,9 @@ from espnet_amd.asr.encoder.conformer_encoder import ConformerEncoder as _Confor
 from espnet_amd.asr.encoder.contextual_block_conformer_encoder import (
     ContextualBlockConformerEncoder as _ContextualBlockConformerEncoder,
 )
+from espnet_amd.asr.encoder.contextual_block_transformer_encoder import (
+    ContextualBlockTransformerEncoder as _ContextualBlockTransformerEncoder,
+)
 from espnet_amd.asr.encoder.e_branchformer_encoder import BranchformerEncoder as _BranchformerEncoder
 from espnet_amd.asr.encoder.e_branchformer_encoder import EBranchformerEncoder as _EBranchformerEncoder
 from espnet_amd.asr.frontend.default import DefaultFrontend as _DefaultFrontend
@@ -69,6 +72,30 @@ class MI355XContextualBlockConformerEncoder(_ContextualBlockConformerEncoder, Ab
     """espnet2/asr/encoder/contextual_block_conformer_encoder.py:34-600 (forward_infer streaming path)."""
 
 
+class MI355XContextualBlockTransformerEncoder(_ContextualBlockTransformerEncoder, AbsEncoder):
+    """espnet2/asr/encoder/contextual_block_transformer_encoder.py (forward_infer streaming path).
+
+    Options outside the MI355X path (`normalize_before=False`, `concat_after=True`, another input layer, ...) build the STOCK
+    espnet2 `ContextualBlockTransformerEncoder` with the same arguments and say so in the log, as `mi355x_conformer` does."""
+
+    def __new__(cls, *args, **kwargs):
+        if not args and not kwargs:  # copy.deepcopy / pickle re-create a Module through cls.__new__(cls) alone
+            return super().__new__(cls)
+        bad = _ContextualBlockTransformerEncoder.unsupported_options(*args, **kwargs)
+        if bad:
+            import logging
+
+            from espnet2.asr.encoder.contextual_block_transformer_encoder import (
+                ContextualBlockTransformerEncoder as _Stock,
+            )
+
+            kwargs.pop("compute_dtype", None)  # the one keyword the stock class does not know
+            logging.warning("mi355x_contextual_block_transformer: %s outside the MI355X fast path -> stock espnet2 "
+                            "ContextualBlockTransformerEncoder (reference code path, not accelerated)", ", ".join(bad))
+            return _Stock(*args, **kwargs)  # not an instance of cls: Python does not call cls.__init__ on it
+        return super().__new__(cls)
+
+
 class MI355XDefaultFrontend(_DefaultFrontend, AbsFrontend):
     """espnet2/asr/frontend/default.py:22-171."""
 
@@ -104,7 +131,8 @@ class MI355XLengthBonus(_LengthBonus, BatchScorerInterface):
 ADAPTERS = {
     "encoder": {"mi355x_conformer": MI355XConformerEncoder, "mi355x_e_branchformer": MI355XEBranchformerEncoder,
                 "mi355x_branchformer": MI355XBranchformerEncoder,
-                "mi355x_contextual_block_conformer": MI355XContextualBlockConformerEncoder},
+                "mi355x_contextual_block_conformer": MI355XContextualBlockConformerEncoder,
+                "mi355x_contextual_block_transformer": MI355XContextualBlockTransformerEncoder},
     "frontend": {"mi355x_default": MI355XDefaultFrontend},
     "normalize": {"mi355x_global_mvn": MI355XGlobalMVN, "mi355x_utterance_mvn": MI355XUtteranceMVN},
     "decoder": {"mi355x_transformer": MI355XTransformerDecoder},

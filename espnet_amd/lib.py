@@ -35,6 +35,7 @@ def EM_ENC_IN_FLIGHT(n):
 
 EM_ENC_PLAN_FUSED, EM_ENC_PLAN_CTC_IDS = 1, 2
 EM_BLOCK_C, EM_BLOCK_D, EM_BLOCK_A, EM_BLOCK_FINAL, EM_BLOCK_CTC, EM_BLOCK_RELU, EM_BLOCK_ATT = 1, 2, 4, 8, 16, 32, 64
+EM_BLOCK_T, EM_BLOCK_Q = 128, 256  # the contextual-block streaming Transformer layer (csrc/block.hip)
 EM_BLOCK_PARAM_GROUP = 1792
 EM_BLOCK_CTC_MAX_UNITS = 88  # vocabularies up to 5 632 labels take the fused CTC stage (the sizes the GPU tests cover); larger ones keep the arg-max GEMM
 EM_PROF_GEMM, EM_PROF_BLOCK, EM_PROF_ATTN, EM_PROF_ROWS = 0, 1, 2, 3
@@ -82,7 +83,8 @@ class EmBlockArgs(C.Structure):
                [("x_out", C.c_void_p), ("params_c", C.c_void_p), ("ffm_b1g", C.c_void_p), ("ff_b1g", C.c_void_p),
                 ("row0_src", C.c_void_p), ("last_dst", C.c_void_p), ("row_stride", C.c_int32), ("ldp", C.c_int32),
                 ("pos", C.c_void_p), ("pos_u", C.c_void_p), ("pos_v", C.c_void_p), ("klens", C.c_void_p), ("kv_frag", C.c_int32),
-                ("ffn_split", C.c_int32), ("ffn_part", C.c_void_p), ("ffn_ticket", C.c_void_p), ("att_mask", C.c_int32)]
+                ("ffn_split", C.c_int32), ("ffn_part", C.c_void_p), ("ffn_ticket", C.c_void_p), ("att_mask", C.c_int32),
+                ("qh_out", C.c_void_p), ("kh_out", C.c_void_p), ("vt_out", C.c_void_p)]
 
 
 EM_ROWS_FFN, EM_ROWS_GLU = 0, 1
@@ -139,7 +141,7 @@ class EmEBranchformerWeights(C.Structure):
 
 # order of include/espnet_amd.h EmTransformerLayer
 _TRF_LAYER_PTRS = ["norm1_g", "norm1_b", "norm2_g", "norm2_b", "wqkv", "bqkv", "wout", "bout", "ff_w1", "ff_w2", "ff_b1",
-                   "ff_b2", "ff_w1p", "ff_w2p"]
+                   "ff_b2", "ff_w1p", "ff_w2p", "cb_wqkvp", "cb_woutp", "cb_ff_w1p", "cb_ff_w2p", "fp_t"]
 
 
 class EmTransformerLayer(C.Structure):
@@ -313,6 +315,13 @@ _SIGNATURES = {
     "em_cb_build_blocks_rows_f32": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
     "em_cb_encode_blocks_batch": (C.c_int, [C.c_int, C.POINTER(EmConformerWeights), _vp, _i32, _i32, _i32, _i32,
                                             _vp, _vp, _vp, _sz, _vp]),
+    "em_cb_propagate_ctx_batch_f32": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "em_cbt_workspace_bytes": (_sz, [C.c_int, C.POINTER(EmTransformerWeights), _i32, _i32]),
+    "em_cbt_encode_blocks": (C.c_int, [C.c_int, C.POINTER(EmTransformerWeights), _vp, _i32, _i32, _i32,
+                                       _vp, _vp, _vp, _sz, _vp]),
+    "em_cbt_encode_blocks_batch": (C.c_int, [C.c_int, C.POINTER(EmTransformerWeights), _vp, _i32, _i32, _i32, _i32,
+                                             _vp, _vp, _vp, _sz, _vp]),
+    "em_cbt_encode_plan": (C.c_int, [C.c_int, C.POINTER(EmTransformerWeights), _i32, _i32, _i32, _i32, _i32]),
     "em_profile_create": (_vp, [_i32]),
     "em_profile_destroy": (None, [_vp]),
     "em_profile_attach": (None, [_vp]),

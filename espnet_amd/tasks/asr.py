@@ -19,6 +19,7 @@ from espnet_amd.asr.ctc import CTC
 from espnet_amd.asr.decoder.transformer_decoder import TransformerDecoder
 from espnet_amd.asr.encoder.conformer_encoder import ConformerEncoder
 from espnet_amd.asr.encoder.contextual_block_conformer_encoder import ContextualBlockConformerEncoder
+from espnet_amd.asr.encoder.contextual_block_transformer_encoder import ContextualBlockTransformerEncoder
 from espnet_amd.asr.encoder.e_branchformer_encoder import BranchformerEncoder, EBranchformerEncoder
 from espnet_amd.asr.encoder.transformer_encoder import TransformerEncoder
 from espnet_amd.asr.espnet_model import ESPnetASRModel
@@ -30,6 +31,7 @@ frontend_choices = {"default": DefaultFrontend}
 normalize_choices = {"utterance_mvn": UtteranceMVN, "global_mvn": GlobalMVN}
 encoder_choices = {"conformer": ConformerEncoder,
                    "contextual_block_conformer": ContextualBlockConformerEncoder,
+                   "contextual_block_transformer": ContextualBlockTransformerEncoder,
                    "e_branchformer": EBranchformerEncoder, "branchformer": BranchformerEncoder,
                    "transformer": TransformerEncoder}
 decoder_choices = {"transformer": TransformerDecoder}

@@ -388,6 +388,20 @@ int em_conformer_encode(int dtype, const EmConformerWeights* w, const float* fea
                           * em_relpos_attention2_bf16 + block<C>, the context `ctx` never exists in memory.  Inputs qh / kh / vt
                           * as A wrote them, plus pos / ldp / pos_u / pos_v / klens below (em_relpos_attention2_bf16's
                           * arguments of the same names).  Any T; d = 256, 4 heads of 64. */
+/* The contextual-block streaming TRANSFORMER layer (transformer/contextual_block_encoder_layer.py forward_infer:
+ * x += self_attn(norm1(x)); x += w_2(relu(w_1(norm2(x))))), always with EM_BLOCK_RELU:
+ *   EM_BLOCK_Q                 : norm1 -> q / k / v per head (the tail of EM_BLOCK_A without the macaron FFN; x is only
+ *                                read, except slot 0 when row0_src replaces it).  params: [norm1 g | b | bq bk bv 768]
+ *   EM_BLOCK_ATT | EM_BLOCK_T  : plain attention over the block's T <= 64 slots (as EM_BLOCK_ATT | EM_BLOCK_C | EM_BLOCK_RELU)
+ *                                -> linear_out + residual -> norm2 -> FFN (ReLU, scale 1; ff_w1 / ff_w2 / ff_b1g, ffn_split
+ *                                honoured) + residual -> x, last slot -> last_dst.  params: [bout | norm2 g | b | ff b2]
+ *   EM_BLOCK_ATT | EM_BLOCK_T | EM_BLOCK_Q : the above, then slot 0 := row0_src (the hand-over), x stored, and the NEXT
+ *                                layer's norm1 -> q / k / v (wqkv = the next layer's) written to qh_out / kh_out / vt_out -
+ *                                buffers other than qh / kh / vt, which the launch's other workgroups are still reading.
+ *                                row0_src and last_dst both set (one block per stream).  params: the two groups above,
+ *                                T's first. */
+#define EM_BLOCK_T 128
+#define EM_BLOCK_Q 256
 #define EM_BLOCK_PARAM_GROUP 1792
 typedef struct EmBlockArgs {
   int32_t B, T, Tpad, d, ff, kernel;
@@ -472,6 +486,8 @@ typedef struct EmBlockArgs {
    * contextual mask (contextual_block_conformer_encoder.py:352-360): the last slot is no key; slot 0 attends to nothing and
    * its context is zero. */
   int32_t att_mask;
+  /* EM_BLOCK_ATT | EM_BLOCK_T | EM_BLOCK_Q: where the Q part writes the NEXT layer's q / k / V^T (layouts of qh / kh / vt). */
+  void *qh_out, *kh_out, *vt_out;
 } EmBlockArgs;
 int em_conformer_block_fused(int mode, const EmBlockArgs* args, void* stream);
 /* Position rows for EM_BLOCK_ATT: pall [2T-1][ldp] bf16 holds linear_pos of L blocks side by side (block l at columns
@@ -584,6 +600,12 @@ typedef struct EmTransformerLayer {
   /* bf16, d = 512, ff % 128 == 0: the operand streams of em_ffn_rows_fused (host: pack_ffn_rows_w1 / _w2) - the FFN +
    * residual + the next LayerNorm as one row-block launch when its rounds fill the chip - or NULL                  */
   const void *ff_w1p, *ff_w2p;
+  /* bf16, d = 256, 4 heads (the contextual-block streaming Transformer, em_cbt_encode_blocks): operands of the row-block
+   * launches EM_BLOCK_Q / EM_BLOCK_T (EmBlockArgs: K units, w_2 per pair of hidden chunks - NOT the layouts of ff_w1p /
+   * ff_w2p above), and fp_t = three parameter groups [norm1 g | b | bq bk bv] [bout | norm2 g | b | ff b2]
+   * [the NEXT layer's first group, zeros behind the last layer] (ff % 128 == 0: ff_b1 is read as it is).  Or NULL. */
+  const void *cb_wqkvp, *cb_woutp, *cb_ff_w1p, *cb_ff_w2p;
+  const float* fp_t;
 } EmTransformerLayer;
 
 typedef struct EmTransformerWeights {
@@ -1137,6 +1159,33 @@ int em_cb_build_blocks_rows_f32(const float* xs, const float* pe, const float* p
 int em_cb_encode_blocks_batch(int dtype, const EmConformerWeights* w, float* x, int32_t n_streams, int32_t n_blk,
                               int32_t L, int32_t mask_mode, const float* past_ctx, float* next_ctx, void* workspace,
                               size_t workspace_bytes, void* stream);
+/*   em_cb_propagate_ctx_f32 for such a batch: the context vectors of stream s at past_ctx / next_ctx + s * ctx_stride floats. */
+int em_cb_propagate_ctx_batch_f32(float* x, const float* past_ctx, float* next_ctx, int32_t n_streams, int32_t n_blk,
+                                  int32_t L, int32_t d, int32_t ctx_stride, void* stream);
+
+/* ---- The same for the contextual-block streaming TRANSFORMER encoder (espnet2/asr/encoder/
+ *      contextual_block_transformer_encoder.py; layer: transformer/contextual_block_encoder_layer.py forward_infer,
+ *      normalize_before, no concat_after): per block  x += self_attn(norm1(x), mask);  x += w_2(relu(w_1(norm2(x)))),
+ *      then the same context hand-over.  Block assembly, em_block_mha, em_cb_propagate_ctx_f32 and em_stream_pos_enc_f32
+ *      above are shared; arguments exactly as the em_cb_* calls of the same names, weights as EmTransformerWeights
+ *      (conv3_* / subsample unused: the embedding is Conv2dSubsamplingWOPosEnc, run by the host layer).
+ *      bf16, d = 256, 4 heads, L <= 64, ff % 128 == 0, ff <= 4096 and every layer's cb_* operands set: the row-block
+ *      launches EM_BLOCK_Q / EM_BLOCK_T of csrc/block.hip; anything else (and ESPNET_AMD_STREAM_NO_FUSED): six launches
+ *      per layer from the GEMM / LayerNorm-GEMM / attention kernels.                                                  */
+size_t em_cbt_workspace_bytes(int dtype, const EmTransformerWeights* w, int32_t n_blk, int32_t L);
+int em_cbt_encode_blocks(int dtype, const EmTransformerWeights* w, float* x, int32_t n_blk, int32_t L,
+                         int32_t mask_mode, const float* past_ctx, float* next_ctx, void* workspace,
+                         size_t workspace_bytes, void* stream);
+int em_cbt_encode_blocks_batch(int dtype, const EmTransformerWeights* w, float* x, int32_t n_streams, int32_t n_blk,
+                               int32_t L, int32_t mask_mode, const float* past_ctx, float* next_ctx, void* workspace,
+                               size_t workspace_bytes, void* stream);
+/*   Which launch sequence such a call takes (the switches as they stand): 0 = per-operator, 1 = the row-block launches with
+ *   the hand-over as its own launch (three per layer), 2 = hand-over folded into them (two per layer: the steady tick of one
+ *   block per stream with both context buffers), 3 = layer l's EM_BLOCK_T and layer l + 1's EM_BLOCK_Q as ONE launch
+ *   (num_blocks + 1 launches: the default; ESPNET_AMD_STREAM_TF_MERGE=0 gives 2).  has_ctx: past_ctx and next_ctx both
+ *   given and different. */
+int em_cbt_encode_plan(int dtype, const EmTransformerWeights* w, int32_t n_streams, int32_t n_blk, int32_t L,
+                       int32_t mask_mode, int32_t has_ctx);
 
 /* ---- optional per-launch timing of the GEMM kernel family (measurement only; bench.py's
  *      `roofline` leg).  While a profile is attached to the calling thread every em_gemm launch
