@@ -1,6 +1,6 @@
 """CTC head on the MI355X.  Mirrors espnet2/asr/ctc.py:9-215 for inference (`ctc_lo`,
-`softmax`/`log_softmax`/`argmax`); state-dict keys `ctc_lo.{weight,bias}`.  The loss is training
-only and out of scope."""
+`softmax`/`log_softmax`/`argmax`, `forced_align`); state-dict keys `ctc_lo.{weight,bias}`.  The loss is
+training only and out of scope."""
 import os
 
 import torch
@@ -83,6 +83,99 @@ class CTC(PackedModule):
         L.check(L.load().em_gemm(self.em_dtype, L.EM_EPI_ARGMAX_PART, L.EM_A_PLAIN, a, st), "em_gemm(ctc_lo, arg-max)")
         L.check(L.load().em_argmax_partials(L.ptr(part), B * T, G, L.ptr(ids), st), "em_argmax_partials")
         return ids if as_int32 else ids.to(torch.int64)
+
+    # ------------------------------------------------------------------ forced alignment (csrc/ctc_align.hip)
+    @staticmethod
+    def check_alignable(olens, targets, blank, vocab):
+        """The host-side checks of a forced alignment, before anything is launched: every id in [0, vocab) and not the
+        blank, and enough frames for the tokens (T_b >= L_b + number of adjacent equal tokens).  `targets`: one list
+        of ids per utterance.  Raises ValueError."""
+        for b, (T_b, y) in enumerate(zip(olens, targets)):
+            y = [int(v) for v in y]
+            if any(v == blank for v in y):
+                raise ValueError(f"utterance {b}: the blank id {blank} cannot be aligned")
+            if any(v < 0 or v >= vocab for v in y):
+                raise ValueError(f"utterance {b}: token ids must lie in [0, {vocab})")
+            need = len(y) + sum(1 for i in range(1, len(y)) if y[i] == y[i - 1])
+            if int(T_b) < max(need, 1):
+                raise ValueError(f"utterance {b}: {int(T_b)} encoder frames cannot carry {len(y)} tokens "
+                                 f"({need} frames needed)")
+
+    def forced_align_device(self, enc_act: torch.Tensor, olens, targets, ylens, blank: int):
+        """Viterbi alignment of `targets` to the CTC posteriors of enc_act (B,T,d) (compute dtype, on the device) for a
+        ragged batch, by `em_ctc_log_probs_t` -> `em_ctc_forced_align` (include/espnet_amd.h states the recursion and
+        the tie rule).  Returns (align (B,T) i32, frame_lp (B,T) f32, tok_start, tok_end (B,Lmax) i32, tok_lp (B,Lmax)
+        f32, total (B,) f32) as device tensors, no host sync.
+
+        olens / ylens: per-utterance lengths, targets (B, Lmax) ids padded with anything.  Given as HOST data (lists or
+        CPU tensors) they are checked first (`check_alignable`: ValueError before any launch) and copied over; given as
+        int32 DEVICE tensors they are taken as they are - for ids the device produced itself (the greedy CTC tokens),
+        which are valid by construction."""
+        L.require_gpu(enc_act, "enc_act")
+        B, T, d = enc_act.shape
+        dev, V = enc_act.device, self.odim
+        on_dev = [torch.is_tensor(x) and x.is_cuda for x in (olens, targets, ylens)]
+        if all(on_dev):
+            if any(x.dtype != torch.int32 for x in (olens, targets, ylens)) or targets.dim() != 2:
+                raise ValueError("device-side olens / targets / ylens must be int32, targets (B, Lmax)")
+            olens_d, tg_d, ylens_d = olens.contiguous(), targets.contiguous(), ylens.contiguous()
+            Lmax = int(targets.shape[1])
+        elif any(on_dev):
+            raise ValueError("olens, targets and ylens must be all host data or all device tensors")
+        else:
+            ol = [int(v) for v in (olens.tolist() if torch.is_tensor(olens) else olens)]
+            yl = [int(v) for v in (ylens.tolist() if torch.is_tensor(ylens) else ylens)]
+            rows = targets.tolist() if torch.is_tensor(targets) else [list(r) for r in targets]
+            if len(ol) != B or len(yl) != B or len(rows) != B:
+                raise ValueError(f"olens, targets and ylens must have {B} rows")
+            if any(n < 0 or n > len(r) for n, r in zip(yl, rows)) or any(n < 0 or n > T for n in ol):
+                raise ValueError("a length lies outside its row")
+            rows = [r[:n] for r, n in zip(rows, yl)]
+            self.check_alignable(ol, rows, blank, V)
+            Lmax = max(yl) if yl else 0
+            tg = torch.zeros(B, max(Lmax, 1), dtype=torch.int32)
+            for b, r in enumerate(rows):
+                tg[b, : len(r)] = torch.tensor(r, dtype=torch.int32)
+            olens_d = torch.tensor(ol, dtype=torch.int32).to(dev, non_blocking=True)
+            ylens_d = torch.tensor(yl, dtype=torch.int32).to(dev, non_blocking=True)
+            tg_d = tg[:, :Lmax].contiguous().to(dev, non_blocking=True) if Lmax else tg.to(dev, non_blocking=True)
+        lib, st = L.load(), L.current_stream_ptr()
+        ws_bytes = int(lib.em_ctc_forced_align_workspace_bytes(B, T, Lmax))
+        p = self.packed(dev)
+        lpT = torch.empty(V, B * T, dtype=torch.float32, device=dev)
+        L.check(lib.em_ctc_log_probs_t(self.em_dtype, L.ptr(enc_act), B, T, d, L.ptr(p.weight), L.ptr(p.bias), V,
+                                       L.ptr(lpT), st), "em_ctc_log_probs_t")
+        return self.align_log_probs_t(lpT, B * T, olens_d, tg_d, Lmax, ylens_d, B, T, blank, ws_bytes=ws_bytes)
+
+    @staticmethod
+    def align_log_probs_t(lpT, ldT, olens_d, tg_d, Lmax, ylens_d, B, T, blank, ws_bytes=None):
+        """`em_ctc_forced_align` on given transposed log-posteriors lpT [V][ldT] (device tensors throughout)."""
+        lib, dev = L.load(), lpT.device
+        if ws_bytes is None:
+            ws_bytes = int(lib.em_ctc_forced_align_workspace_bytes(B, T, Lmax))
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
+        Lp = max(Lmax, 1)
+        align = torch.empty(B, T, dtype=torch.int32, device=dev)
+        frame_lp = torch.empty(B, T, dtype=torch.float32, device=dev)
+        tok_start = torch.empty(B, Lp, dtype=torch.int32, device=dev)
+        tok_end = torch.empty(B, Lp, dtype=torch.int32, device=dev)
+        tok_lp = torch.empty(B, Lp, dtype=torch.float32, device=dev)
+        total = torch.empty(B, dtype=torch.float32, device=dev)
+        L.check(lib.em_ctc_forced_align(L.ptr(lpT), ldT, L.ptr(olens_d), L.ptr(tg_d), Lmax, L.ptr(ylens_d), B, T, blank,
+                                        L.ptr(align), L.ptr(frame_lp), L.ptr(tok_start), L.ptr(tok_end), L.ptr(tok_lp),
+                                        L.ptr(total), L.ptr(ws), ws_bytes, L.current_stream_ptr()), "em_ctc_forced_align")
+        return align, frame_lp, tok_start[:, :Lmax], tok_end[:, :Lmax], tok_lp[:, :Lmax], total
+
+    def forced_align(self, hs_pad: torch.Tensor, hlens, ys_pad, ylens, blank_idx: int = 0) -> torch.Tensor:
+        """CTC.forced_align of the reference (espnet2/asr/ctc.py; there a wrapper of
+        torchaudio.functional.forced_align for ONE utterance): hs_pad (B,T,d) encoder output on the device, hlens (B,),
+        ys_pad (B,Lmax) target ids, ylens (B,).  Returns the (B,T) int64 frame labels of the best path, -1 beyond
+        hlens[b].  Any B is taken.  Where two moves tie exactly the smaller one is kept (include/espnet_amd.h;
+        torchaudio's CPU loop takes neither move when both beat staying and are equal): identical on inputs without
+        exact ties."""
+        act = self._to_act(hs_pad)
+        host = [x.cpu() if torch.is_tensor(x) else x for x in (hlens, ys_pad, ylens)]
+        return self.forced_align_device(act, host[0], host[1], host[2], int(blank_idx))[0].to(torch.int64)
 
     @staticmethod
     def _token_outputs(B, T, dev, out):

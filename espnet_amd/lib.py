@@ -372,6 +372,10 @@ _SIGNATURES = {
     "em_conformer_encode_plan": (C.c_int, [C.c_int, C.POINTER(EmConformerWeights), _i32]),
     "em_conformer_encode_plan_for": (C.c_int, [C.c_int, C.POINTER(EmConformerWeights), _i32, _i32, _i32]),
     "em_ctc_prefix_extend": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _i32, _vp, _vp]),
+    "em_ctc_forced_align": (C.c_int, [_vp, _i32, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                      _sz, _vp]),
+    "em_ctc_forced_align_workspace_bytes": (_sz, [_i32, _i32, _i32]),
+    "em_ctc_forced_align_max_tokens": (_i32, []),
     "em_ngram_score": (C.c_int, [C.POINTER(EmNgramModel), _i32, _vp, _vp, _vp, _vp, _i32, _vp, _vp]),
     "em_arpa_count": (C.c_int, [C.c_char_p, _vp, _vp, _vp]),
     "em_arpa_load": (C.c_int, [C.c_char_p, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),

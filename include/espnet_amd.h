@@ -1073,6 +1073,33 @@ int em_ctc_prefix_state(const float* lpT, const int32_t* xlens, const float* r_p
 int em_ctc_prefix_extend(const float* lpT, int32_t T_new, int32_t blank, const float* r_old, int32_t n,
                          int32_t T_old, float* r_new, void* stream);
 
+/* ---- CTC forced alignment (csrc/ctc_align.hip): the Viterbi path of a given transcript through the CTC posteriors,
+ *      CTC.forced_align (espnet2/asr/ctc.py, a wrapper of torchaudio.functional.forced_align), for a ragged batch in
+ *      one launch.  lpT [V][ldT] f32 = em_ctc_log_probs_t's output (ldT >= B*T; utterance b's frames are the columns
+ *      b*T .. b*T + xlens[b] - 1), targets [B][Lmax] (ids in [0, V), none equal to blank; the caller checks that),
+ *      xlens / ylens [B], all on the device.
+ *   Per utterance, T_b = xlens[b], L = ylens[b], lp[t][v] = lpT[v][b*T + t]:
+ *      states s = 0 .. S-1, S = 2L + 1, lab[s] = blank (s even) or y[s >> 1] (s odd);
+ *      alpha[0][0] = lp[0][blank], alpha[0][1] = lp[0][y[0]] (L > 0), every other state -inf;
+ *      alpha[t][s] = max(alpha[t-1][s], alpha[t-1][s-1], alpha[t-1][s-2]) + lp[t][lab[s]], the move by two only for odd
+ *      s >= 3 with lab[s] != lab[s-2]; one f32 add per cell.  Of equal maxima the SMALLEST move is recorded (stay, one,
+ *      two: a larger move wins only if strictly greater); the path ends in state S-1 if alpha[T_b-1][S-1] >
+ *      alpha[T_b-1][S-2], otherwise in S-2 (in state 0 when L == 0).
+ *   Outputs: align [B][T] = lab of the path's state per frame (-1 for t >= T_b); frame_lp [B][T] = lp[t][align[t]] (0
+ *      beyond T_b); total [B] = alpha[T_b-1][end]; tok_start / tok_end [B][Lmax] = first frame and one past the last
+ *      frame whose path state is 2i + 1; tok_lp [B][Lmax] = the f32 sum of frame_lp over that span in frame order,
+ *      divided by the span's length.  Entries i >= L read -1 / -1 / 0.  A row that admits no path (T_b < L + number of
+ *      adjacent equal tokens, or T_b == 0) is not an error of the kernel: total = -inf, align -1, frame_lp 0, spans -1,
+ *      tok_lp 0.
+ *   Transcripts up to Lmax = em_ctc_forced_align_max_tokens() (4 095) tokens; above: EM_ERR_UNSUPPORTED.  ws: em_ctc_forced_align_workspace_bytes(B, T, Lmax)
+ *   bytes of device memory (0 when the back-pointers fit LDS: ws may then be NULL); a smaller one: EM_ERR_WORKSPACE. */
+int em_ctc_forced_align(const float* lpT, int32_t ldT, const int32_t* xlens, const int32_t* targets, int32_t Lmax,
+                        const int32_t* ylens, int32_t B, int32_t T, int32_t blank, int32_t* align, float* frame_lp,
+                        int32_t* tok_start, int32_t* tok_end, float* tok_lp, float* total, void* ws, size_t ws_bytes,
+                        void* stream);
+size_t em_ctc_forced_align_workspace_bytes(int32_t B, int32_t T, int32_t Lmax);
+int32_t em_ctc_forced_align_max_tokens(void);
+
 /* ---- §8(f) rank 3: block-synchronous streaming search, BatchBeamSearchOnline
  *      (espnet2/legacy/nets/batch_beam_search_online.py:155-534).  The host mirrors the reference's
  *      control flow (block loop :296-376, process_one_block :394-493: repetition / local-<eos> breaks,
