@@ -84,6 +84,10 @@ class BeamSearch:
         # (profiles/r06z_beam_eager_ab.txt) - and a capture cannot run while another host thread launches (SearchLanes'
         # threaded lanes: hipErrorStreamCaptureInvalidated).  Off by default; ESPNET_AMD_SEARCH_GRAPH=1 turns it on.
         self.use_hipgraph = False
+        # step_hook: None, or a callable `_search_run` hands its argument block, buffer set and the `init` / `steps` closures
+        # before the search starts (tests/test_gpu_search_steps.py walks the label steps one by one with it).  The search
+        # itself then runs as always, from its own em_search_init.
+        self.step_hook = None
         # (Round 2 also cut the batch into sub-batch searches on concurrent HIP streams: 0.646 -> 0.740 (2 lanes) ->
         # 1.332 ms (4) per label step, profiles/r02_experiments_not_kept.txt - the launches of the lanes do not
         # overlap.  Removed in round 3; the search is one generator over the whole batch.)
@@ -276,6 +280,8 @@ class BatchBeamSearch(BeamSearch):
             L.check(lib.em_search_steps(em_dtype, C.byref(p), dwp, C.byref(bs), i0, i1,
                                         L.current_stream_ptr()), "em_search_steps")
 
+        if self.step_hook is not None:
+            self.step_hook(p=p, bufs=bufs, init=init, steps=steps, maxlens=maxlens, em_dtype=em_dtype)
         init()
         imax, K = max(maxlens), self.step_chunk
         if self.use_hipgraph:
