@@ -2,7 +2,7 @@
 
 Mirrors espnet2/asr/espnet_model.py:45-467 for the attributes and methods the inference path
 touches: `encode(speech, speech_lengths)`, `_extract_feats`, `.frontend/.normalize/.encoder/
-.decoder/.ctc`, `.sos/.eos/.blank_id/.token_list/.vocab_size`.  State-dict keys are the
+.decoder/.ctc/.joint_network`, `.sos/.eos/.blank_id/.token_list/.vocab_size`, `.use_transducer_decoder`.  State-dict keys are the
 reference's (`frontend.logmel.melmat`, `encoder.*`, `decoder.*`, `ctc.ctc_lo.*`).
 
 `encode` keeps the reference signature (padded batch + lengths, any B); `encode_device` is the
@@ -41,8 +41,10 @@ class ESPnetASRModel(torch.nn.Module):
         assert 0.0 <= ctc_weight <= 1.0, ctc_weight
         assert 0.0 <= interctc_weight < 1.0, interctc_weight
         super().__init__()
-        if specaug is not None or preencoder is not None or postencoder is not None or joint_network is not None:
-            raise NotImplementedError("specaug/preencoder/postencoder/transducer are outside the hot path")
+        if specaug is not None or preencoder is not None or postencoder is not None:
+            raise NotImplementedError("specaug/preencoder/postencoder are outside the hot path")
+        if joint_network is not None and len(transducer_multi_blank_durations) > 0:
+            raise NotImplementedError("transducer_multi_blank_durations: multi-blank transducers are outside the hot path")
         token_list = list(token_list)
         # espnet_model.py:76-87
         self.blank_id = token_list.index(sym_blank) if sym_blank in token_list else 0
@@ -59,10 +61,17 @@ class ESPnetASRModel(torch.nn.Module):
         self.preencoder = None
         self.postencoder = None
         self.encoder = encoder
-        self.use_transducer_decoder = False
         self._len_cache = {}
         # espnet_model.py:167-192
-        self.decoder = decoder if ctc_weight < 1.0 else None
+        self.use_transducer_decoder = joint_network is not None
+        if self.use_transducer_decoder:  # (the transducer branch of the reference: blank is label 0, the CTC head optional)
+            self.blank_id = 0
+            self.decoder = decoder
+            self.joint_network = joint_network
+            decoder.set_joint_network(joint_network)
+        else:
+            self.decoder = decoder if ctc_weight < 1.0 else None
+            self.joint_network = None
         self.ctc = None if ctc_weight == 0.0 else ctc
         # the fused encoder path can take the CTC head's arg-max inside its last kernel (csrc/block.hip EM_BLOCK_CTC);
         # a plain attribute, not a submodule: the head's parameters stay under `ctc.` only
@@ -72,14 +81,14 @@ class ESPnetASRModel(torch.nn.Module):
     # ------------------------------------------------------------------ packing
     def set_compute_dtype(self, dtype: str):
         """'float32' (exact-f32 MFMA parity mode) or 'bfloat16' (bf16 MFMA, f32 accumulate)."""
-        for m in (self.encoder, self.ctc, self.decoder):
+        for m in (self.encoder, self.ctc, self.decoder, self.joint_network):
             if m is not None and hasattr(m, "compute_dtype"):
                 m.compute_dtype = dtype
                 m.invalidate()
 
     def load_state_dict(self, state_dict, strict: bool = True, **kw):
         r = super().load_state_dict(state_dict, strict=strict, **kw)
-        for m in (self.frontend, self.encoder, self.ctc, self.decoder):
+        for m in (self.frontend, self.encoder, self.ctc, self.decoder, self.joint_network):
             if m is not None and hasattr(m, "invalidate"):
                 m.invalidate()
         return r

@@ -1,0 +1,89 @@
+"""JointNetwork of a transducer model on the MI355X.
+
+Mirrors espnet2/asr_transducer/joint_network.py (constructor keywords; state-dict keys `lin_enc.{weight,bias}`,
+`lin_dec.weight`, `lin_out.{weight,bias}`): forward(enc, dec) = lin_out(tanh(lin_enc(enc) + lin_dec(dec))).  The
+torch.nn layers are parameter containers only.  On the device the three Linears are apart: `enc_proj` is ONE em_gemm over
+all frames of a batch, `lin_dec` closes the prediction network's step (em_transducer_dec_step) and tanh + `lin_out` +
+log-softmax are `em_transducer_joint_logp`, or the vocabulary-tile launch of the fused greedy walk
+(em_transducer_greedy).  The joint space is zero-padded to the GEMM K step at pack time.
+"""
+import ctypes as C
+
+import torch
+
+from espnet_amd import lib as L
+from espnet_amd.asr.decoder.transducer_decoder import pad64, padk
+from espnet_amd.packing import PackedModule
+
+
+class JointNetwork(PackedModule):
+    def __init__(self, output_size: int, encoder_size: int, decoder_size: int, joint_space_size: int = 256,
+                 joint_activation_type: str = "tanh", compute_dtype: str = "bfloat16", **activation_parameters):
+        super().__init__()
+        if joint_activation_type != "tanh":
+            raise NotImplementedError(f"joint_activation_type={joint_activation_type!r}: only tanh is on the device path")
+        if encoder_size % 64 != 0:  # (lin_enc is one em_gemm on the encoder's own rows, which are not K-padded)
+            raise NotImplementedError(f"encoder_size={encoder_size}: the joint network's lin_enc runs for encoder widths "
+                                      "that are multiples of 64")
+        self.lin_enc = torch.nn.Linear(encoder_size, joint_space_size)
+        self.lin_dec = torch.nn.Linear(decoder_size, joint_space_size, bias=False)
+        self.lin_out = torch.nn.Linear(joint_space_size, output_size)
+        self.output_size, self.encoder_size, self.decoder_size = output_size, encoder_size, decoder_size
+        self.joint_space_size = joint_space_size
+        self.compute_dtype = compute_dtype
+
+    @property
+    def em_dtype(self) -> int:
+        return L.DTYPES[self.compute_dtype]
+
+    @property
+    def jpad(self) -> int:
+        return pad64(self.joint_space_size)
+
+    def _build_pack(self, pk):
+        jp, J = self.jpad, self.joint_space_size
+        w_enc = torch.zeros(jp, self.encoder_size)
+        w_enc[:J] = self.lin_enc.weight.detach().float().cpu()
+        b_enc = torch.zeros(jp)
+        b_enc[:J] = self.lin_enc.bias.detach().float().cpu()
+        pk.lin_enc, pk.enc_b = pk.A(w_enc), pk.F(b_enc)
+        pk.lin_dec = pk.A(padk(self.lin_dec.weight, pad64(self.decoder_size)))
+        pk.lin_out, pk.out_b = pk.A(padk(self.lin_out.weight, jp)), pk.F(self.lin_out.bias)
+
+    @torch.no_grad()
+    def enc_proj_device(self, enc_act: torch.Tensor) -> torch.Tensor:
+        """lin_enc(enc) + bias for all frames at once: enc_act (..., D) in the compute dtype -> (..., jpad) f32."""
+        L.require_gpu(enc_act, "enc_act")
+        if enc_act.dtype != self.act_dtype:
+            enc_act = enc_act.to(self.act_dtype)
+        enc_act = enc_act.contiguous()
+        D = enc_act.shape[-1]
+        if D != self.encoder_size:
+            raise ValueError(f"enc_act has width {D}, the joint network was built for encoder_size={self.encoder_size}")
+        M = enc_act.numel() // D
+        p = self.packed(enc_act.device)
+        out = torch.empty(*enc_act.shape[:-1], self.jpad, dtype=torch.float32, device=enc_act.device)
+        a = L.EmGemmArgs(A=enc_act.data_ptr(), W=p.lin_enc.data_ptr(), C=out.data_ptr(), bias=p.enc_b.data_ptr(), M=M,
+                         N=self.jpad, K=D, lda=D, ldc=self.jpad, scale=1.0)
+        L.check(L.load().em_gemm(self.em_dtype, L.EM_EPI_SCALE_F32, L.EM_A_PLAIN, a, L.current_stream_ptr()),
+                "em_gemm(joint lin_enc)")
+        return out
+
+    @torch.no_grad()
+    def logp_device(self, decoder, enc_proj, dec_proj, enc_idx=None, dec_idx=None) -> torch.Tensor:
+        """`em_transducer_joint_logp`: log_softmax(lin_out(tanh(enc_proj[enc_idx] + dec_proj[dec_idx]))) (n, V) f32 for n
+        pairs of rows (an index vector of None: row r itself)."""
+        dev = enc_proj.device
+        n = int(enc_idx.numel()) if enc_idx is not None else int(dec_idx.numel()) if dec_idx is not None else int(enc_proj.shape[0])
+        w, keep = decoder.weights(dev)
+        z = torch.empty(n, self.jpad, dtype=self.act_dtype, device=dev)
+        logp = torch.empty(n, self.output_size, dtype=torch.float32, device=dev)
+        L.check(L.load().em_transducer_joint_logp(self.em_dtype, C.byref(w), L.ptr(enc_proj), L.ptr(enc_idx), L.ptr(dec_proj),
+                                                  L.ptr(dec_idx), n, L.ptr(z), L.ptr(logp), L.current_stream_ptr()),
+                "em_transducer_joint_logp")
+        return logp
+
+    @torch.no_grad()
+    def forward(self, enc_out: torch.Tensor, dec_out: torch.Tensor) -> torch.Tensor:
+        raise NotImplementedError("JointNetwork.forward on broadcast (B, T, U) lattices is training only; decoding goes "
+                                  "through enc_proj_device / em_transducer_joint_logp")

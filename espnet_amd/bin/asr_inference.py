@@ -9,6 +9,8 @@ bin/s2t_inference_ctc.py:700-749).
 Decoding modes
   * ctc_greedy=True (G1): per-frame argmax + groupby + drop
     blank/sos/eos (asr_inference.py:574-575) — bit-exact integer contract, fully on device.
+  * a transducer model (decoder: transducer): BeamSearchTransducer built from `transducer_conf` and `beam_size` -
+    the fused greedy walk or the default beam search, espnet_amd/asr/transducer/.
   * otherwise: label-synchronous joint CTC/attention beam search (BatchBeamSearch semantics,
     espnet2/legacy/nets/batch_beam_search.py) — see espnet_amd/nets/.
 The log markers "speech length: N" and "best hypo: ..." that utils/calculate_rtf.py parses are kept.
@@ -68,9 +70,8 @@ class Speech2Text:
         for k, v in unsupported.items():
             if v not in (None, False, {}, [], 0.99, 5, -1, ["Linear"], "qint8"):
                 raise NotImplementedError(f"Speech2Text({k}={v!r}) is outside the MI355X hot path")
-        if transducer_conf is not None or streaming:
-            raise NotImplementedError("transducer scorers and streaming=True (use Speech2TextStreaming): "
-                                      "SURVEY.md §8(f) 'next' rows")
+        if streaming:
+            raise NotImplementedError("streaming=True (use Speech2TextStreaming)")
         if not str(device).startswith("cuda"):
             raise RuntimeError("espnet_amd.Speech2Text runs on an MI355X only (device='cuda'); no CPU fallback")
         # the reference's `dtype` is the model dtype; here it selects the MFMA mode
@@ -94,9 +95,21 @@ class Speech2Text:
         else:
             self.tokenizer = build_tokenizer(token_type=token_type, bpemodel=bpemodel)
         self.converter = TokenIDConverter(token_list=token_list)
-        self.beam_search = None
+        self.beam_search = self.beam_search_transducer = None
         self.lm = self.ngram = None
-        if not ctc_greedy:  # (greedy CTC decodes without scorers: an n-gram does not apply there)
+        if asr_model.use_transducer_decoder:  # asr_inference.py: BeamSearchTransducer in place of the joint search
+            if lm_train_config is not None or ngram_file is not None:
+                raise NotImplementedError("lm_train_config / ngram_file with a transducer model: language-model fusion in "
+                                          "the transducer search is outside the MI355X hot path")
+            if not ctc_greedy:
+                from espnet_amd.asr.transducer.beam_search_transducer import BeamSearchTransducer
+
+                self.beam_search_transducer = BeamSearchTransducer(
+                    decoder=asr_model.decoder, joint_network=asr_model.joint_network, beam_size=beam_size,
+                    nbest=nbest, token_list=token_list, **(transducer_conf or {}))
+        elif transducer_conf is not None:
+            raise ValueError("transducer_conf was given, but the model has no joint network (decoder: transducer)")
+        elif not ctc_greedy:  # (greedy CTC decodes without scorers: an n-gram does not apply there)
             from espnet_amd.nets.batch_beam_search import build_beam_search
 
             lm = None
@@ -117,7 +130,8 @@ class Speech2Text:
                 normalize_length=normalize_length, lm=lm, ngram=self.ngram,
                 ngram_weight=ngram_weight if self.ngram is not None else 0.0)
         m = asr_model
-        pack_modules(device, [m.frontend, m.encoder, m.ctc] + ([] if ctc_greedy else [m.decoder, self.lm, self.ngram]))
+        pack_modules(device, [m.frontend, m.encoder, m.ctc] +
+                     ([] if ctc_greedy else [m.decoder, m.joint_network, self.lm, self.ngram]))
 
     # ------------------------------------------------------------------ single utterance (reference API)
     @torch.no_grad()
@@ -138,6 +152,9 @@ class Speech2Text:
         st = self.asr_model.encode_device(speech, [int(n) for n in speech_lengths], isolate=True)
         if self.ctc_greedy:
             return self._finish_greedy(*self.decode_greedy_device(st))
+        if self.beam_search_transducer is not None:
+            hyps = self.beam_search_transducer.search_batch(st.enc_act, st.olens)
+            return [self._format_transducer(h[: self.nbest]) for h in hyps]
         hyps = self.beam_search.search_batch(st.enc_act, st.olens, maxlenratio=self.maxlenratio,
                                              minlenratio=self.minlenratio)
         return [self._format(h[: self.nbest]) for h in hyps]
@@ -148,6 +165,8 @@ class Speech2Text:
         handle's `.result()` waits for this batch alone (an event after its D2H copy), so the caller can
         enqueue the next batch first and format this one while the GPU runs.  The beam search polls the
         device between step chunks and therefore completes inside this call."""
+        if self.beam_search_transducer is not None:  # (the walk reads back once, at its end: completes inside this call)
+            return _Done(self.batch_decode(speech, speech_lengths))
         if not self.ctc_greedy:
             # Round 6: several joint searches in flight (espnet_amd.nets.batch_beam_search.SearchLanes) - this batch is encoded
             # and its search started on a free lane's stream, the handle's `.result()` drives the lanes until it has ended.
@@ -323,6 +342,18 @@ class Speech2Text:
         results = []
         for hyp in nbest_hyps:
             token_int = [x for x in hyp.yseq[1:-1].tolist() if x != 0]
+            token = self.converter.ids2tokens(token_int)
+            text = self.tokenizer.tokens2text(token) if self.tokenizer is not None else None
+            results.append((text, token, token_int, hyp))
+        if results and logger.isEnabledFor(logging.INFO):
+            logger.info("best hypo: " + "".join(results[0][1]) + "\n")
+        return results
+
+    def _format_transducer(self, nbest_hyps):
+        """asr_inference.py, the transducer branch: token_int = yseq[1:] without blanks."""
+        results = []
+        for hyp in nbest_hyps:
+            token_int = [x for x in hyp.yseq[1:] if x != 0]
             token = self.converter.ids2tokens(token_int)
             text = self.tokenizer.tokens2text(token) if self.tokenizer is not None else None
             results.append((text, token, token_int, hyp))

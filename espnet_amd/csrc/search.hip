@@ -25,6 +25,7 @@
 #include <stdlib.h>
 
 #include "em_common.h"
+#include "rnn_cell.h"
 #include "switches.h"
 
 namespace {
@@ -1167,15 +1168,11 @@ __global__ void rnn_cell_kernel(Ctx c, int i_host, int layers, int l, int nhid, 
   for (int ch = threadIdx.x; ch < nhid; ch += blockDim.x) {
     float hh;
     if constexpr (KIND == EM_LM_LSTM) {
-      const float gi = 1.f / (1.f + expf(-g[ch])), gf = 1.f / (1.f + expf(-g[nhid + ch]));
-      const float gg = tanhf(g[2 * nhid + ch]), go = 1.f / (1.f + expf(-g[3 * nhid + ch]));
-      const float cc = gf * (i > 0 ? sprev[ch] : 0.f) + gi * gg;
-      hh = go * tanhf(cc);
+      float cc;
+      hh = em_lstm_cell(g[ch], g[nhid + ch], g[2 * nhid + ch], g[3 * nhid + ch], i > 0 ? sprev[ch] : 0.f, &cc);
       snew[ch] = cc;
     } else if constexpr (KIND == EM_LM_GRU) {
-      const float gr = 1.f / (1.f + expf(-g[ch])), gz = 1.f / (1.f + expf(-g[nhid + ch]));
-      const float nn = tanhf(g[2 * nhid + ch] + gr * g[3 * nhid + ch]);
-      hh = (1.f - gz) * nn + gz * (i > 0 ? sprev[ch] : 0.f);
+      hh = em_gru_cell(g[ch], g[nhid + ch], g[2 * nhid + ch], g[3 * nhid + ch], i > 0 ? sprev[ch] : 0.f);
       snew[ch] = hh;
     } else if constexpr (KIND == EM_LM_RNN_TANH) {
       hh = tanhf(g[ch]);

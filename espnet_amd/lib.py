@@ -239,6 +239,13 @@ class EmLmWeights(C.Structure):
                 ("rnn", C.POINTER(EmRnnLayer))]
 
 
+class EmTransducerWeights(C.Structure):
+    """include/espnet_amd.h EmTransducerWeights (csrc/transducer.hip)."""
+    _fields_ = [(n, C.c_int32) for n in ("kind", "vocab", "nhid", "d", "num_layers", "joint", "jp", "blank")] + \
+               [("embed", C.c_void_p), ("rnn", C.POINTER(EmRnnLayer))] + \
+               [(n, C.c_void_p) for n in ("lin_dec", "lin_out", "out_b")]
+
+
 SEARCH_BUFFERS = ["xlens", "maxlens", "minlens", "ctc_lpT", "tok", "parent", "anc_a", "anc_b",
                   "alive", "run_score", "run_sdec", "run_sctc", "run_slen", "s_prev", "r_a", "r_b",
                   "cand_tok", "cand_full", "cand_psi", "cand_total", "sel_idx", "sel_total",
@@ -379,6 +386,13 @@ _SIGNATURES = {
     "em_ngram_score": (C.c_int, [C.POINTER(EmNgramModel), _i32, _vp, _vp, _vp, _vp, _i32, _vp, _vp]),
     "em_arpa_count": (C.c_int, [C.c_char_p, _vp, _vp, _vp]),
     "em_arpa_load": (C.c_int, [C.c_char_p, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "em_transducer_dec_step": (C.c_int, [C.c_int, C.POINTER(EmTransducerWeights), _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp,
+                                         _vp, _vp]),
+    "em_transducer_joint_logp": (C.c_int, [C.c_int, C.POINTER(EmTransducerWeights), _vp, _vp, _vp, _vp, _i32, _vp, _vp,
+                                           _vp]),
+    "em_transducer_greedy": (C.c_int, [C.c_int, C.POINTER(EmTransducerWeights), _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp,
+                                       _vp, _vp, _vp, _sz, _vp]),
+    "em_transducer_greedy_workspace_bytes": (_sz, [C.c_int, C.POINTER(EmTransducerWeights), _i32, _i32]),
     "em_ctc_greedy": (C.c_int, [C.c_int, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _i32,
                                 _vp, _vp, _vp, _vp, _vp]),
 }

@@ -16,6 +16,7 @@ import torch
 import yaml
 
 from espnet_amd.asr.ctc import CTC
+from espnet_amd.asr.decoder.transducer_decoder import TransducerDecoder
 from espnet_amd.asr.decoder.transformer_decoder import TransformerDecoder
 from espnet_amd.asr.encoder.conformer_encoder import ConformerEncoder
 from espnet_amd.asr.encoder.contextual_block_conformer_encoder import ContextualBlockConformerEncoder
@@ -24,6 +25,7 @@ from espnet_amd.asr.encoder.e_branchformer_encoder import BranchformerEncoder, E
 from espnet_amd.asr.encoder.transformer_encoder import TransformerEncoder
 from espnet_amd.asr.espnet_model import ESPnetASRModel
 from espnet_amd.asr.frontend.default import DefaultFrontend
+from espnet_amd.asr.transducer.joint_network import JointNetwork
 from espnet_amd.layers.global_mvn import GlobalMVN
 from espnet_amd.layers.utterance_mvn import UtteranceMVN
 
@@ -34,7 +36,7 @@ encoder_choices = {"conformer": ConformerEncoder,
                    "contextual_block_transformer": ContextualBlockTransformerEncoder,
                    "e_branchformer": EBranchformerEncoder, "branchformer": BranchformerEncoder,
                    "transformer": TransformerEncoder}
-decoder_choices = {"transformer": TransformerDecoder}
+decoder_choices = {"transformer": TransformerDecoder, "transducer": TransducerDecoder}
 model_choices = {"espnet": ESPnetASRModel}
 
 
@@ -86,8 +88,13 @@ class ASRTask:
                        **(_get(args, "encoder_conf") or {}))
         # 5. decoder
         dname = _get(args, "decoder", "transformer")
-        decoder = None
-        if dname is not None:
+        decoder = joint_network = None
+        if dname == "transducer":  # espnet2/tasks/asr.py build_model: the prediction network and its joint network
+            decoder = TransducerDecoder(vocab_size, embed_pad=0, compute_dtype=compute_dtype,
+                                        **(_get(args, "decoder_conf") or {}))
+            joint_network = JointNetwork(vocab_size, encoder.output_size(), decoder.dunits, compute_dtype=compute_dtype,
+                                         **(_get(args, "joint_net_conf") or {}))
+        elif dname is not None:
             dcls = _choice(decoder_choices, "decoder", dname)
             decoder = dcls(vocab_size=vocab_size, encoder_output_size=encoder.output_size(),
                            compute_dtype=compute_dtype, **(_get(args, "decoder_conf") or {}))
@@ -98,7 +105,7 @@ class ASRTask:
         mcls = _choice(model_choices, "model", _get(args, "model", "espnet"))
         model = mcls(vocab_size=vocab_size, frontend=frontend, specaug=None, normalize=normalize,
                      preencoder=None, encoder=encoder, postencoder=None, decoder=decoder, ctc=ctc,
-                     joint_network=None, token_list=token_list, **(_get(args, "model_conf") or {}))
+                     joint_network=joint_network, token_list=token_list, **(_get(args, "model_conf") or {}))
         return model
 
     @classmethod

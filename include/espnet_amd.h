@@ -1100,6 +1100,56 @@ int em_ctc_forced_align(const float* lpT, int32_t ldT, const int32_t* xlens, con
 size_t em_ctc_forced_align_workspace_bytes(int32_t B, int32_t T, int32_t Lmax);
 int32_t em_ctc_forced_align_max_tokens(void);
 
+/* ---- transducer (RNN-T) decoding (csrc/transducer.hip): the prediction network as a decoder, the joint network and the
+ *      greedy search.  Reference: espnet2/asr/decoder/transducer_decoder.py (TransducerDecoder), espnet2/asr_transducer/
+ *      joint_network.py (JointNetwork), espnet2/asr/transducer/beam_search_transducer.py (BeamSearchTransducer), wired by
+ *      espnet2/tasks/asr.py and espnet2/bin/asr_inference.py.
+ *   Prediction network: y -> embed[y] (row `blank` is the padding row) -> num_layers single-layer LSTM / GRU cells, input =
+ *      hidden = nhid, each from its own caller-held state -> dec_out = the top layer's h.
+ *   Joint network: logits = lin_out(tanh(lin_enc(enc) + lin_dec(dec_out))); lin_enc has a bias, lin_dec none, lin_out one.
+ *      enc_proj = lin_enc(enc) + bias is the CALLER's product (one em_gemm over all B * T frames, EM_EPI_SCALE_F32 with
+ *      scale 1 into [B*T][jp] f32, the rows of lin_enc and its bias zero-padded to jp): it is never recomputed per step.
+ *   Layouts: d = nhid and jp = joint, each padded to a multiple of 64 with zeros; hidden states act [layers][n][d] with the
+ *      f32 master state beside them (LSTM c, GRU h) as in EmSearchBuffers.rnn_hs / rnn_cs; rnn = EmRnnLayer with in_pad = d. */
+typedef struct EmTransducerWeights {
+  int32_t kind;            /* EM_LM_LSTM | EM_LM_GRU */
+  int32_t vocab, nhid, d;  /* d = nhid padded */
+  int32_t num_layers;
+  int32_t joint, jp;       /* joint_space_size and its padded value */
+  int32_t blank;
+  const void* embed;            /* [vocab][d] act: decoder.embed.weight */
+  const struct EmRnnLayer* rnn; /* [num_layers], host array */
+  const void* lin_dec;          /* [joint][d] act: joint_network.lin_dec.weight */
+  const void* lin_out;          /* [vocab][jp] act: joint_network.lin_out.weight */
+  const float* out_b;           /* [vocab]: joint_network.lin_out.bias */
+} EmTransducerWeights;
+/*   One step of the prediction network and lin_dec for n rows (TransducerDecoder.score / batch_score): tok [n] the last
+ *   label of every row, states hs_in act / cs_in f32 [layers][n][d] -> hs_out / cs_out (other buffers than the inputs;
+ *   pad channels are written zero), dec_out [n][nhid] f32 (the top h as the compute dtype holds it; may be NULL),
+ *   dec_proj [n][jp] f32 = lin_dec(dec_out), columns >= joint zero.  mask [n] or NULL: a row with mask[r] == 0 copies its
+ *   state bit for bit and its dec_out / dec_proj rows are not written.                                               */
+int em_transducer_dec_step(int dtype, const EmTransducerWeights* w, const int32_t* tok, const int32_t* mask, int32_t n,
+                           const void* hs_in, const float* cs_in, void* hs_out, float* cs_out, float* dec_out,
+                           float* dec_proj, void* stream);
+/*   logp [n][vocab] f32 = log_softmax(lin_out(tanh(enc_proj[enc_idx[r]] + dec_proj[dec_idx[r]]))) for n pairs of rows
+ *   (an index vector may be NULL: row r itself).  z_ws: [n][jp] act scratch.                                         */
+int em_transducer_joint_logp(int dtype, const EmTransducerWeights* w, const float* enc_proj, const int32_t* enc_idx,
+                             const float* dec_proj, const int32_t* dec_idx, int32_t n, void* z_ws, float* logp,
+                             void* stream);
+/*   BeamSearchTransducer.greedy_search for a ragged batch in lock-step, with no host read-back: per frame t < olens[b]
+ *   the arg-max of the joint log-softmax (lowest id on exact ties); a non-blank label is appended to tokens[b], its
+ *   log-probability added to score[b] and the row's prediction network advances; a blank changes nothing (at most one
+ *   label per frame).  enc_proj [B][T][jp] f32.  Outputs: tokens [B][T] i32 (the first ylens[b] entries are written; the
+ *   leading blank is not stored), ylens [B], score [B] f32; optional trace (frame_tok NULL: none, else all three), written
+ *   at frames t < olens[b] only: frame_tok [B][T] the arg-max, frame_top [B][T] its log-probability, frame_margin [B][T]
+ *   the top-1 minus top-2 logit.  Per frame: one launch over the vocabulary tiles, one decision launch, one launch per
+ *   layer and one for lin_dec + the next frame's tanh.  B <= 64 (EM_ERR_UNSUPPORTED above; the caller splits the batch);
+ *   ws: em_transducer_greedy_workspace_bytes(dtype, w, B, T) bytes of device memory, a smaller one: EM_ERR_WORKSPACE.  */
+int em_transducer_greedy(int dtype, const EmTransducerWeights* w, const float* enc_proj, const int32_t* olens, int32_t B,
+                         int32_t T, int32_t* tokens, int32_t* ylens, float* score, int32_t* frame_tok, float* frame_top,
+                         float* frame_margin, void* ws, size_t ws_bytes, void* stream);
+size_t em_transducer_greedy_workspace_bytes(int dtype, const EmTransducerWeights* w, int32_t B, int32_t T);
+
 /* ---- §8(f) rank 3: block-synchronous streaming search, BatchBeamSearchOnline
  *      (espnet2/legacy/nets/batch_beam_search_online.py:155-534).  The host mirrors the reference's
  *      control flow (block loop :296-376, process_one_block :394-493: repetition / local-<eos> breaks,
