@@ -13,47 +13,27 @@ the reference registry keeps the stock `conformer` entry for those, see INTEGRAT
 The torch.nn layers below are parameter CONTAINERS: their forward() is never called.  The
 arithmetic is csrc/{frontend,gemm,norm,attention,conv,encoder}.hip.
 """
+import contextlib
 import ctypes as C
-import math
 import os
 import threading
 import weakref
-from typing import List, Optional, Tuple
+from typing import List, Optional
 
 import torch
 
 from espnet_amd import lib as L
-from espnet_amd.nets_utils import (SUBSAMPLING_CONVS, SUBSAMPLING_MIN_FRAMES, conv2d_subsampled_lengths,
-                                   conv_out_size)
-from espnet_amd.packing import PackedModule
+from espnet_amd.asr.encoder._subsampled_base import (LN_EPS, LayerNorm, SubsampledEncoderBase,  # noqa: F401
+                                                     _Conv2dSubsampling, _fused_enabled, pack_conv1_frags,
+                                                     pack_conv2_frags, rel_pos_table, resolve_rel_pos,
+                                                     rows_ffn_packable)
+from espnet_amd.nets_utils import SUBSAMPLING_CONVS
 
 _POS_PROJ_LOCK = threading.Lock()
 # the packed weights struct carries the per-call `ctc_ids` pointer: setting it and launching the encoder is one critical
 # section for host threads that encode concurrently; the ids a call produced are kept per THREAD (ADVICE r04)
 _ENC_CALL_LOCK = threading.Lock()
 _TLS = threading.local()
-
-LN_EPS = 1e-12  # transformer/layer_norm.py:23
-
-
-class LayerNorm(torch.nn.LayerNorm):
-    def __init__(self, nout):
-        super().__init__(nout, eps=LN_EPS)
-
-
-class _Conv2dSubsampling(torch.nn.Module):
-    """Parameters of Conv2dSubsampling / Conv2dSubsampling6 / Conv2dSubsampling8
-    (transformer/subsampling.py:386-409, 692-715, 785-808): `conv.{0,2[,4]}`, `out`."""
-
-    def __init__(self, idim, odim, input_layer: str = "conv2d"):
-        super().__init__()
-        mods, cin = [], 1
-        for k, s in SUBSAMPLING_CONVS[input_layer]:
-            mods += [torch.nn.Conv2d(cin, odim, k, s), torch.nn.ReLU()]
-            cin = odim
-        self.conv = torch.nn.Sequential(*mods)
-        self.out = torch.nn.Linear(odim * conv_out_size(idim, input_layer), odim)
-
 
 class _RelPositionMultiHeadedAttention(torch.nn.Module):
     """Parameters of transformer/attention.py:362-389 (+ MultiHeadedAttention :24-75)."""
@@ -106,14 +86,6 @@ class _EncoderLayer(torch.nn.Module):
         self.norm_ff_macaron = LayerNorm(size)
         self.norm_conv = LayerNorm(size)
         self.norm_final = LayerNorm(size)
-
-
-def _fused_enabled(enc) -> bool:
-    """The fused per-block kernels are the default where they apply; `enc.fused = False` or
-    ESPNET_AMD_FUSED=0 keeps the one-operator-per-launch sequence (A/B measurements, bisecting)."""
-    import os
-
-    return bool(getattr(enc, "fused", True)) and os.environ.get("ESPNET_AMD_FUSED", "1") != "0"
 
 
 def pack_k_units(w: torch.Tensor) -> torch.Tensor:
@@ -191,55 +163,7 @@ def pack_rows_glu(w: torch.Tensor) -> torch.Tensor:
     return pack_ffn_rows_w1(w.detach()[glu_chunk_order(w.shape[1])])
 
 
-def pack_conv1_frags(w1: torch.Tensor, b1: torch.Tensor) -> torch.Tensor:
-    """conv.0 weight [256][9] + bias [256] (f32) -> the MFMA operand of the fused conv1 + conv2 kernel (include/espnet_amd.h,
-    em_conv2d_sub12_bf16): per channel 32 bf16 k-slots  hi(w) | hi(w) | lo(w) | hi(b), lo(b), 0, 0, 0  with hi(x) = bf16(x),
-    lo(x) = bf16(x - hi(x)), laid out [chunk][fragment][lg][lr][e] for channel 32 cc + 16 f + lr, k = 8 lg + e."""
-    w1 = w1.detach().to(torch.float32).cpu().reshape(-1, 9)
-    b1 = b1.detach().to(torch.float32).cpu()
-    d = w1.shape[0]
-    assert d % 32 == 0, d
-
-    def hi(x):
-        return x.to(torch.bfloat16).to(torch.float32)
-
-    wh, bh = hi(w1), hi(b1)
-    wl, bl = hi(w1 - wh), hi(b1 - bh)
-    k = torch.zeros(d, 32)
-    k[:, 0:9], k[:, 9:18], k[:, 18:27], k[:, 27], k[:, 28] = wh, wh, wl, bh, bl
-    return k.reshape(d // 32, 2, 16, 4, 8).permute(0, 1, 3, 2, 4).contiguous().reshape(-1)
-
-
-def pack_conv2_frags(w2: torch.Tensor) -> torch.Tensor:
-    """conv.2 weight as [256][9 * 256] with column (kt*3 + kf) * 256 + c_in -> fragment-major
-    [chunk cc][tap][wave w][fragment j][lg][lr][e] = w2[64 w + 16 (lr // 4) + 4 j + lr % 4][tap * 256 + 32 cc + 8 lg + e]:
-    MFMA row lr of a wave's fragment j is an output channel chosen so that a lane's 16 results of a position
-    (4 fragments x 4 rows) are 16 CONSECUTIVE channels - two 16-byte stores instead of four 8-byte ones."""
-    n, k = w2.shape
-    assert n % 256 == 0 and k == 9 * n, (n, k)  # (d = 512: one block of this layout per 256 output channels, 16 chunks each)
-    halves = []
-    for h0 in range(0, n, 256):
-        u = w2.detach()[h0 : h0 + 256].reshape(4, 4, 4, 4, 9, n // 32, 4, 8)  # [w][q = lr // 4][j][r = lr % 4][tap][cc][lg][e]
-        halves.append(u.permute(5, 4, 0, 2, 6, 1, 3, 7).contiguous().reshape(-1))
-    return torch.cat(halves)
-
-
-def rel_pos_table(T: int, d: int) -> torch.Tensor:
-    """RelPositionalEncoding rows for a length-T input (embedding.py:286-332): row k is the
-    sinusoid of relative position T-1-k.  Built on the host with the same fp32 torch ops the
-    reference uses (`extend_pe`), once per distinct T."""
-    pe_positive = torch.zeros(T, d)
-    pe_negative = torch.zeros(T, d)
-    position = torch.arange(0, T, dtype=torch.float32).unsqueeze(1)
-    div_term = torch.exp(torch.arange(0, d, 2, dtype=torch.float32) * -(math.log(10000.0) / d))
-    pe_positive[:, 0::2] = torch.sin(position * div_term)
-    pe_positive[:, 1::2] = torch.cos(position * div_term)
-    pe_negative[:, 0::2] = torch.sin(-1 * position * div_term)
-    pe_negative[:, 1::2] = torch.cos(-1 * position * div_term)
-    return torch.cat([torch.flip(pe_positive, [0]), pe_negative[1:]], dim=0)
-
-
-class ConformerEncoder(PackedModule):
+class ConformerEncoder(SubsampledEncoderBase):
     _WS_FN, _ENC_FN = "em_conformer_workspace_bytes", "em_conformer_encode"  # C-ABI entry points of forward_device
 
     @staticmethod
@@ -255,14 +179,8 @@ class ConformerEncoder(PackedModule):
         if concat_after: bad.append("concat_after=True")
         if positionwise_layer_type != "linear": bad.append(f"positionwise_layer_type={positionwise_layer_type}")
         if not macaron_style: bad.append("macaron_style=False")
-        # conformer_encoder.py:127-136: rel_pos_type "legacy" turns rel_pos / rel_selfattn into their legacy_ forms
-        if rel_pos_type == "legacy":
-            pos_enc_layer_type = "legacy_rel_pos" if pos_enc_layer_type == "rel_pos" else pos_enc_layer_type
-            selfattention_layer_type = ("legacy_rel_selfattn" if selfattention_layer_type == "rel_selfattn"
-                                        else selfattention_layer_type)
-        elif rel_pos_type != "latest":
-            raise ValueError("unknown rel_pos_type: " + rel_pos_type)
-        legacy = pos_enc_layer_type == "legacy_rel_pos" and selfattention_layer_type == "legacy_rel_selfattn"
+        pos_enc_layer_type, selfattention_layer_type, legacy = resolve_rel_pos(rel_pos_type, pos_enc_layer_type,
+                                                                               selfattention_layer_type)
         if not legacy:
             if pos_enc_layer_type != "rel_pos": bad.append(f"pos_enc_layer_type={pos_enc_layer_type}")
             if selfattention_layer_type != "rel_selfattn": bad.append(f"selfattention_layer_type={selfattention_layer_type}")
@@ -275,21 +193,6 @@ class ConformerEncoder(PackedModule):
         if linear_units % 64: bad.append("linear_units % 64 != 0")
         if cnn_module_kernel not in (3, 7, 15, 31): bad.append(f"cnn_module_kernel={cnn_module_kernel}")
         return bad, legacy
-
-    @classmethod
-    def unsupported_options(cls, *args, **kwargs) -> List[str]:
-        """The constructor arguments (positional or keyword, reference defaults applied) that fall outside the fast
-        path, without building anything: what `espnet_amd.integration.espnet2_adapters` consults to hand such a
-        configuration to the stock espnet2 class under the same yaml name."""
-        import inspect
-
-        ba = inspect.signature(cls.__init__).bind(None, *args, **kwargs)
-        ba.apply_defaults()
-        names = inspect.signature(cls._option_check).parameters
-        try:
-            return cls._option_check(**{k: ba.arguments[k] for k in names})[0]
-        except ValueError as e:
-            return [str(e)]
 
     def __init__(self, input_size: int, output_size: int = 256, attention_heads: int = 4,
                  linear_units: int = 2048, num_blocks: int = 6, dropout_rate: float = 0.1,
@@ -305,67 +208,27 @@ class ConformerEncoder(PackedModule):
                  stochastic_depth_rate=0.0, layer_drop_rate: float = 0.0,
                  max_pos_emb_len: int = 5000, qk_norm: bool = False, use_flash_attn: bool = True,
                  compute_dtype: str = "bfloat16"):
-        super().__init__()
-        bad, legacy = self._option_check(
-            input_layer=input_layer, normalize_before=normalize_before, concat_after=concat_after,
-            positionwise_layer_type=positionwise_layer_type, macaron_style=macaron_style, rel_pos_type=rel_pos_type,
-            pos_enc_layer_type=pos_enc_layer_type, selfattention_layer_type=selfattention_layer_type,
-            activation_type=activation_type, use_cnn_module=use_cnn_module, zero_triu=zero_triu,
-            interctc_layer_idx=interctc_layer_idx, interctc_use_conditioning=interctc_use_conditioning,
-            ctc_trim=ctc_trim, qk_norm=qk_norm, output_size=output_size, attention_heads=attention_heads,
-            linear_units=linear_units, cnn_module_kernel=cnn_module_kernel)
+        bad, legacy = self._unsupported(locals())
         if bad:
             raise NotImplementedError("outside the MI355X Conformer fast path: " + ", ".join(bad))
-        self._output_size = output_size
-        self._input_size = input_size
-        self.heads, self.linear_units, self.num_blocks = attention_heads, linear_units, num_blocks
+        super().__init__(input_size, output_size, attention_heads, linear_units, num_blocks, input_layer, compute_dtype,
+                         lambda: _EncoderLayer(output_size, attention_heads, linear_units, cnn_module_kernel),
+                         legacy_relpos=legacy, max_pos_emb_len=max_pos_emb_len)
         self.cnn_module_kernel = cnn_module_kernel
         self.normalize_before = normalize_before
-        self.interctc_layer_idx = list(interctc_layer_idx)
-        self.interctc_use_conditioning = interctc_use_conditioning
-        self.compute_dtype = compute_dtype
-        self.input_layer = input_layer
-        self.legacy_relpos, self.max_pos_emb_len = legacy, max_pos_emb_len
-        self.embed = _Conv2dSubsampling(input_size, output_size, input_layer)
-        self.encoders = torch.nn.ModuleList(
-            [_EncoderLayer(output_size, attention_heads, linear_units, cnn_module_kernel)
-             for _ in range(num_blocks)])
-        self.after_norm = LayerNorm(output_size)
-        self._pos_cache = {}
-        self._ws = None
-        self._olens_cache = {}
         self.last_ctc_ids = None
         object.__setattr__(self, "fused_ctc", None)  # set by the model: a CTC head to fuse (not a submodule of the encoder)
 
-    def output_size(self) -> int:
-        return self._output_size
-
     # ------------------------------------------------------------------ packing (load time)
-    @property
-    def em_dtype(self) -> int:
-        return L.DTYPES[self.compute_dtype]
-
-    def invalidate(self):
-        super().invalidate()
-        self._pos_cache = {}
-
     def _build_pack(self, pk):
         """The reference-layout parameters in the layouts the kernels consume."""
         A, F = pk.A, pk.F
         d, ff, Lb = self._output_size, self.linear_units, self.num_blocks
-        e = self.embed
-        F2 = e.out.in_features // d
         w = L.EmConformerWeights()
         w.d, w.heads, w.ff, w.num_blocks = d, self.heads, ff, Lb
         w.kernel, w.n_mels = self.cnn_module_kernel, self._input_size
-        t = {}
-        t["conv1_w"] = F(e.conv[0].weight.reshape(d, 9))
-        t["conv1_b"] = F(e.conv[0].bias)
-        self._pack_subsampling(w, t, A, F)
-        t["embed_w"] = A(e.out.weight.reshape(d, d, F2).permute(0, 2, 1).reshape(d, F2 * d))
-        t["embed_b"] = F(e.out.bias)
+        t = self._pack_embed(pk, w)
         t["wpos_all"] = A(torch.cat([l.self_attn.linear_pos.weight for l in self.encoders], dim=0))
-        t["after_norm_g"], t["after_norm_b"] = F(self.after_norm.weight), F(self.after_norm.bias)
         pk.fill(w, t)
         layers = (L.EmConformerLayer * Lb)()
         glu_perm = torch.arange(2 * d).reshape(2, d // 16, 16).permute(1, 0, 2).reshape(-1)
@@ -398,7 +261,7 @@ class ConformerEncoder(PackedModule):
         if self._fusable():
             self._pack_fused(pk, layers)
             self._pack_fused_ctc(pk, w)
-        elif self.em_dtype == L.EM_BF16 and d == 512 and ff % 128 == 0 and ff >= 256 and _fused_enabled(self):
+        elif rows_ffn_packable(pk.act, d, ff) and _fused_enabled(self):
             # the 512-wide model: each feed-forward module as one row-block launch (csrc/ffn_rows.hip)
             for i, l in enumerate(self.encoders):
                 lt = dict(ffm_w1p=A(pack_ffn_rows_w1(l.feed_forward_macaron.w_1.weight)),
@@ -421,7 +284,7 @@ class ConformerEncoder(PackedModule):
         """Shapes the row-block fused kernels cover (csrc/block.hip); everything else keeps the per-operator launches."""
         return (self.em_dtype == L.EM_BF16 and self._output_size == 256 and self.heads == 4
                 and self.linear_units <= 1024 and self.cnn_module_kernel == 31
-                and not getattr(self, "legacy_relpos", False))
+                and not self.legacy_relpos)
 
     def _pack_fused(self, pk, layers):
         """Operands of em_conformer_block_fused (include/espnet_amd.h): pointwise_conv1 in 64-row value / gate
@@ -513,23 +376,6 @@ class ConformerEncoder(PackedModule):
         stamp = getattr(pk, "ctc_stamp", None)
         return stamp is None or self.fused_ctc is None or stamp == self._ctc_version(self.fused_ctc)
 
-    def _pack_subsampling(self, w, t, A, F):
-        """conv.2 (and conv.4): [d][k*k*d] with column (kt*k + kf)*d + c_in, the implicit GEMM's K order."""
-        e, d = self.embed, self._output_size
-        layer = getattr(self, "input_layer", "conv2d")
-        w.subsample = {"conv2d": 4, "conv2d6": 6, "conv2d8": 8}[layer]
-        w.legacy_relpos = int(getattr(self, "legacy_relpos", False))
-        k2 = e.conv[2].weight.size(-1)
-        t["conv2_w"] = A(e.conv[2].weight.permute(0, 2, 3, 1).reshape(d, k2 * k2 * d))
-        t["conv2_b"] = F(e.conv[2].bias)
-        if layer == "conv2d" and d in (256, 512) and self.em_dtype == L.EM_BF16:
-            # operands of the fused conv1 + conv2 kernel (csrc/subsample2.hip): the conv1 map is never materialised
-            t["conv1_wf"] = A(pack_conv1_frags(e.conv[0].weight, e.conv[0].bias))
-            t["conv2_wf"] = A(pack_conv2_frags(e.conv[2].weight.permute(0, 2, 3, 1).reshape(d, 9 * d)))
-        if layer == "conv2d8":
-            t["conv3_w"] = A(e.conv[4].weight.permute(0, 2, 3, 1).reshape(d, 9 * d))
-            t["conv3_b"] = F(e.conv[4].bias)
-
     def _pos_projected(self, T: int, device, pk, pos: torch.Tensor) -> torch.Tensor:
         """pos (2T-1 | T, d) x wpos_all^T -> (rows, num_blocks * d) in the activation dtype, through the same em_gemm
         call the encoder entry point makes without EM_ENC_POS_PROJECTED (bit-identical); kept for the last few lengths
@@ -575,128 +421,39 @@ class ConformerEncoder(PackedModule):
                 cache[key] = (out, ev, cur.cuda_stream, pk)  # (the pack is kept alive with its projection)
         return out
 
-    def _pos_emb(self, T: int, device) -> torch.Tensor:
-        """(2T-1, d) rows for a length-T input: a contiguous row slice of one table built for a maximum
-        length, exactly as the reference slices its `pe` buffer (embedding.py:329-332).  Row k of the
-        slice is the sinusoid of relative position T-1-k whatever the table length, so the values are
-        bit-identical to a table built for T; the table grows by doubling (built once per size)."""
-        if getattr(self, "legacy_relpos", False):
-            return self._legacy_pos_emb(T, device)
-        key = (str(device), self.em_dtype)
-        tab = self._pos_cache.get(key)
-        if tab is None or tab[0] < T:
-            tmax = max(512, tab[0] * 2 if tab else 0)
-            while tmax < T:
-                tmax *= 2
-            tab = (tmax, rel_pos_table(tmax, self._output_size).to(self.act_dtype).to(device))
-            self._pos_cache[key] = tab
-        tmax, table = tab
-        return table[tmax - T : tmax + T - 1]
-
-    def _legacy_pos_emb(self, T: int, device) -> torch.Tensor:
-        """(T, d): LegacyRelPositionalEncoding rows (embedding.py:223-262 over PositionalEncoding(reverse=True)
-        :50-82): the reference builds positions max_len-1 .. 0 once and uses the first T rows, so row k is the
-        sinusoid of position max_len-1-k — a prefix of one table (rebuilt longer like `extend_pe` if needed)."""
-        key = ("legacy", str(device), self.em_dtype)
-        tab = self._pos_cache.get(key)
-        if tab is None or tab.size(0) < T:
-            n = max(T, self.max_pos_emb_len)
-            d = self._output_size
-            position = torch.arange(n - 1, -1, -1.0, dtype=torch.float32).unsqueeze(1)
-            div_term = torch.exp(torch.arange(0, d, 2, dtype=torch.float32) * -(math.log(10000.0) / d))
-            pe = torch.zeros(n, d)
-            pe[:, 0::2] = torch.sin(position * div_term)
-            pe[:, 1::2] = torch.cos(position * div_term)
-            tab = pe.to(self.act_dtype).to(device)
-            self._pos_cache[key] = tab
-        return tab[:T]
-
-    # ------------------------------------------------------------------ forward
-    def output_frames(self, T_f: int) -> int:
-        return conv_out_size(T_f, getattr(self, "input_layer", "conv2d"))
-
-    def forward_device(self, feats: torch.Tensor, flens: List[int], flens_dev: torch.Tensor,
-                       mvn_partial: Optional[torch.Tensor] = None, isolate: bool = False):
-        """feats (B,T_f,D) f32 on the GPU.  Returns (enc_out f32 (B,T,d), enc_act (B,T,d) in the
-        compute dtype, olens list, olens_dev i32)."""
-        L.require_gpu(feats, "feats")
-        B, T_f, D = feats.shape
-        # check_short_utt (subsampling.py:31-49) via conformer_encoder.py:360-369; the reference sees one
-        # utterance per call, so in a padded batch every row is held to the same limit
-        layer = getattr(self, "input_layer", "conv2d")
-        lim = SUBSAMPLING_MIN_FRAMES[layer]
-        short = [b for b, n in enumerate(flens) if n < lim] if T_f >= lim else list(range(B))
-        if short:
-            n0 = min(T_f, int(flens[short[0]]))
-            raise L.TooShortUttError(
-                f"has {n0} frames and is too short for subsampling "
-                f"(it needs more than {lim} frames), return empty results", n0, lim, indices=short)
-        dev = feats.device
-        pk = self.packed(dev)
-        w = pk.w
-        lib = L.load()
-        T = self.output_frames(T_f)
-        if isolate:  # every utterance as if it were the whole batch: tmax = its own length
-            olens = [conv2d_subsampled_lengths([n], int(n), layer)[0] for n in flens]
-        else:  # the padded mask is sliced, so padded rows keep up to two frames more (subsampling.py:448)
-            olens = conv2d_subsampled_lengths(flens, T_f, layer)
-        okey = (tuple(olens), dev)
-        olens_dev = self._olens_cache.get(okey)
-        if olens_dev is None:  # kept on the device for repeating batch shapes (see encode_device)
-            olens_dev = torch.tensor(olens, dtype=torch.int32).to(dev, non_blocking=True)
-            if len(self._olens_cache) >= 8:
-                self._olens_cache.pop(next(iter(self._olens_cache)))
-            self._olens_cache[okey] = olens_dev
-        need = getattr(lib, self._WS_FN)(self.em_dtype, C.byref(w), B, T_f)
-        # one workspace per stream: independent utterance batches may be encoded concurrently on
-        # different HIP streams
-        skey = torch.cuda.current_stream().cuda_stream
-        if self._ws is None:
-            self._ws = {}
-        ws = self._ws.get(skey)
-        if ws is None or ws.numel() < need or ws.device != dev:
-            ws = torch.empty(need, dtype=torch.uint8, device=dev)
-            self._ws[skey] = ws
-        d = self._output_size
-        enc_out = torch.empty(B, T, d, dtype=torch.float32, device=dev)
-        enc_act = torch.empty(B, T, d, dtype=self.act_dtype, device=dev)
-        # the fused path also hands back the CTC head's per-frame arg-max (EM_BLOCK_CTC): no logits, no second pass
-        # (whether they WILL be written is the library's decision, asked through em_conformer_encode_plan: the host does
-        # not re-derive the kernel's shape conditions)
-        self.last_ctc_ids = None
-        enc_flags = (L.EM_ENC_ISOLATE_UTTS if isolate else 0) | (0 if _fused_enabled(self) else L.EM_ENC_NO_FUSED)
-        if getattr(self, "fold_c", None) if getattr(self, "fold_c", None) is not None else os.environ.get("ESPNET_AMD_FOLD") == "1":
-            enc_flags |= L.EM_ENC_FOLD_C  # block<C|D|...>: two launches per block (opt-in: measured no faster, DESIGN.md)
-        if getattr(self, "split_att", None) if getattr(self, "split_att", None) is not None else os.environ.get("ESPNET_AMD_SPLIT_ATT") == "1":
-            enc_flags |= L.EM_ENC_SPLIT_ATT  # attention and block<C> as two launches (rounds 2-5) instead of block<ATT|C>: A/B switch
-        # batches the caller keeps in flight on other HIP streams (bench.py's StepPipeline, the decode CLI's lanes set the
-        # attribute): the library takes the 512-wide models' row-block launches from a smaller share of the chip then
-        enc_flags |= L.EM_ENC_IN_FLIGHT(max(1, min(15, int(getattr(self, "batches_in_flight", 1) or 1))))
+    # ------------------------------------------------------------------ forward (the hooks of SubsampledEncoderBase)
+    def _call_operands(self, T: int, dev, pk):
+        flags = 0
+        if self.fold_c if getattr(self, "fold_c", None) is not None else os.environ.get("ESPNET_AMD_FOLD") == "1":
+            flags |= L.EM_ENC_FOLD_C  # block<C|D|...>: two launches per block (opt-in: measured no faster)
+        if self.split_att if getattr(self, "split_att", None) is not None else os.environ.get("ESPNET_AMD_SPLIT_ATT") == "1":
+            flags |= L.EM_ENC_SPLIT_ATT  # attention and block<C> as two launches (rounds 2-5) instead of block<ATT|C>: A/B switch
         pos = self._pos_emb(T, dev)
-        if self._ENC_FN == "em_conformer_encode" and getattr(w, "wpos_all", None):
+        if pk.w.wpos_all:
             # linear_pos of every block depends on T and the weights only: projected once per length, handed over ready
             pos = self._pos_projected(T, dev, pk, pos)
-            enc_flags |= L.EM_ENC_POS_PROJECTED | (L.EM_ENC_POS_PACKED if getattr(pos, "_em_packed", False) else 0)
+            flags |= L.EM_ENC_POS_PROJECTED | (L.EM_ENC_POS_PACKED if getattr(pos, "_em_packed", False) else 0)
+        return pos, flags
+
+    @contextlib.contextmanager
+    def _ctc_ids_plan(self, w, enc_flags, B, T, T_f, dev):
+        """The fused path also hands back the CTC head's per-frame arg-max (EM_BLOCK_CTC): no logits, no second pass.
+        Whether they WILL be written is the library's decision, asked through em_conformer_encode_plan_for: the host does
+        not re-derive the kernel's shape conditions."""
+        self.last_ctc_ids = None
         with _ENC_CALL_LOCK:
-            if hasattr(w, "ctc_ids"):
-                w.ctc_ids = None
-                if self._ENC_FN == "em_conformer_encode" and getattr(w, "ctc_units", 0) > 0:
-                    ids = torch.empty(B, T, dtype=torch.int32, device=dev)
-                    w.ctc_ids = ids.data_ptr()
-                    plan = lib.em_conformer_encode_plan_for(self.em_dtype, C.byref(w), enc_flags, B, T_f)
-                    if plan < 0:
-                        L.check(plan, "em_conformer_encode_plan")
-                    if plan & L.EM_ENC_PLAN_CTC_IDS:
-                        self.last_ctc_ids = ids
-                    else:
-                        w.ctc_ids = None
-            rc = getattr(lib, self._ENC_FN)(
-                self.em_dtype, C.byref(w), L.ptr(feats), L.ptr(mvn_partial), L.ptr(flens_dev),
-                L.ptr(olens_dev), B, T_f, L.ptr(pos), L.ptr(ws),
-                ws.numel(), L.ptr(enc_out), L.ptr(enc_act),
-                enc_flags, L.current_stream_ptr())
-        L.check(rc, self._ENC_FN)
-        return enc_out, enc_act, olens, olens_dev
+            w.ctc_ids = None
+            if w.ctc_units > 0:
+                ids = torch.empty(B, T, dtype=torch.int32, device=dev)
+                w.ctc_ids = ids.data_ptr()
+                plan = L.load().em_conformer_encode_plan_for(self.em_dtype, C.byref(w), enc_flags, B, T_f)
+                if plan < 0:
+                    L.check(plan, "em_conformer_encode_plan")
+                if plan & L.EM_ENC_PLAN_CTC_IDS:
+                    self.last_ctc_ids = ids
+                else:
+                    w.ctc_ids = None
+            yield
 
     @property
     def last_ctc_ids(self):
@@ -710,11 +467,3 @@ class ConformerEncoder(PackedModule):
         if not hasattr(_TLS, "ids"):
             _TLS.ids = weakref.WeakKeyDictionary()  # (keyed by the encoder itself: an entry dies with it, ids are never reused)
         _TLS.ids[self] = v
-
-    def forward(self, xs_pad: torch.Tensor, ilens: torch.Tensor, prev_states: torch.Tensor = None
-                ) -> Tuple[torch.Tensor, torch.Tensor, Optional[torch.Tensor]]:
-        flens = [int(v) for v in ilens.tolist()]
-        flens_dev = torch.tensor(flens, dtype=torch.int32).to(xs_pad.device, non_blocking=True)
-        enc_out, _, olens, _ = self.forward_device(xs_pad.to(torch.float32).contiguous(), flens,
-                                                   flens_dev, None)
-        return enc_out, torch.tensor(olens, dtype=torch.long, device=xs_pad.device), None

@@ -20,10 +20,11 @@ from typing import List, Optional
 import torch
 
 from espnet_amd import lib as L
-from espnet_amd.asr.encoder.conformer_encoder import (ConformerEncoder, LayerNorm, _Conv2dSubsampling,
-                                                      _PositionwiseFeedForward,
-                                                      _RelPositionMultiHeadedAttention, pack_ffn_rows_w1,
-                                                      pack_ffn_rows_w2)
+from espnet_amd.asr.encoder._subsampled_base import (LayerNorm, SubsampledEncoderBase, resolve_rel_pos,
+                                                     rows_ffn_packable)
+from espnet_amd.asr.encoder.conformer_encoder import (_PositionwiseFeedForward, _RelPositionMultiHeadedAttention,
+                                                      pack_ffn_rows_w1, pack_ffn_rows_w2)
+from espnet_amd.nets_utils import SUBSAMPLING_CONVS
 
 
 class _CSGU(torch.nn.Module):
@@ -74,32 +75,23 @@ class _EBranchformerEncoderLayer(torch.nn.Module):
         self.merge_proj = torch.nn.Linear(2 * size if merge_method == "concat" else size, size)
 
 
-class EBranchformerEncoder(ConformerEncoder):
+class EBranchformerEncoder(SubsampledEncoderBase):
     merge_method, cgmlp_weight = "concat", None
     _WS_FN, _ENC_FN = "em_ebranchformer_workspace_bytes", "em_ebranchformer_encode"
 
-    def __init__(self, input_size: int, output_size: int = 256, attention_heads: int = 4,
-                 attention_layer_type: str = "rel_selfattn", pos_enc_layer_type: str = "rel_pos",
-                 rel_pos_type: str = "latest", cgmlp_linear_units: int = 2048, cgmlp_conv_kernel: int = 31,
-                 use_linear_after_conv: bool = False, gate_activation: str = "identity", num_blocks: int = 12,
-                 dropout_rate: float = 0.1, positional_dropout_rate: float = 0.1,
-                 attention_dropout_rate: float = 0.0, input_layer: Optional[str] = "conv2d",
-                 zero_triu: bool = False, padding_idx: int = -1, layer_drop_rate: float = 0.0,
-                 max_pos_emb_len: int = 5000, use_ffn: bool = False, macaron_ffn: bool = False,
-                 ffn_activation_type: str = "swish", linear_units: int = 2048,
-                 positionwise_layer_type: str = "linear", merge_conv_kernel: int = 3, interctc_layer_idx=None,
-                 interctc_use_conditioning: bool = False, qk_norm: bool = False, use_flash_attn: bool = True,
-                 gradient_checkpoint_layers: List[int] = [], compute_dtype: str = "bfloat16"):
-        torch.nn.Module.__init__(self)
+    @staticmethod
+    def _option_check(*, input_layer, rel_pos_type, pos_enc_layer_type, attention_layer_type, use_linear_after_conv,
+                      gate_activation, zero_triu, qk_norm, output_size, attention_heads, cgmlp_linear_units,
+                      cgmlp_conv_kernel, use_ffn=True, macaron_ffn=True, ffn_activation_type="swish",
+                      positionwise_layer_type="linear", interctc_layer_idx=None, interctc_use_conditioning=False,
+                      linear_units=0, merge_conv_kernel=3):
+        """Options of espnet2/asr/encoder/e_branchformer_encoder.py:186-225 that the MI355X kernels do not cover ->
+        (list of "name=value" strings, legacy rel-pos flag).  The options from use_ffn on are the E-Branchformer's
+        alone: BranchformerEncoder._option_check leaves them at these defaults, which pass."""
         bad = []
-        if input_layer not in ("conv2d", "conv2d6", "conv2d8"): bad.append(f"input_layer={input_layer}")
-        # e_branchformer_encoder.py:226-235 / branchformer_encoder.py:330-339: "legacy" maps to the legacy_ classes
-        if rel_pos_type == "legacy":
-            pos_enc_layer_type = "legacy_rel_pos" if pos_enc_layer_type == "rel_pos" else pos_enc_layer_type
-            attention_layer_type = "legacy_rel_selfattn" if attention_layer_type == "rel_selfattn" else attention_layer_type
-        elif rel_pos_type != "latest":
-            raise ValueError("unknown rel_pos_type: " + rel_pos_type)
-        legacy = pos_enc_layer_type == "legacy_rel_pos" and attention_layer_type == "legacy_rel_selfattn"
+        if input_layer not in SUBSAMPLING_CONVS: bad.append(f"input_layer={input_layer}")
+        pos_enc_layer_type, attention_layer_type, legacy = resolve_rel_pos(rel_pos_type, pos_enc_layer_type,
+                                                                           attention_layer_type)
         if not legacy:
             if attention_layer_type != "rel_selfattn": bad.append(f"attention_layer_type={attention_layer_type}")
             if pos_enc_layer_type != "rel_pos": bad.append(f"pos_enc_layer_type={pos_enc_layer_type}")
@@ -116,30 +108,35 @@ class EBranchformerEncoder(ConformerEncoder):
         if cgmlp_linear_units % 128: bad.append("cgmlp_linear_units % 128 != 0")
         if cgmlp_conv_kernel not in (3, 7, 15, 31): bad.append(f"cgmlp_conv_kernel={cgmlp_conv_kernel}")
         if merge_conv_kernel not in (3, 7, 15, 31): bad.append(f"merge_conv_kernel={merge_conv_kernel}")
+        return bad, legacy
+
+    def __init__(self, input_size: int, output_size: int = 256, attention_heads: int = 4,
+                 attention_layer_type: str = "rel_selfattn", pos_enc_layer_type: str = "rel_pos",
+                 rel_pos_type: str = "latest", cgmlp_linear_units: int = 2048, cgmlp_conv_kernel: int = 31,
+                 use_linear_after_conv: bool = False, gate_activation: str = "identity", num_blocks: int = 12,
+                 dropout_rate: float = 0.1, positional_dropout_rate: float = 0.1,
+                 attention_dropout_rate: float = 0.0, input_layer: Optional[str] = "conv2d",
+                 zero_triu: bool = False, padding_idx: int = -1, layer_drop_rate: float = 0.0,
+                 max_pos_emb_len: int = 5000, use_ffn: bool = False, macaron_ffn: bool = False,
+                 ffn_activation_type: str = "swish", linear_units: int = 2048,
+                 positionwise_layer_type: str = "linear", merge_conv_kernel: int = 3, interctc_layer_idx=None,
+                 interctc_use_conditioning: bool = False, qk_norm: bool = False, use_flash_attn: bool = True,
+                 gradient_checkpoint_layers: List[int] = [], compute_dtype: str = "bfloat16"):
+        bad, legacy = self._unsupported(locals())
         if bad:
             raise NotImplementedError("outside the MI355X E-Branchformer fast path: " + ", ".join(bad))
-        self._output_size, self._input_size = output_size, input_size
-        self.heads, self.linear_units, self.num_blocks = attention_heads, linear_units, num_blocks
+        super().__init__(input_size, output_size, attention_heads, linear_units, num_blocks, input_layer, compute_dtype,
+                         lambda: _EBranchformerEncoderLayer(output_size, attention_heads, linear_units, cgmlp_linear_units,
+                                                            cgmlp_conv_kernel, merge_conv_kernel),
+                         legacy_relpos=legacy, max_pos_emb_len=max_pos_emb_len)
         self.cgmlp_linear_units, self.cgmlp_conv_kernel = cgmlp_linear_units, cgmlp_conv_kernel
         self.merge_conv_kernel = merge_conv_kernel
-        self.interctc_layer_idx, self.interctc_use_conditioning = [], False
-        self.compute_dtype = compute_dtype
-        self.input_layer = input_layer
-        self.legacy_relpos, self.max_pos_emb_len = legacy, max_pos_emb_len
-        self.embed = _Conv2dSubsampling(input_size, output_size, input_layer)
-        self.encoders = torch.nn.ModuleList(
-            [_EBranchformerEncoderLayer(output_size, attention_heads, linear_units, cgmlp_linear_units,
-                                        cgmlp_conv_kernel, merge_conv_kernel) for _ in range(num_blocks)])
-        self.after_norm = LayerNorm(output_size)
-        self._pos_cache, self._ws, self._olens_cache = {}, None, {}
 
     def _build_pack(self, pk):
         A, F, act = pk.A, pk.F, pk.act
         d, ff, Lb, cg = self._output_size, self.linear_units, self.num_blocks, self.cgmlp_linear_units
         if (cg // 2) % (64 if self.em_dtype == L.EM_BF16 else 32):
             raise NotImplementedError("cgmlp_linear_units / 2 must be a multiple of the GEMM K step")
-        e = self.embed
-        F2 = e.out.in_features // d
         w = L.EmEBranchformerWeights()
         w.d, w.heads, w.cg, w.num_blocks = d, self.heads, cg, Lb
         w.cg_kernel, w.merge_kernel, w.n_mels = self.cgmlp_conv_kernel, self.merge_conv_kernel or 0, self._input_size
@@ -147,12 +144,8 @@ class EBranchformerEncoder(ConformerEncoder):
         w.ff = ff or 0
         w.use_ffn, w.merge_conv = int(has_ffn), int(has_mconv)
         w.merge_method = L.EM_MERGE_LEARNED_AVE if self.merge_method == "learned_ave" else L.EM_MERGE_CONCAT
-        t = dict(conv1_w=F(e.conv[0].weight.reshape(d, 9)), conv1_b=F(e.conv[0].bias),
-                 embed_w=A(e.out.weight.reshape(d, d, F2).permute(0, 2, 1).reshape(d, F2 * d)),
-                 embed_b=F(e.out.bias),
-                 wpos_all=A(torch.cat([l.attn.linear_pos.weight for l in self.encoders], dim=0)),
-                 after_norm_g=F(self.after_norm.weight), after_norm_b=F(self.after_norm.bias))
-        self._pack_subsampling(w, t, A, F)
+        t = self._pack_embed(pk, w)
+        t["wpos_all"] = A(torch.cat([l.attn.linear_pos.weight for l in self.encoders], dim=0))
         pk.fill(w, t)
         layers = (L.EmEBranchformerLayer * Lb)()
         for i, l in enumerate(self.encoders):
@@ -190,7 +183,7 @@ class EBranchformerEncoder(ConformerEncoder):
                     ffm_w2=A(l.feed_forward_macaron.w_2.weight), ffm_b2=F(l.feed_forward_macaron.w_2.bias),
                     ff_w1=A(l.feed_forward.w_1.weight), ff_b1=F(l.feed_forward.w_1.bias),
                     ff_w2=A(l.feed_forward.w_2.weight), ff_b2=F(l.feed_forward.w_2.bias))
-            if has_ffn and d == 512 and ff % 128 == 0 and ff >= 256 and act == torch.bfloat16:
+            if rows_ffn_packable(act, d, ff):
                 # operand streams of the row-block feed-forward launches (csrc/ffn_rows.hip), as the 512-wide Conformer's
                 lt.update(ffm_w1p=A(pack_ffn_rows_w1(l.feed_forward_macaron.w_1.weight)),
                           ffm_w2p=A(pack_ffn_rows_w2(l.feed_forward_macaron.w_2.weight)),
@@ -214,6 +207,38 @@ class BranchformerEncoder(EBranchformerEncoder):
     a float or one per block — folded into the packed merge_proj weight); learned_ave (the pooled per-utterance
     branch weights are computed on the device, `em_branch_learned_ave`; attn_branch_drop_rate is training-only)."""
 
+    @staticmethod
+    def _option_check(*, use_attn, use_cgmlp, merge_method, cgmlp_weight, num_blocks, input_layer, rel_pos_type,
+                      pos_enc_layer_type, attention_layer_type, use_linear_after_conv, gate_activation, zero_triu, qk_norm,
+                      output_size, attention_heads, cgmlp_linear_units, cgmlp_conv_kernel):
+        """Options of espnet2/asr/encoder/branchformer_encoder.py:293-340 outside the fast path: the Branchformer's own,
+        then those it shares with the E-Branchformer."""
+        bad = []
+        if not (use_attn and use_cgmlp): bad.append("use_attn and use_cgmlp must both be True")
+        if merge_method not in ("concat", "learned_ave", "fixed_ave"):
+            raise ValueError(f"unknown merge method: {merge_method}")  # branchformer_encoder.py:133
+        cgmlp_weight = BranchformerEncoder._block_weights(cgmlp_weight, num_blocks)
+        if merge_method == "fixed_ave":
+            assert all(0.0 <= c <= 1.0 for c in cgmlp_weight), "cgmlp weight should be between 0.0 and 1.0"
+            if any(c in (0.0, 1.0) for c in cgmlp_weight):  # :120-127 drops one branch and its parameters
+                bad.append("fixed_ave with cgmlp_weight 0.0 / 1.0 (single-branch layers)")
+        shared, legacy = EBranchformerEncoder._option_check(
+            input_layer=input_layer, rel_pos_type=rel_pos_type, pos_enc_layer_type=pos_enc_layer_type,
+            attention_layer_type=attention_layer_type, use_linear_after_conv=use_linear_after_conv,
+            gate_activation=gate_activation, zero_triu=zero_triu, qk_norm=qk_norm, output_size=output_size,
+            attention_heads=attention_heads, cgmlp_linear_units=cgmlp_linear_units, cgmlp_conv_kernel=cgmlp_conv_kernel)
+        return bad + shared, legacy
+
+    @staticmethod
+    def _block_weights(cgmlp_weight, num_blocks) -> List[float]:
+        """cgmlp_weight as one float per block (branchformer_encoder.py:490-496)."""
+        if isinstance(cgmlp_weight, (int, float)):
+            cgmlp_weight = [float(cgmlp_weight)] * num_blocks
+        if len(cgmlp_weight) != num_blocks:
+            raise ValueError(f"Length of cgmlp_weight ({len(cgmlp_weight)}) should be equal to "
+                             f"num_blocks ({num_blocks})")
+        return [float(c) for c in cgmlp_weight]
+
     def __init__(self, input_size: int, output_size: int = 256, use_attn: bool = True, attention_heads: int = 4,
                  attention_layer_type: str = "rel_selfattn", pos_enc_layer_type: str = "rel_pos",
                  rel_pos_type: str = "latest", use_cgmlp: bool = True, cgmlp_linear_units: int = 2048,
@@ -224,52 +249,15 @@ class BranchformerEncoder(EBranchformerEncoder):
                  input_layer: Optional[str] = "conv2d", zero_triu: bool = False, padding_idx: int = -1,
                  stochastic_depth_rate=0.0, qk_norm: bool = False, use_flash_attn: bool = True,
                  compute_dtype: str = "bfloat16"):
-        torch.nn.Module.__init__(self)
-        bad = []
-        if not (use_attn and use_cgmlp): bad.append("use_attn and use_cgmlp must both be True")
-        if merge_method not in ("concat", "learned_ave", "fixed_ave"):
-            raise ValueError(f"unknown merge method: {merge_method}")  # branchformer_encoder.py:133
-        if isinstance(cgmlp_weight, (int, float)):  # :490-496
-            cgmlp_weight = [float(cgmlp_weight)] * num_blocks
-        if len(cgmlp_weight) != num_blocks:
-            raise ValueError(f"Length of cgmlp_weight ({len(cgmlp_weight)}) should be equal to "
-                             f"num_blocks ({num_blocks})")
-        if merge_method == "fixed_ave":
-            assert all(0.0 <= c <= 1.0 for c in cgmlp_weight), "cgmlp weight should be between 0.0 and 1.0"
-            if any(c in (0.0, 1.0) for c in cgmlp_weight):  # :120-127 drops one branch and its parameters
-                bad.append("fixed_ave with cgmlp_weight 0.0 / 1.0 (single-branch layers)")
-        if input_layer not in ("conv2d", "conv2d6", "conv2d8"): bad.append(f"input_layer={input_layer}")
-        # e_branchformer_encoder.py:226-235 / branchformer_encoder.py:330-339: "legacy" maps to the legacy_ classes
-        if rel_pos_type == "legacy":
-            pos_enc_layer_type = "legacy_rel_pos" if pos_enc_layer_type == "rel_pos" else pos_enc_layer_type
-            attention_layer_type = "legacy_rel_selfattn" if attention_layer_type == "rel_selfattn" else attention_layer_type
-        elif rel_pos_type != "latest":
-            raise ValueError("unknown rel_pos_type: " + rel_pos_type)
-        legacy = pos_enc_layer_type == "legacy_rel_pos" and attention_layer_type == "legacy_rel_selfattn"
-        if not legacy:
-            if attention_layer_type != "rel_selfattn": bad.append(f"attention_layer_type={attention_layer_type}")
-            if pos_enc_layer_type != "rel_pos": bad.append(f"pos_enc_layer_type={pos_enc_layer_type}")
-        if use_linear_after_conv: bad.append("use_linear_after_conv=True")
-        if gate_activation != "identity": bad.append(f"gate_activation={gate_activation}")
-        if zero_triu: bad.append("zero_triu=True")
-        if qk_norm: bad.append("qk_norm=True")
-        if output_size % 64 or output_size // attention_heads != 64: bad.append("d_k != 64")
-        if cgmlp_linear_units % 128: bad.append("cgmlp_linear_units % 128 != 0")
-        if cgmlp_conv_kernel not in (3, 7, 15, 31): bad.append(f"cgmlp_conv_kernel={cgmlp_conv_kernel}")
+        bad, legacy = self._unsupported(locals())
         if bad:
             raise NotImplementedError("outside the MI355X Branchformer fast path: " + ", ".join(bad))
-        self._output_size, self._input_size = output_size, input_size
-        self.heads, self.linear_units, self.num_blocks = attention_heads, None, num_blocks
+        # (BranchformerEncoder has no max_pos_emb_len argument: the pos_enc_class default, 5000)
+        SubsampledEncoderBase.__init__(
+            self, input_size, output_size, attention_heads, None, num_blocks, input_layer, compute_dtype,
+            lambda: _EBranchformerEncoderLayer(output_size, attention_heads, None, cgmlp_linear_units, cgmlp_conv_kernel,
+                                               None, merge_method),
+            legacy_relpos=legacy)
         self.cgmlp_linear_units, self.cgmlp_conv_kernel = cgmlp_linear_units, cgmlp_conv_kernel
         self.merge_conv_kernel = None
-        self.merge_method, self.cgmlp_weight = merge_method, [float(c) for c in cgmlp_weight]
-        self.interctc_layer_idx, self.interctc_use_conditioning = [], False
-        self.compute_dtype = compute_dtype
-        self.input_layer = input_layer
-        self.legacy_relpos, self.max_pos_emb_len = legacy, 5000  # BranchformerEncoder has no max_pos_emb_len argument (pos_enc_class default)
-        self.embed = _Conv2dSubsampling(input_size, output_size, input_layer)
-        self.encoders = torch.nn.ModuleList(
-            [_EBranchformerEncoderLayer(output_size, attention_heads, None, cgmlp_linear_units, cgmlp_conv_kernel,
-                                        None, merge_method) for _ in range(num_blocks)])
-        self.after_norm = LayerNorm(output_size)
-        self._pos_cache, self._ws, self._olens_cache = {}, None, {}
+        self.merge_method, self.cgmlp_weight = merge_method, self._block_weights(cgmlp_weight, num_blocks)

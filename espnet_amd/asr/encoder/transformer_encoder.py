@@ -13,15 +13,14 @@ LayerNorms are the Conformer's kernels; the attention is csrc/abs_attn.hip.  The
 CONTAINERS: their forward() is never called.
 """
 import ctypes as C
-import inspect
 from typing import List, Optional
 
 import torch
 
 from espnet_amd import lib as L
 from espnet_amd.asr.decoder.transformer_decoder import abs_pos_table
-from espnet_amd.asr.encoder.conformer_encoder import (ConformerEncoder, LayerNorm, _Conv2dSubsampling,
-                                                      _PositionwiseFeedForward, pack_ffn_rows_w1, pack_ffn_rows_w2)
+from espnet_amd.asr.encoder._subsampled_base import LayerNorm, SubsampledEncoderBase, rows_ffn_packable
+from espnet_amd.asr.encoder.conformer_encoder import _PositionwiseFeedForward, pack_ffn_rows_w1, pack_ffn_rows_w2
 from espnet_amd.nets_utils import SUBSAMPLING_CONVS
 
 
@@ -48,7 +47,7 @@ class _EncoderLayer(torch.nn.Module):
         self.norm2 = LayerNorm(size)
 
 
-class TransformerEncoder(ConformerEncoder):
+class TransformerEncoder(SubsampledEncoderBase):
     _WS_FN, _ENC_FN = "em_transformer_workspace_bytes", "em_transformer_encode"
 
     @staticmethod
@@ -70,16 +69,6 @@ class TransformerEncoder(ConformerEncoder):
         if linear_units % 64: bad.append("linear_units % 64 != 0")
         return bad, None
 
-    @classmethod
-    def unsupported_options(cls, *args, **kwargs) -> List[str]:
-        """The constructor arguments outside the fast path (reference defaults applied; keywords the reference class does
-        not take included), without building anything."""
-        ba = inspect.signature(cls.__init__).bind(None, *args, **kwargs)
-        ba.apply_defaults()
-        foreign = [f"{k}={v!r} (not a TransformerEncoder keyword)" for k, v in ba.arguments.get("unsupported", {}).items()]
-        names = inspect.signature(cls._option_check).parameters
-        return foreign + cls._option_check(**{k: ba.arguments[k] for k in names})[0]
-
     def __init__(self, input_size: int, output_size: int = 256, attention_heads: int = 4, linear_units: int = 2048,
                  num_blocks: int = 6, dropout_rate: float = 0.1, positional_dropout_rate: float = 0.1,
                  attention_dropout_rate: float = 0.0, input_layer: Optional[str] = "conv2d", pos_enc_class=None,
@@ -87,44 +76,23 @@ class TransformerEncoder(ConformerEncoder):
                  positionwise_conv_kernel_size: int = 1, padding_idx: int = -1, interctc_layer_idx: List[int] = [],
                  interctc_use_conditioning: bool = False, layer_drop_rate: float = 0.0, qk_norm: bool = False,
                  use_flash_attn: bool = True, compute_dtype: str = "bfloat16", **unsupported):
-        torch.nn.Module.__init__(self)
         # (the reference takes no other keyword: a Conformer / E-Branchformer option in a transformer encoder_conf is a
         # configuration this class cannot reproduce, reported like Speech2Text's **unsupported)
-        bad = [f"{k}={v!r} (not a TransformerEncoder keyword)" for k, v in unsupported.items()]
-        bad += self._option_check(
-            input_layer=input_layer, pos_enc_class=pos_enc_class, normalize_before=normalize_before,
-            concat_after=concat_after, positionwise_layer_type=positionwise_layer_type,
-            interctc_layer_idx=interctc_layer_idx, interctc_use_conditioning=interctc_use_conditioning, qk_norm=qk_norm,
-            output_size=output_size, attention_heads=attention_heads, linear_units=linear_units)[0]
+        bad, _ = self._unsupported(locals())
         if bad:
             raise NotImplementedError("outside the MI355X Transformer-encoder fast path: " + ", ".join(bad))
-        self._output_size, self._input_size = output_size, input_size
-        self.heads, self.linear_units, self.num_blocks = attention_heads, linear_units, num_blocks
+        super().__init__(input_size, output_size, attention_heads, linear_units, num_blocks, input_layer, compute_dtype,
+                         lambda: _EncoderLayer(output_size, attention_heads, linear_units))
         self.normalize_before = normalize_before
-        self.interctc_layer_idx, self.interctc_use_conditioning = [], False
-        self.compute_dtype = compute_dtype
-        self.input_layer = input_layer
-        self.legacy_relpos = False
-        self.embed = _Conv2dSubsampling(input_size, output_size, input_layer)
-        self.encoders = torch.nn.ModuleList(
-            [_EncoderLayer(output_size, attention_heads, linear_units) for _ in range(num_blocks)])
-        self.after_norm = LayerNorm(output_size)
-        self._pos_cache, self._ws, self._olens_cache = {}, None, {}
 
     def _build_pack(self, pk):
         A, F, act = pk.A, pk.F, pk.act
         d, ff, Lb = self._output_size, self.linear_units, self.num_blocks
-        e = self.embed
-        F2 = e.out.in_features // d
         w = L.EmTransformerWeights()
         w.d, w.heads, w.ff, w.num_blocks, w.n_mels = d, self.heads, ff, Lb, self._input_size
-        t = dict(conv1_w=F(e.conv[0].weight.reshape(d, 9)), conv1_b=F(e.conv[0].bias),
-                 embed_w=A(e.out.weight.reshape(d, d, F2).permute(0, 2, 1).reshape(d, F2 * d)),
-                 embed_b=F(e.out.bias), after_norm_g=F(self.after_norm.weight), after_norm_b=F(self.after_norm.bias))
-        self._pack_subsampling(w, t, A, F)
-        pk.fill(w, t)
+        pk.fill(w, self._pack_embed(pk, w))
         layers = (L.EmTransformerLayer * max(Lb, 1))()
-        rows = act == torch.bfloat16 and d == 512 and ff % 128 == 0 and ff >= 256
+        rows = rows_ffn_packable(act, d, ff)
         for i, l in enumerate(self.encoders):
             sa, fw = l.self_attn, l.feed_forward
             lt = dict(norm1_g=F(l.norm1.weight), norm1_b=F(l.norm1.bias), norm2_g=F(l.norm2.weight),
@@ -139,7 +107,7 @@ class TransformerEncoder(ConformerEncoder):
         w.layers = C.cast(layers, C.POINTER(L.EmTransformerLayer))
         pk.w, pk.layers = w, layers
 
-    def _pos_emb(self, T: int, device) -> torch.Tensor:
+    def _call_operands(self, T: int, device, pk):
         """pe[:T] (T, d) f32: PositionalEncoding's table (embedding.py extend_pe, the same fp32 torch ops) sliced as the
         reference slices it; one table per device, rebuilt longer (doubling) when an input outgrows it.  Row t depends on
         t alone, so a slice of a longer table is bit-identical to a table built for T."""
@@ -151,4 +119,4 @@ class TransformerEncoder(ConformerEncoder):
                 n *= 2
             tab = abs_pos_table(n, self._output_size).to(torch.float32).to(device)
             self._pos_cache[key] = tab
-        return tab[:T]
+        return tab[:T], 0

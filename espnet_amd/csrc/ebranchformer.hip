@@ -20,12 +20,12 @@
 #include "em_common.h"
 #include "switches.h"
 #include "subsample.h"
+#include "enc_host.h"
+
+using em_host::gemm;
+using em_host::LN_EPS;
 
 namespace {
-
-constexpr float LN_EPS = 1e-12f;
-
-inline size_t align_up(size_t v) { return (v + 255) & ~(size_t)255; }
 
 struct Ws {
   size_t c1, c2, c3, x, xn, xn2, big, gn, gated, cat, tmp, ctx, pall, mw, qh, kh, vt, total;
@@ -41,44 +41,30 @@ inline Ws layout(int dtype, const EmEBranchformerWeights* w, int B, int T_f) {
   size_t wide = w->ff > 3 * w->d ? w->ff : 3 * w->d;
   if ((size_t)w->cg > wide) wide = w->cg;
   Ws s;
-  size_t o = 0;
-  s.c1 = o; o += align_up(mb[0]);
-  s.c2 = o; o += align_up(mb[1]);
-  s.c3 = o; o += align_up(mb[2]);
-  s.x = o; o += align_up(M * d * 4);
-  s.xn = o; o += align_up(M * d * es);
-  s.xn2 = o; o += align_up(M * d * es);
-  s.big = o; o += align_up(M * wide * es);
-  s.gn = o; o += align_up(M * (size_t)(w->cg / 2) * es);
-  s.gated = o; o += align_up(M * (size_t)(w->cg / 2) * es);
-  s.cat = o; o += align_up(M * 2 * d * es);
-  s.tmp = o; o += align_up(M * 2 * d * es);
-  s.ctx = o; o += align_up(M * d * es);
-  s.pall = o; o += align_up((size_t)(2 * g.T_out - 1) * w->num_blocks * d * es);
-  s.mw = o; o += align_up((size_t)B * 2 * sizeof(float));
+  em_host::Bump b;
+  s.c1 = b.take(mb[0]);
+  s.c2 = b.take(mb[1]);
+  s.c3 = b.take(mb[2]);
+  s.x = b.take(M * d * 4);
+  s.xn = b.take(M * d * es);
+  s.xn2 = b.take(M * d * es);
+  s.big = b.take(M * wide * es);
+  s.gn = b.take(M * (size_t)(w->cg / 2) * es);
+  s.gated = b.take(M * (size_t)(w->cg / 2) * es);
+  s.cat = b.take(M * 2 * d * es);
+  s.tmp = b.take(M * 2 * d * es);
+  s.ctx = b.take(M * d * es);
+  s.pall = b.take((size_t)(2 * g.T_out - 1) * w->num_blocks * d * es);
+  s.mw = b.take((size_t)B * 2 * sizeof(float));
   // per-head operands of the LDS-resident attention (csrc/attention2.hip; bf16, d_k = 64): as in encoder.hip
-  s.Tpad = (g.T_out + 255) / 256 * 256;
-  const size_t per_head = (size_t)B * d * s.Tpad * es;
-  s.qh = o; o += align_up(per_head);
-  s.kh = o; o += align_up(per_head);
-  s.vt = o; o += align_up(per_head);
-  s.total = o;
+  s.Tpad = em_host::tpad256(g.T_out);
+  const size_t per_head = em_host::head_slab_bytes(B, w->d, s.Tpad, es);
+  s.qh = b.take(per_head);
+  s.kh = b.take(per_head);
+  s.vt = b.take(per_head);
+  s.total = b.o;
   return s;
 }
-
-inline int gemm(int dtype, int epi, const void* A, const void* W, void* C, const float* bias, int M,
-                int N, int K, int lda, int ldc, float scale, void* stream) {
-  EmGemmArgs a = {};
-  a.A = A; a.W = W; a.C = C; a.bias = bias;
-  a.M = M; a.N = N; a.K = K; a.lda = lda; a.ldc = ldc; a.scale = scale;
-  return em_gemm(dtype, epi, EM_A_PLAIN, &a, stream);
-}
-
-#define EM_TRY(expr)                \
-  do {                              \
-    int rc__ = (expr);              \
-    if (rc__ != EM_OK) return rc__; \
-  } while (0)
 
 // ---- Branchformer learned_ave (branchformer_encoder.py:212-270).  Branch k of utterance b is attention-pooled
 // over its valid frames with scores (x_t . pool_w + pool_b) / sqrt(d), and the pooled vector is projected to
@@ -224,20 +210,16 @@ extern "C" int em_ebranchformer_encode(int dtype, const EmEBranchformerWeights* 
   const bool ffn = w->use_ffn != 0;
   // round 4: bf16 with d_k = 64 -> the LDS-resident attention, its operands written per head by the projection GEMMs
   // (see encoder.hip; ESPNET_AMD_NO_ATTN2_LARGE=1: developer A/B switch)
-  const bool no_attn2 = em_sw().no_attn2_large;
-  const bool attn2 = dtype == EM_BF16 && !w->legacy_relpos && !no_attn2 && !(flags & EM_ENC_NO_FUSED) && d == 64 * h &&
-                     (size_t)B * d * s.Tpad * 4 < ((size_t)1 << 32) - 64;
+  const bool attn2 = !w->legacy_relpos && !(flags & EM_ENC_NO_FUSED) && em_host::head_operands_ok(dtype, d, h, B, s.Tpad);
   void* qh = ws + s.qh;
   void* vt = ws + s.vt;
-  if (attn2 && hipMemsetAsync(qh, 0, (s.vt - s.qh) + (size_t)B * d * s.Tpad * es, (hipStream_t)stream) != hipSuccess)
-    return EM_ERR_LAUNCH;
+  if (attn2) EM_TRY(em_host::clear_head_slabs(qh, (s.vt - s.qh) + em_host::head_slab_bytes(B, d, s.Tpad, es), stream));
   // Round 6: the two feed-forward modules as row-block launches of csrc/ffn_rows.hip (bf16, d = 512, the host packed their
   // operand streams): [macaron FFN + residual + norm_mha] and [FFN + residual + norm_final + the next LayerNorm] - three
   // launches each until now (two tiled GEMMs through the [M][ff] hidden activation + a LayerNorm) - when a round of
   // 64-row workgroups fills its share of the chip (em_rows_fill_ok: B = 32 x 10 s is 125 workgroups - taken with two batches
   // in flight, EM_ENC_IN_FLIGHT).  ESPNET_AMD_NO_FFN_ROWS=1: developer switch.
-  bool ffn_rows = ffn && dtype == EM_BF16 && d == 512 && ff % 128 == 0 && ff >= 256 && !(flags & EM_ENC_NO_FUSED) &&
-                  !em_sw().no_ffn_rows && em_rows_fill_ok(M, flags);
+  bool ffn_rows = ffn && em_host::rows_ffn_ok(dtype, d, ff, flags, M);
   for (int l = 0; ffn_rows && l < L; ++l) ffn_rows = ly[l].ffm_w1p && ly[l].ffm_w2p && ly[l].ff_w1p && ly[l].ff_w2p;
   const EmEBranchformerLayer* ln_in = nullptr;  // set for the launch that computes norm_ff itself (reset after it)
   // ... and q | k | v walked behind the macaron launch (EmFfnRowsArgs.post_q; ESPNET_AMD_NO_ROWS_QKV=1: developer switch)
@@ -284,16 +266,7 @@ extern "C" int em_ebranchformer_encode(int dtype, const EmEBranchformerWeights* 
     if (!(ffn_rows && rows_qkv)) EM_TRY(em_layernorm(dtype, x, q.norm_mlp_g, q.norm_mlp_b, M, d, LN_EPS, xn2, nullptr, stream));
     // branch 1 (:141-152): rel-pos self-attention; linear_out lands in cat[:, :d]
     if (attn2) {
-      if (!rows_qkv) {
-        EmGemmArgs a = {};
-        a.A = xn; a.W = q.wqkv; a.C = qh; a.bias = q.bqkv;
-        a.M = M; a.N = 2 * d; a.K = d; a.lda = d; a.ldc = 64; a.scale = 1.f;
-        a.T1 = T; a.T2 = s.Tpad; a.F1 = h; a.d = d;
-        EM_TRY(em_gemm(dtype, EM_EPI_QK_HEADS, EM_A_PLAIN, &a, stream));
-        a.A = (const unsigned char*)q.wqkv + (size_t)2 * d * d * es; a.W = xn; a.C = vt; a.bias = q.bqkv + 2 * d;
-        a.M = d; a.N = M; a.ldc = s.Tpad;
-        EM_TRY(em_gemm(dtype, EM_EPI_VT_HEADS, EM_A_PLAIN, &a, stream));
-      }
+      if (!rows_qkv) EM_TRY(em_host::project_heads(dtype, xn, q.wqkv, q.bqkv, qh, vt, M, d, h, T, s.Tpad, stream));
       EM_TRY(em_relpos_attention2_bf16(qh, ws + s.kh, vt, (const unsigned char*)pall + (size_t)l * d * es, L * d, q.pos_u,
                                        q.pos_v, olens, B, T, s.Tpad, h, ctx, stream));
     } else {

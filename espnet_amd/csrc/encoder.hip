@@ -14,18 +14,18 @@
 #include "em_common.h"
 #include "switches.h"
 #include "subsample.h"
+#include "enc_host.h"
+
+using em_host::align_up;
+using em_host::gemm;
+using em_host::LN_EPS;
 
 namespace {
-
-constexpr float LN_EPS = 1e-12f;  // transformer/layer_norm.py:23
-
-inline size_t align_up(size_t v) { return (v + 255) & ~(size_t)255; }
 
 struct Ws {
   size_t c1, c2, c3, x, xn, big, g, g2, ctx, pall, qh, kh, vt, ppk, total;
   int Tpad;
 };
-inline int fused_tpad(int T) { return (T + 255) / 256 * 256; }
 inline Ws layout(int dtype, const EmConformerWeights* w, int B, int T_f) {
   const size_t es = dtype == EM_BF16 ? 2 : 4;
   em_sub::Geo g;
@@ -35,38 +35,28 @@ inline Ws layout(int dtype, const EmConformerWeights* w, int B, int T_f) {
   em_sub::map_bytes(g, B, w->d, es, mb);
   size_t wide = w->ff > 3 * w->d ? w->ff : 3 * w->d;
   Ws s;
-  size_t o = 0;
-  s.c1 = o; o += align_up(mb[0]);
-  s.c2 = o; o += align_up(mb[1]);
-  s.c3 = o; o += align_up(mb[2]);
-  s.x = o; o += align_up(M * d * 4);
-  s.xn = o; o += align_up(M * d * es);
-  s.big = o; o += align_up(M * wide * es);
-  s.g = o; o += align_up(M * d * es);
-  s.g2 = o; o += align_up(M * d * es);
-  s.ctx = o; o += align_up(M * d * es);
-  s.pall = o; o += align_up((size_t)(2 * g.T_out - 1) * w->num_blocks * d * es);
+  em_host::Bump b;
+  s.c1 = b.take(mb[0]);
+  s.c2 = b.take(mb[1]);
+  s.c3 = b.take(mb[2]);
+  s.x = b.take(M * d * 4);
+  s.xn = b.take(M * d * es);
+  s.big = b.take(M * wide * es);
+  s.g = b.take(M * d * es);
+  s.g2 = b.take(M * d * es);
+  s.ctx = b.take(M * d * es);
+  s.pall = b.take((size_t)(2 * g.T_out - 1) * w->num_blocks * d * es);
   // fused path (csrc/block.hip, csrc/attention2.hip): Q, K [B][H][Tpad][64], V^T [B][H][64][Tpad]
-  s.Tpad = fused_tpad(g.T_out);
-  const size_t per_head = (size_t)B * d * s.Tpad * es;
-  s.qh = o; o += align_up(per_head);
-  s.kh = o; o += align_up(per_head);
-  s.vt = o; o += align_up(per_head);
+  s.Tpad = em_host::tpad256(g.T_out);
+  const size_t per_head = em_host::head_slab_bytes(B, w->d, s.Tpad, es);
+  s.qh = b.take(per_head);
+  s.kh = b.take(per_head);
+  s.vt = b.take(per_head);
   // block<ATT|C> (round 6): the position rows of every block, fragment-major (em_relpos_pack_pos_bf16)
-  s.ppk = o; o += align_up((size_t)w->num_blocks * 4 * em_relpos_pos_fragments(g.T_out) * 2048);
-  s.total = o;
+  s.ppk = b.take((size_t)w->num_blocks * 4 * em_relpos_pos_fragments(g.T_out) * 2048);
+  s.total = b.o;
   return s;
 }
-
-inline int gemm(int dtype, int epi, const void* A, const void* W, void* C, const float* bias, int M,
-                int N, int K, int lda, int ldc, float scale, void* stream) {
-  EmGemmArgs a = {};
-  a.A = A; a.W = W; a.C = C; a.bias = bias;
-  a.M = M; a.N = N; a.K = K; a.lda = lda; a.ldc = ldc; a.scale = scale;
-  a.T1 = a.F1 = a.T2 = a.F2 = a.d = 0;
-  return em_gemm(dtype, epi, EM_A_PLAIN, &a, stream);
-}
-
 
 }  // namespace
 
@@ -106,13 +96,9 @@ struct RowsPlan {
 };
 inline RowsPlan rows_plan(int dtype, const EmConformerWeights* w, int flags, long M) {
   RowsPlan r = {false, false, false, false};
-  const bool no_ffn_rows = em_sw().no_ffn_rows;
-  const int d = w->d, ff = w->ff, L = w->num_blocks;
+  const int L = w->num_blocks;
   const EmConformerLayer* ly = w->layers;
-  if (!(dtype == EM_BF16 && d == 512 && ff % 128 == 0 && ff >= 256 && !(flags & EM_ENC_NO_FUSED) && !no_ffn_rows && ly && L > 0 &&
-        M > 0))
-    return r;
-  r.ffn = em_rows_fill_ok(M, flags);
+  r.ffn = ly && L > 0 && M > 0 && em_host::rows_ffn_ok(dtype, w->d, w->ff, flags, M);
   for (int l = 0; r.ffn && l < L; ++l) r.ffn = ly[l].ffm_w1p && ly[l].ffm_w2p && ly[l].ff_w1p && ly[l].ff_w2p;
   // ... pointwise_conv2 + residual + norm_ff ride in the second module's launch when the host packed pw2 as well
   r.pre_pw2 = r.ffn;
@@ -142,12 +128,6 @@ inline int encode_plan(int dtype, const EmConformerWeights* w, int flags, long M
   const bool ctc = w->ctc_ids && w->ctc_w && w->ctc_b && w->ctc_units > 0;
   return EM_ENC_PLAN_FUSED | (ctc ? EM_ENC_PLAN_CTC_IDS : 0);
 }
-
-#define EM_TRY(expr)            \
-  do {                          \
-    int rc__ = (expr);          \
-    if (rc__ != EM_OK) return rc__; \
-  } while (0)
 
 }  // namespace
 
@@ -221,9 +201,7 @@ extern "C" int em_conformer_encode(int dtype, const EmConformerWeights* w, const
     // key columns >= 32 * ceil(T / 32) of V^T are never written and meet probability 0 in P.V: they must be finite.
     // (When the 32-frame row blocks cover Tpad - T = 249: 8 x 32 = 256 - every column is written by the block kernels,
     // frames past T as recomputed copies of frame T - 1: no memset, 5 us of a 1.07 ms step.)
-    if (32 * em_cdiv(T, 32) < s.Tpad &&
-        hipMemsetAsync(vt, 0, (size_t)B * d * s.Tpad * es, (hipStream_t)stream) != hipSuccess)
-      return EM_ERR_LAUNCH;
+    if (32 * em_cdiv(T, 32) < s.Tpad) EM_TRY(em_host::clear_head_slabs(vt, em_host::head_slab_bytes(B, d, s.Tpad, es), stream));
     EmBlockArgs ba = {};
     ba.B = B; ba.T = T; ba.Tpad = s.Tpad; ba.d = d; ba.ff = ff; ba.kernel = w->kernel; ba.eps = LN_EPS;
     ba.x = x; ba.ctx = ctx; ba.glu = gl; ba.qh = qh; ba.kh = kh; ba.vt = vt;
@@ -299,19 +277,13 @@ extern "C" int em_conformer_encode(int dtype, const EmConformerWeights* w, const
   // ffn_fused_rowblock.hip.txt).
   // Round 4: wherever d_k = 64 and the dtype is bf16 (the large model, 8 heads) the attention runs in the LDS-resident
   // kernel of the fused path (csrc/attention2.hip: 0.11 of the MFMA peak against 0.05 for relpos_attn_kernel, which takes
-  // 90 us per block at B = 64): its per-head operands are written by the projection GEMMs themselves - q | k through
-  // EM_EPI_QK_HEADS, V^T as the swapped product W_v . xn^T through EM_EPI_VT_HEADS - so there is no repacking pass.
-  // ESPNET_AMD_NO_ATTN2_LARGE=1: developer A/B switch.
-  const bool no_attn2 = em_sw().no_attn2_large;
-  const bool attn2 = dtype == EM_BF16 && !w->legacy_relpos && !(flags & EM_ENC_NO_FUSED) && !no_attn2 && d == 64 * h &&
-                     (size_t)B * d * s.Tpad * 4 < ((size_t)1 << 32) - 64;
+  // 90 us per block at B = 64): its per-head operands are written by the projection GEMMs themselves
+  // (em_host::project_heads, where the shared part of this rule - em_host::head_operands_ok - lives too).
+  const bool attn2 = !w->legacy_relpos && !(flags & EM_ENC_NO_FUSED) && em_host::head_operands_ok(dtype, d, h, B, s.Tpad);
   void* qh = ws + s.qh;
   void* vt = ws + s.vt;
-  if (attn2) {
-    // frames >= T of every (b, head) slab must be finite: keys / probabilities there are masked, not skipped
-    if (hipMemsetAsync(qh, 0, (s.vt - s.qh) + (size_t)B * d * s.Tpad * es, (hipStream_t)stream) != hipSuccess)
-      return EM_ERR_LAUNCH;
-  }
+  // frames >= T of every (b, head) slab must be finite: keys / probabilities there are masked, not skipped
+  if (attn2) EM_TRY(em_host::clear_head_slabs(qh, (s.vt - s.qh) + em_host::head_slab_bytes(B, d, s.Tpad, es), stream));
   const RowsPlan rp = rows_plan(dtype, w, flags, M);
   const bool ffn_rows = rp.ffn, pre_pw2 = rp.pre_pw2, rows_glu = rp.glu;
   const EmConformerLayer* pre_layer = nullptr;  // set for the call that carries the projection
@@ -358,16 +330,7 @@ extern "C" int em_conformer_encode(int dtype, const EmConformerWeights* w, const
       EM_TRY(em_layernorm(dtype, x, q.norm_mha_g, q.norm_mha_b, M, d, LN_EPS, xn, nullptr, stream));
     }
     if (attn2) {
-      if (!rows_qkv) {
-        EmGemmArgs a = {};
-        a.A = xn; a.W = q.wqkv; a.C = qh; a.bias = q.bqkv;
-        a.M = M; a.N = 2 * d; a.K = d; a.lda = d; a.ldc = 64; a.scale = 1.f;
-        a.T1 = T; a.T2 = s.Tpad; a.F1 = h; a.d = d;
-        EM_TRY(em_gemm(dtype, EM_EPI_QK_HEADS, EM_A_PLAIN, &a, stream));
-        a.A = (const unsigned char*)q.wqkv + (size_t)2 * d * d * es; a.W = xn; a.C = vt; a.bias = q.bqkv + 2 * d;
-        a.M = d; a.N = M; a.ldc = s.Tpad;
-        EM_TRY(em_gemm(dtype, EM_EPI_VT_HEADS, EM_A_PLAIN, &a, stream));
-      }
+      if (!rows_qkv) EM_TRY(em_host::project_heads(dtype, xn, q.wqkv, q.bqkv, qh, vt, M, d, h, T, s.Tpad, stream));
       EM_TRY(em_relpos_attention2_bf16(qh, ws + s.kh, vt, (const unsigned char*)pall + (size_t)l * d * es, L * d, q.pos_u,
                                        q.pos_v, olens, B, T, s.Tpad, h, ctx, stream));
     } else {

@@ -27,6 +27,10 @@
 #include "em_common.h"
 #include "rnn_cell.h"
 #include "switches.h"
+#include "enc_host.h"
+
+using em_host::gemm;
+using em_host::LN_EPS;
 
 namespace {
 
@@ -1092,24 +1096,6 @@ __global__ __launch_bounds__(256) void col_logsoftmax_kernel(float* __restrict__
       x[o] = x[o] + (bias ? bias[v] : 0.f) - lse;
     }
 }
-
-
-inline int gemm(int dtype, int epi, const void* A, const void* W, void* C, const float* bias, int M,
-                int N, int K, int lda, int ldc, float scale, void* stream) {
-  EmGemmArgs a = {};
-  a.A = A; a.W = W; a.C = C; a.bias = bias;
-  a.M = M; a.N = N; a.K = K; a.lda = lda; a.ldc = ldc; a.scale = scale;
-  a.T1 = a.F1 = a.T2 = a.F2 = a.d = 0;
-  return em_gemm(dtype, epi, EM_A_PLAIN, &a, stream);
-}
-
-#define EM_TRY(expr)                \
-  do {                              \
-    int rc__ = (expr);              \
-    if (rc__ != EM_OK) return rc__; \
-  } while (0)
-
-constexpr float LN_EPS = 1e-12f;
 
 // C = epi(LN(x) W^T + bias) for the n rows of a search step.  Measured at K = 512 (tools/ln_gemm_bench.py):
 // the fused kernel takes 8-9 us against 9.4-9.7 us for LayerNorm + tiled GEMM (two launches at the ~4.7 us

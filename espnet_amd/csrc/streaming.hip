@@ -20,6 +20,10 @@
 
 #include "em_common.h"
 #include "switches.h"
+#include "enc_host.h"
+
+using em_host::gemm;
+using em_host::LN_EPS;
 
 namespace {
 
@@ -413,8 +417,6 @@ __global__ __launch_bounds__(256) void stream_pos_enc_kernel(const float* __rest
     out[(size_t)j * d + c] = xs[(size_t)j * d + c] * xscale + pe[(size_t)(start + j) * d + c];
 }
 
-inline size_t align_up(size_t v) { return (v + 255) & ~(size_t)255; }
-
 struct CbWs {
   size_t xn, big, g, g2, ctx, qh, kh, vt, part, ticket, total;
   int Tpad;
@@ -424,13 +426,13 @@ inline CbWs cb_layout(int dtype, const EmConformerWeights* w, int M) {
   const size_t d = w->d;
   const size_t wide = (size_t)w->ff > 3 * d ? w->ff : 3 * d;
   CbWs s;
-  size_t o = 0;
-  s.xn = o; o += align_up((size_t)M * d * es);
-  s.big = o; o += align_up((size_t)M * wide * es);
-  s.g = o; o += align_up((size_t)M * d * es);
-  s.g2 = o; o += align_up((size_t)M * d * es);
-  s.ctx = o; o += align_up((size_t)M * d * es);
-  s.total = o;
+  em_host::Bump b;
+  s.xn = b.take((size_t)M * d * es);
+  s.big = b.take((size_t)M * wide * es);
+  s.g = b.take((size_t)M * d * es);
+  s.g2 = b.take((size_t)M * d * es);
+  s.ctx = b.take((size_t)M * d * es);
+  s.total = b.o;
   return s;
 }
 // ... plus the per-head operands of the fused layer (bf16, d = 256: csrc/block.hip): q / k [n_blk][4][Tpad][64],
@@ -458,15 +460,15 @@ inline CbWs cb_layout_fused(int dtype, const EmConformerWeights* w, int n_blk, i
   CbWs s = cb_layout(dtype, w, n_blk * L);
   s.Tpad = (L + 63) / 64 * 64;
   const size_t per_head = (size_t)n_blk * w->d * s.Tpad * 2;
-  size_t o = s.total;
-  s.qh = o; o += align_up(per_head);
-  s.kh = o; o += align_up(per_head);
-  s.vt = o; o += align_up(per_head);
+  em_host::Bump b = {s.total};
+  s.qh = b.take(per_head);
+  s.kh = b.take(per_head);
+  s.vt = b.take(per_head);
   // split FFN of the row-block launches (round 6, EmBlockArgs.ffn_split): partial sums [row blocks][S][8192] f32 + tickets
   const int nrb = n_blk * ((L + 31) / 32), S = cb_ffn_split(w, nrb);
-  s.part = o; o += S > 1 ? align_up((size_t)nrb * S * 8192 * 4) : 0;
-  s.ticket = o; o += S > 1 ? align_up((size_t)nrb * 4) : 0;
-  s.total = o;
+  s.part = b.take(S > 1 ? (size_t)nrb * S * 8192 * 4 : 0);
+  s.ticket = b.take(S > 1 ? (size_t)nrb * 4 : 0);
+  s.total = b.o;
   return s;
 }
 // Which streaming layers take the fused launch sequence: bf16, 256 wide, 4 heads, conv width 15, ff <= 4096 in whole
@@ -491,22 +493,6 @@ inline bool cb_fusable(int dtype, const EmConformerWeights* w, int L, int n_blk)
   }
   return true;
 }
-
-inline int gemm(int dtype, int epi, const void* A, const void* W, void* C, const float* bias, int M,
-                int N, int K, int lda, int ldc, float scale, void* stream) {
-  EmGemmArgs a = {};
-  a.A = A; a.W = W; a.C = C; a.bias = bias;
-  a.M = M; a.N = N; a.K = K; a.lda = lda; a.ldc = ldc; a.scale = scale;
-  return em_gemm(dtype, epi, EM_A_PLAIN, &a, stream);
-}
-
-#define EM_TRY(expr)                \
-  do {                              \
-    int rc__ = (expr);              \
-    if (rc__ != EM_OK) return rc__; \
-  } while (0)
-
-constexpr float LN_EPS = 1e-12f;
 
 }  // namespace
 

@@ -16,12 +16,13 @@
 
 #include "em_common.h"
 #include "switches.h"
+#include "enc_host.h"
+
+using em_host::align_up;
+using em_host::gemm;
+using em_host::LN_EPS;
 
 namespace {
-
-constexpr float LN_EPS = 1e-12f;
-
-inline size_t align_up(size_t v) { return (v + 255) & ~(size_t)255; }
 
 struct Ws {
   size_t xn, big, ctx, qkv[2], part, ticket, total;  // qkv[i]: q | k | V^T per head, set i (fused path; two sets: see merge)
@@ -33,11 +34,11 @@ inline Ws layout(int dtype, const EmTransformerWeights* w, int M) {
   const size_t d = w->d;
   const size_t wide = (size_t)w->ff > 3 * d ? w->ff : 3 * d;
   Ws s = {};
-  size_t o = 0;
-  s.xn = o; o += align_up((size_t)M * d * es);
-  s.big = o; o += align_up((size_t)M * wide * es);
-  s.ctx = o; o += align_up((size_t)M * d * es);
-  s.total = o;
+  em_host::Bump b;
+  s.xn = b.take((size_t)M * d * es);
+  s.big = b.take((size_t)M * wide * es);
+  s.ctx = b.take((size_t)M * d * es);
+  s.total = b.o;
   return s;
 }
 // Shares of the FFN's hidden dimension per 32-row block: the rule csrc/streaming.hip measured for the Conformer layer's FFNs
@@ -56,12 +57,12 @@ inline Ws layout_fused(const EmTransformerWeights* w, int n_blk, int L) {
   Ws s = {};
   s.Tpad = (L + 63) / 64 * 64;
   s.per_head = align_up((size_t)n_blk * w->d * s.Tpad * 2);
-  size_t o = 0;
-  for (int i = 0; i < 2; ++i) { s.qkv[i] = o; o += 3 * s.per_head; }
+  em_host::Bump b;
+  for (int i = 0; i < 2; ++i) s.qkv[i] = b.take(3 * s.per_head);
   const int nrb = n_blk * ((L + 31) / 32), S = ffn_split(w, nrb);
-  s.part = o; o += S > 1 ? align_up((size_t)nrb * S * 8192 * 4) : 0;
-  s.ticket = o; o += S > 1 ? align_up((size_t)nrb * 4) : 0;
-  s.total = o;
+  s.part = b.take(S > 1 ? (size_t)nrb * S * 8192 * 4 : 0);
+  s.ticket = b.take(S > 1 ? (size_t)nrb * 4 : 0);
+  s.total = b.o;
   return s;
 }
 // Which calls take the row-block launches: the gate of the Conformer variant (cb_fusable) - bf16, 256 wide, 4 heads,
@@ -88,20 +89,6 @@ inline bool merged(bool fold) {
   const int sw = em_sw().stream_tf_merge;
   return fold && (sw < 0 ? merge_default() : sw != 0);
 }
-
-inline int gemm(int dtype, int epi, const void* A, const void* W, void* C, const float* bias, int M, int N, int K, int lda,
-                int ldc, float scale, void* stream) {
-  EmGemmArgs a = {};
-  a.A = A; a.W = W; a.C = C; a.bias = bias;
-  a.M = M; a.N = N; a.K = K; a.lda = lda; a.ldc = ldc; a.scale = scale;
-  return em_gemm(dtype, epi, EM_A_PLAIN, &a, stream);
-}
-
-#define EM_TRY(expr)                \
-  do {                              \
-    int rc__ = (expr);              \
-    if (rc__ != EM_OK) return rc__; \
-  } while (0)
 
 int encode_impl(int dtype, const EmTransformerWeights* w, float* x, int32_t n_streams, int32_t n_blk_s, int32_t L,
                 int32_t mask_mode, const float* past_ctx, float* next_ctx, void* workspace, size_t workspace_bytes,

@@ -14,17 +14,12 @@
 
 #include "em_common.h"
 #include "rnn_cell.h"
+#include "enc_host.h"
 
 namespace {
 
 constexpr int MAXRT = 4;  // 16-row tiles per launch: n <= 64 rows
 constexpr int MAXROWS = 16 * MAXRT;
-
-#define EM_TRY(expr)                \
-  do {                              \
-    const int rc__ = (expr);        \
-    if (rc__ != EM_OK) return rc__; \
-  } while (0)
 
 // acc[rt] += A[row(rt)][k] * W[col][k] over the k-steps s0, s0 + stride, ... < nsteps of this wave.  arow / wrow carry
 // the lane's k offset already (lg * EPL).  Only the nrt row tiles that hold rows are loaded and multiplied (nrt is
@@ -368,17 +363,16 @@ struct WalkWs {
 };
 WalkWs walk_layout(int dtype, const EmTransducerWeights* w, int B) {
   const size_t es = dtype == EM_BF16 ? 2 : 4;
-  auto up = [](size_t v) { return (v + 255) / 256 * 256; };
   WalkWs o;
-  size_t at = 0;
-  o.part = at, at += up((size_t)B * em_cdiv(w->vocab, 16) * sizeof(float4));
-  o.z = at, at += up((size_t)B * w->jp * es);
-  o.dec_proj = at, at += up((size_t)B * w->jp * 4);
-  o.hs = at, at += up((size_t)2 * w->num_layers * B * w->d * es);
-  o.cs = at, at += up((size_t)2 * w->num_layers * B * w->d * 4);
-  o.tok_cur = at, at += up((size_t)B * 4);
-  o.emit = at, at += up((size_t)B * 4);
-  o.total = at;
+  em_host::Bump b;
+  o.part = b.take((size_t)B * em_cdiv(w->vocab, 16) * sizeof(float4));
+  o.z = b.take((size_t)B * w->jp * es);
+  o.dec_proj = b.take((size_t)B * w->jp * 4);
+  o.hs = b.take((size_t)2 * w->num_layers * B * w->d * es);
+  o.cs = b.take((size_t)2 * w->num_layers * B * w->d * 4);
+  o.tok_cur = b.take((size_t)B * 4);
+  o.emit = b.take((size_t)B * 4);
+  o.total = b.o;
   return o;
 }
 

@@ -18,12 +18,12 @@
 #include "em_common.h"
 #include "switches.h"
 #include "subsample.h"
+#include "enc_host.h"
+
+using em_host::gemm;
+using em_host::LN_EPS;
 
 namespace {
-
-constexpr float LN_EPS = 1e-12f;
-
-inline size_t align_up(size_t v) { return (v + 255) & ~(size_t)255; }
 
 struct Ws {
   size_t c1, c2, c3, x, xn, big, ctx, qh, kh, vt, total;
@@ -38,37 +38,23 @@ inline Ws layout(int dtype, const EmTransformerWeights* w, int B, int T_f) {
   em_sub::map_bytes(g, B, w->d, es, mb);
   const size_t wide = (size_t)w->ff > 3 * d ? (size_t)w->ff : 3 * d;
   Ws s;
-  size_t o = 0;
-  s.c1 = o; o += align_up(mb[0]);
-  s.c2 = o; o += align_up(mb[1]);
-  s.c3 = o; o += align_up(mb[2]);
-  s.x = o; o += align_up(M * d * 4);
-  s.xn = o; o += align_up(M * d * es);
-  s.big = o; o += align_up(M * wide * es);
-  s.ctx = o; o += align_up(M * d * es);
+  em_host::Bump b;
+  s.c1 = b.take(mb[0]);
+  s.c2 = b.take(mb[1]);
+  s.c3 = b.take(mb[2]);
+  s.x = b.take(M * d * 4);
+  s.xn = b.take(M * d * es);
+  s.big = b.take(M * wide * es);
+  s.ctx = b.take(M * d * es);
   // per-head operands of the bf16 attention (q, k [B][H][Tpad][64], V^T [B][H][64][Tpad])
-  s.Tpad = (g.T_out + 255) / 256 * 256;
-  const size_t per_head = dtype == EM_BF16 ? (size_t)B * d * s.Tpad * es : 0;
-  s.qh = o; o += align_up(per_head);
-  s.kh = o; o += align_up(per_head);
-  s.vt = o; o += align_up(per_head);
-  s.total = o;
+  s.Tpad = em_host::tpad256(g.T_out);
+  const size_t per_head = dtype == EM_BF16 ? em_host::head_slab_bytes(B, w->d, s.Tpad, es) : 0;
+  s.qh = b.take(per_head);
+  s.kh = b.take(per_head);
+  s.vt = b.take(per_head);
+  s.total = b.o;
   return s;
 }
-
-inline int gemm(int dtype, int epi, const void* A, const void* W, void* C, const float* bias, int M, int N, int K, int lda,
-                int ldc, float scale, void* stream) {
-  EmGemmArgs a = {};
-  a.A = A; a.W = W; a.C = C; a.bias = bias;
-  a.M = M; a.N = N; a.K = K; a.lda = lda; a.ldc = ldc; a.scale = scale;
-  return em_gemm(dtype, epi, EM_A_PLAIN, &a, stream);
-}
-
-#define EM_TRY(expr)                \
-  do {                              \
-    int rc__ = (expr);              \
-    if (rc__ != EM_OK) return rc__; \
-  } while (0)
 
 // x[b*T + t][c] += pe[t][c]  (PositionalEncoding.forward after the * sqrt(d) of the embed GEMM's epilogue)
 __global__ __launch_bounds__(256) void abs_pe_add_kernel(float* __restrict__ x, const float* __restrict__ pe, int T, int d4,
@@ -106,7 +92,6 @@ extern "C" int em_transformer_encode(int dtype, const EmTransformerWeights* w, c
   em_sub::Geo g;
   if (!em_sub::geo(w->subsample, T_f, w->n_mels, &g)) return EM_ERR_UNSUPPORTED;
   const int T = g.T_out, M = B * T;
-  const size_t es = dtype == EM_BF16 ? 2 : 4;
   unsigned char* ws = (unsigned char*)workspace;
   float* x = (float*)(ws + s.x);
   void* xn = ws + s.xn;
@@ -131,13 +116,13 @@ extern "C" int em_transformer_encode(int dtype, const EmTransformerWeights* w, c
     return em_layernorm(dtype, x, w->after_norm_g, w->after_norm_b, M, d, LN_EPS, enc_act, enc_out, stream);
 
   // bf16: q / k / V^T written per head by the projection GEMMs for the MFMA attention (as the Conformer's attention2 path;
-  // ESPNET_AMD_NO_ATTN2_LARGE=1 - developer switch - and operands past 32-bit offsets keep the row-layout kernel)
-  const bool heads_path = dtype == EM_BF16 && !em_sw().no_attn2_large && (size_t)B * d * s.Tpad * 4 < ((size_t)1 << 32) - 64;
+  // ESPNET_AMD_NO_ATTN2_LARGE=1 - developer switch - and operands past 32-bit offsets keep the row-layout kernel).
+  // EM_ENC_NO_FUSED does not switch this path off, unlike the Conformer's and the E-Branchformer's.
+  const bool heads_path = em_host::head_operands_ok(dtype, d, h, B, s.Tpad);
   // 512-wide bf16 model: FFN + residual + the next LayerNorm as one row-block launch (csrc/ffn_rows.hip, ReLU) when a round of
   // 64-row workgroups fills its share of the chip - the rule and the developer switches of the Conformer / E-Branchformer
   // (ESPNET_AMD_NO_FFN_ROWS, ESPNET_AMD_FFN_ROWS_MIN_FILL; EM_ENC_IN_FLIGHT)
-  bool ffn_rows = dtype == EM_BF16 && d == 512 && ff % 128 == 0 && ff >= 256 && !(flags & EM_ENC_NO_FUSED) &&
-                  !em_sw().no_ffn_rows && em_rows_fill_ok(M, flags);
+  bool ffn_rows = em_host::rows_ffn_ok(dtype, d, ff, flags, M);
   for (int l = 0; ffn_rows && l < L; ++l) ffn_rows = ly[l].ff_w1p && ly[l].ff_w2p;
 
   EM_TRY(em_layernorm(dtype, x, ly[0].norm1_g, ly[0].norm1_b, M, d, LN_EPS, xn, nullptr, stream));
@@ -146,14 +131,7 @@ extern "C" int em_transformer_encode(int dtype, const EmTransformerWeights* w, c
     const bool last = l + 1 == L;
     // ---- x += linear_out(MHA(norm1(x)))  (xn holds norm1(x))
     if (heads_path) {
-      EmGemmArgs a = {};
-      a.A = xn; a.W = q.wqkv; a.C = qh; a.bias = q.bqkv;
-      a.M = M; a.N = 2 * d; a.K = d; a.lda = d; a.ldc = 64; a.scale = 1.f;
-      a.T1 = T; a.T2 = s.Tpad; a.F1 = h; a.d = d;
-      EM_TRY(em_gemm(dtype, EM_EPI_QK_HEADS, EM_A_PLAIN, &a, stream));
-      a.A = (const unsigned char*)q.wqkv + (size_t)2 * d * d * es; a.W = xn; a.C = vt; a.bias = q.bqkv + 2 * d;
-      a.M = d; a.N = M; a.ldc = s.Tpad;
-      EM_TRY(em_gemm(dtype, EM_EPI_VT_HEADS, EM_A_PLAIN, &a, stream));
+      EM_TRY(em_host::project_heads(dtype, xn, q.wqkv, q.bqkv, qh, vt, M, d, h, T, s.Tpad, stream));
       EM_TRY(em_abs_attention_bf16(qh, kh, vt, olens, B, T, s.Tpad, h, ctx, stream));
     } else {
       EM_TRY(gemm(dtype, EM_EPI_STORE, xn, q.wqkv, big, q.bqkv, M, 3 * d, d, d, 3 * d, 1.f, stream));

@@ -93,6 +93,34 @@ def test_unsupported_choices_raise():
     assert ASRTask.build_model(cfg).encoder.legacy_relpos
 
 
+_EBF_ON = dict(use_ffn=True, macaron_ffn=True)  # the reference defaults of both are False: outside the fast path
+
+
+@pytest.mark.parametrize("cls_name,base,kw,named", [
+    ("EBranchformerEncoder", _EBF_ON, dict(use_ffn=False, macaron_ffn=False), "use_ffn"),  # = the reference defaults
+    ("EBranchformerEncoder", _EBF_ON, dict(gate_activation="swish"), "gate_activation"),
+    ("EBranchformerEncoder", _EBF_ON, dict(input_layer="linear"), "input_layer"),
+    ("EBranchformerEncoder", _EBF_ON, dict(rel_pos_type="legacy", pos_enc_layer_type="abs_pos"), "pos_enc_layer_type"),
+    ("BranchformerEncoder", {}, dict(gate_activation="swish"), "gate_activation"),
+    ("BranchformerEncoder", {}, dict(input_layer="linear"), "input_layer"),
+    ("BranchformerEncoder", {}, dict(rel_pos_type="legacy", pos_enc_layer_type="abs_pos"), "pos_enc_layer_type"),
+    ("BranchformerEncoder", {}, dict(use_cgmlp=False), "use_cgmlp"),
+    ("BranchformerEncoder", {}, dict(merge_method="fixed_ave", cgmlp_weight=1.0), "fixed_ave"),
+])
+def test_branchformer_unsupported_options_equal_the_constructor_message(cls_name, base, kw, named):
+    """`unsupported_options` of the (E-)Branchformer binds its OWN constructor (it used to raise KeyError: 'normalize_before'
+    through the Conformer's option names) and reports exactly the options the constructor refuses."""
+    from espnet_amd.asr.encoder import e_branchformer_encoder as M
+
+    cls = getattr(M, cls_name)
+    assert cls.unsupported_options(80, **base) == []
+    bad = cls.unsupported_options(80, **{**base, **kw})
+    assert any(named in s for s in bad), bad
+    with pytest.raises(NotImplementedError) as ei:
+        cls(80, **{**base, **kw})
+    assert str(ei.value).split(": ", 1)[1].split(", ") == bad
+
+
 def test_lengths_match_oracle():
     import random
 
