@@ -26,13 +26,23 @@ import numpy as np
 import torch
 
 from espnet_amd import lib as L
-from espnet_amd.asr.encoder._contextual_block_base import ContextualBlockEncoderBase
-from espnet_amd.asr.encoder.contextual_block_conformer_encoder import StreamingStepGraph
+from espnet_amd.asr.encoder._contextual_block_base import ContextualBlockEncoderBase, StreamingStepGraph
 from espnet_amd.nets.beam_search import Hypothesis
 from espnet_amd.tasks.asr import ASRTask
 from espnet_amd.text.token_id_converter import TokenIDConverter, build_tokenizer
 
 logger = logging.getLogger(__name__)
+
+
+def _collapse_greedy(frame_ids, last: int, out: List[int], drop) -> int:
+    """Incremental G1 (bin/asr_inference.py:574-575): the per-frame arg-max ids of a call appended to `out`, repeats
+    collapsed - across the seam to the previous call too (`last`: its last frame's id) - and the ids in `drop`
+    (blank, <sos/eos>) left out.  Returns the new `last`."""
+    for t in frame_ids:
+        if t != last and t not in drop:
+            out.append(t)
+        last = t
+    return last
 
 
 class Speech2TextStreaming:
@@ -129,26 +139,56 @@ class Speech2TextStreaming:
             self.beam_search.reset()
 
     # ------------------------------------------------------------------ frontend (:205-293)
+    def _chunk_plan(self, n_all: int, is_final: bool, carried: bool):
+        """The time-axis arithmetic of `apply_frontend` (:205-293) for `n_all` samples at hand (carried buffer + chunk):
+        (zeros to append, samples to process, samples to carry on, frames to drop in front, frames to drop at the end) - the
+        frames that see an artificial chunk edge are trimmed (:261-286).  None: the call only buffers."""
+        pad = 0
+        if n_all <= self.win_length:
+            if not is_final:
+                return None
+            pad = self.win_length - n_all
+        edge = math.ceil(math.ceil(self.win_length / self.hop_length) / 2)
+        front = edge if carried else 0
+        if is_final:
+            return pad, n_all + pad, 0, front, 0
+        n_frames, n_residual = divmod(n_all, self.hop_length)
+        return 0, n_frames * self.hop_length, (edge * 2 - 1) * self.hop_length + n_residual, front, edge
+
+    def _features_device(self, wav: torch.Tensor, front: int, back: int) -> torch.Tensor:
+        """wav (S, n) f32 on the device -> normalised features (S, t, n_mels) without `front` / `back` edge frames
+        (espnet_model.py:450-467)."""
+        m = self.asr_model
+        S, n = wav.shape
+        # (the frame counts of a call are the same call after call: their device copy is made once per (S, n), not with a
+        # pageable host -> device copy in front of every call's launches)
+        key = (S, n, wav.device)
+        fcache = self.__dict__.setdefault("_flens_cache", {})  # (objects assembled without __init__ in the tests)
+        flens_dev = fcache.get(key)
+        if flens_dev is None:
+            if len(fcache) > 64:
+                fcache.clear()
+            flens_dev = fcache[key] = torch.tensor(m.frontend.feature_lengths([n] * S), dtype=torch.int32).to(wav.device)
+            if wav.is_cuda:
+                torch.cuda.current_stream().synchronize()  # (other streams' ticks read it too: batch_call_async)
+        feats = m.frontend.forward_device(wav, flens_dev)
+        if m.normalize is not None:
+            feats = m.normalize.forward_device(feats, flens_dev)
+        return feats.narrow(1, front, feats.size(1) - front - back)
+
     def apply_frontend(self, speech: torch.Tensor, prev_states=None, is_final: bool = False):
         if prev_states is not None:
             speech = torch.cat([prev_states["waveform_buffer"], speech], dim=0)
-        if speech.size(0) <= self.win_length:
-            if is_final:
-                speech = torch.cat([speech, torch.zeros(self.win_length - speech.size(0), dtype=speech.dtype)], dim=0)
-            else:
-                return None, None, {"waveform_buffer": speech.clone()}
-        edge = math.ceil(math.ceil(self.win_length / self.hop_length) / 2)
-        if is_final:
-            speech_to_process, waveform_buffer = speech, None
-        else:
-            n_frames = speech.size(0) // self.hop_length
-            n_residual = speech.size(0) % self.hop_length
-            speech_to_process = speech.narrow(0, 0, n_frames * self.hop_length)
-            keep = (edge * 2 - 1) * self.hop_length + n_residual
-            waveform_buffer = speech.narrow(0, speech.size(0) - keep, keep).clone()
-        # (the chunk through one of two pinned staging rows and an asynchronous copy, the frame count from a per-length cache:
-        # a pageable host -> device copy is synchronous, and there were two of them in front of every call's first launch)
-        n = speech_to_process.size(0)
+        plan = self._chunk_plan(speech.size(0), is_final, prev_states is not None)
+        if plan is None:
+            return None, None, {"waveform_buffer": speech.clone()}
+        pad, n, keep, front, back = plan
+        if pad:
+            speech = torch.cat([speech, torch.zeros(pad, dtype=speech.dtype)], dim=0)
+        speech_to_process = speech.narrow(0, 0, n)
+        waveform_buffer = None if is_final else speech.narrow(0, speech.size(0) - keep, keep).clone()
+        # (the chunk through one of two pinned staging rows and an asynchronous copy: a pageable host -> device copy is
+        # synchronous, and there were two of them in front of every call's first launch)
         if speech_to_process.is_cuda or torch.device(self.device).type != "cuda":
             wav = speech_to_process.unsqueeze(0).to(torch.float32).to(self.device)
         else:
@@ -162,27 +202,7 @@ class Speech2TextStreaming:
             ring[2] += 1
             buf[0].copy_(speech_to_process)
             wav = buf.to(self.device, non_blocking=True)
-        m = self.asr_model
-        key = (1, n, wav.device)
-        fcache = self.__dict__.setdefault("_flens_cache", {})
-        flens_dev = fcache.get(key)
-        if flens_dev is None:
-            if len(fcache) > 64:
-                fcache.clear()
-            flens_dev = fcache[key] = torch.tensor(m.frontend.feature_lengths([n]), dtype=torch.int32).to(wav.device)
-            if wav.is_cuda:
-                torch.cuda.current_stream().synchronize()
-        feats = m.frontend.forward_device(wav, flens_dev)  # espnet_model.py:450-467
-        if m.normalize is not None:
-            feats = m.normalize.forward_device(feats, flens_dev)
-        # trimming of the frames that see the artificial chunk edges (:261-286)
-        if is_final:
-            if prev_states is not None:
-                feats = feats.narrow(1, edge, feats.size(1) - edge)
-        elif prev_states is None:
-            feats = feats.narrow(1, 0, feats.size(1) - edge)
-        else:
-            feats = feats.narrow(1, edge, feats.size(1) - 2 * edge)
+        feats = self._features_device(wav, front, back)
         feats_lengths = torch.full([1], feats.size(1), dtype=torch.long)
         return feats, feats_lengths, (None if is_final else {"waveform_buffer": waveform_buffer})
 
@@ -217,44 +237,14 @@ class Speech2TextStreaming:
         speech = speech.to(self.device, dtype=torch.float32, non_blocking=True)
         if prev_states is not None:
             speech = torch.cat([prev_states["waveform_buffer"], speech], dim=1)
-        n_all = speech.size(1)
-        if n_all <= self.win_length:
-            if is_final:
-                speech = torch.cat([speech, speech.new_zeros(speech.size(0), self.win_length - n_all)], dim=1)
-            else:
-                return None, {"waveform_buffer": speech.clone()}
-        edge = math.ceil(math.ceil(self.win_length / self.hop_length) / 2)
-        if is_final:
-            to_process, waveform_buffer = speech, None
-        else:
-            n_frames = speech.size(1) // self.hop_length
-            n_residual = speech.size(1) % self.hop_length
-            to_process = speech.narrow(1, 0, n_frames * self.hop_length)
-            keep = (edge * 2 - 1) * self.hop_length + n_residual
-            waveform_buffer = speech.narrow(1, speech.size(1) - keep, keep).clone()
-        wav = to_process.contiguous()
-        S, n = wav.shape
-        m = self.asr_model
-        # (the frame counts of a tick are the same tick after tick: their device copy is made once per (S, n), not with a
-        # pageable host -> device copy in front of every tick's launches)
-        key = (S, n, wav.device)
-        flens_dev = self._flens_cache.get(key)
-        if flens_dev is None:
-            if len(self._flens_cache) > 64:
-                self._flens_cache.clear()
-            flens = m.frontend.feature_lengths([n] * S)
-            flens_dev = self._flens_cache[key] = torch.tensor(flens, dtype=torch.int32).to(wav.device)
-            torch.cuda.current_stream().synchronize()  # (other streams' ticks read it too: batch_call_async)
-        feats = m.frontend.forward_device(wav, flens_dev)
-        if m.normalize is not None:
-            feats = m.normalize.forward_device(feats, flens_dev)
-        if is_final:
-            if prev_states is not None:
-                feats = feats.narrow(1, edge, feats.size(1) - edge)
-        elif prev_states is None:
-            feats = feats.narrow(1, 0, feats.size(1) - edge)
-        else:
-            feats = feats.narrow(1, edge, feats.size(1) - 2 * edge)
+        plan = self._chunk_plan(speech.size(1), is_final, prev_states is not None)
+        if plan is None:
+            return None, {"waveform_buffer": speech.clone()}
+        pad, n, keep, front, back = plan
+        if pad:
+            speech = torch.cat([speech, speech.new_zeros(speech.size(0), pad)], dim=1)
+        waveform_buffer = None if is_final else speech.narrow(1, speech.size(1) - keep, keep).clone()
+        feats = self._features_device(speech.narrow(1, 0, n).contiguous(), front, back)
         return feats, (None if is_final else {"waveform_buffer": waveform_buffer})
 
     @torch.no_grad()
@@ -342,10 +332,7 @@ class Speech2TextStreaming:
         """Incremental G1: argmax of the new frames, collapsing repeats across the chunk seam."""
         m = self.asr_model
         ids = m.ctc.argmax(enc.unsqueeze(0), as_int32=True)[0].tolist()
-        for t in ids:
-            if t != self._last_id and t not in (m.blank_id, m.sos, m.eos):
-                self._partial_ids.append(t)
-            self._last_id = t
+        self._last_id = _collapse_greedy(ids, self._last_id, self._partial_ids, (m.blank_id, m.sos, m.eos))
 
     def _results(self, is_final: bool):
         m = self.asr_model
@@ -471,12 +458,7 @@ class PendingTick:
                 self._event.synchronize()
                 drop = (m.blank_id, m.sos, m.eos)
                 for s_, row in enumerate(self._ids_host.tolist()):
-                    last, out = bst["last"][s_], bst["ids"][s_]
-                    for t in row:
-                        if t != last and t not in drop:
-                            out.append(t)
-                        last = t
-                    bst["last"][s_] = last
+                    bst["last"][s_] = _collapse_greedy(row, bst["last"][s_], bst["ids"][s_], drop)
                 self._ids_host = None
             self._res = [list(v) for v in bst["ids"]]
             if bst["pending"] is self:
@@ -583,12 +565,7 @@ class StreamPool:
                 st["frontend"] = self._unstack(fe_next, i)
                 st["encoder"] = self._unstack(en_next, i) if feats is not None else st["encoder"]
                 if ids is not None:
-                    last, out = st["last"], st["ids"]
-                    for t in ids[i]:
-                        if t != last and t not in drop:
-                            out.append(t)
-                        last = t
-                    st["last"] = last
+                    st["last"] = _collapse_greedy(ids[i], st["last"], st["ids"], drop)
         res = {sid: list(self.streams[sid]["ids"]) for sid in chunks}
         for sid, (_, is_final) in chunks.items():
             if is_final:

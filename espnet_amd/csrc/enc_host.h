@@ -4,7 +4,9 @@
 //   - Bump: workspace layouts as one call per slot;
 //   - tpad256 / head_slab_bytes / project_heads / clear_head_slabs: the per-head operand format of the LDS-resident
 //     attention kernels (csrc/attention2.hip, csrc/abs_attn.hip): q, k [B][H][Tpad][64], V^T [B][H][64][Tpad], bf16;
-//   - rows_ffn_ok / head_operands_ok: the two rules that pick the 512-wide models' launch forms.
+//   - rows_ffn_ok / head_operands_ok: the two rules that pick the 512-wide models' launch forms;
+//   - stream_*: what the two streaming launch sequences (streaming.hip, streaming_tf.hip) share - the FFN share rule and
+//     its set-up, the folded / launched context hand-over, the head of the per-operator scratch, LayerNorm + projection.
 #pragma once
 #include <stddef.h>
 
@@ -81,5 +83,90 @@ inline bool rows_ffn_ok(int dtype, int d, int ff, int flags, long M) {
   return dtype == EM_BF16 && d == 512 && ff % 128 == 0 && ff >= 256 && !(flags & EM_ENC_NO_FUSED) && !em_sw().no_ffn_rows &&
          em_rows_fill_ok(M, flags);
 }
+
+// ---- the two contextual-block streaming encoders (csrc/streaming.hip: Conformer layers, csrc/streaming_tf.hip: Transformer
+// layers): the same blocks [n_streams * n_blk_s][L][d] f32, the same FFN launch shape, the same context hand-over.
+
+// Shares of an FFN's hidden dimension per 32-row block in the fused streaming layers (EmBlockArgs.ffn_split, round 6).  A tick
+// of a few streams runs every launch on a few of the chip's 256 CUs, each pushing the whole 2 MiB of an FFN through ONE CU's
+// MFMA pipes (~8 us of a ~20 us launch); S workgroups per row block take 1 / S of it each and meet once (a store, a ticket,
+// the last one sums: 3 - 5 us, growing with S).  Measured per call of 12 Conformer layers (profiles/r06t_stream_split_sweep.txt):
+//   streams (row blocks)   1 (2)   8 (16)   16 (32)   32 (64)   64 (128)
+//   S = 1                  926     941      941       945       946   us
+//   S = 2                  788     807      846       874      1029
+//   S = 4                  720     772      840       996      1430
+//   S = 8                  742     826     1030      1429      2184
+// so: 4 up to 32 row blocks, 2 up to 64, 1 beyond; whole pairs of 64-wide chunks per share.
+// ESPNET_AMD_STREAM_FFN_SPLIT=n: developer switch (1 = off, n = forced).
+inline int stream_ffn_split(int ff, int row_blocks) {
+  const int forced = em_sw().stream_ffn_split;
+  const int pairs = (((ff >> 6) + 1) & ~1) / 2;
+  int S = forced > 0 ? forced : row_blocks <= 32 ? 4 : row_blocks <= 64 ? 2 : 1;
+  if (S > 16) S = 16;
+  while (S > 1 && pairs % S != 0) --S;
+  return S;
+}
+// ... its meeting place behind a fused layout: partial sums [row blocks][S][8192] f32 + one ticket per row block
+inline void stream_ffn_slots(Bump& b, int ff, int row_blocks, size_t* part, size_t* ticket) {
+  const int S = stream_ffn_split(ff, row_blocks);
+  *part = b.take(S > 1 ? (size_t)row_blocks * S * 8192 * 4 : 0);
+  *ticket = b.take(S > 1 ? (size_t)row_blocks * 4 : 0);
+}
+// ... and a call's set-up.  The tickets start at zero and every launch leaves them there.
+inline int stream_ffn_setup(EmBlockArgs& ba, int row_blocks, void* part, void* ticket, void* stream) {
+  const int S = stream_ffn_split(ba.ff, row_blocks);
+  if (S <= 1) return EM_OK;
+  ba.ffn_split = S; ba.ffn_part = (float*)part; ba.ffn_ticket = (int32_t*)ticket;
+  return hipMemsetAsync(ticket, 0, (size_t)row_blocks * 4, (hipStream_t)stream) == hipSuccess ? EM_OK : EM_ERR_LAUNCH;
+}
+
+// One block per stream (the steady-state tick) with both context buffers: the hand-over after layer l is "slot 0 := the
+// previous call's context vector of layer l; this call's := the last slot", so it rides in the fused launches (EmBlockArgs
+// row0_src / last_dst) - a launch less per layer (4.9 us each, 59 of a 32-stream tick's 1 170 us;
+// profiles/r05x_stream_batch32_kernel_stats.csv).  past_ctx == next_ctx: the next layer would read THIS call's vector where it
+// wants the previous call's - the hand-over launch reads before it writes and is safe in place, so an aliased call keeps it
+// (ADVICE r05).  ESPNET_AMD_STREAM_NO_CTX_FOLD: developer A/B switch, read per call (tests/test_gpu_streaming.py compares
+// the two bit for bit).
+inline bool stream_fold_ctx(int mask_mode, int n_blk_s, const float* past_ctx, const float* next_ctx) {
+  return mask_mode && n_blk_s == 1 && past_ctx && next_ctx && past_ctx != next_ctx && !em_sw().stream_no_ctx_fold;
+}
+
+// The hand-over after layer l as its own launch: x[b][0] := the block in front's last slot, or past_ctx[l] for a stream's first
+// block; next_ctx[l] := the last slot of its last block.  past_ctx / next_ctx [n_streams][NL][d].
+inline int stream_hand_over(float* x, const float* past_ctx, float* next_ctx, int l, int n_streams, int n_blk_s, int L, int d,
+                            int NL, void* stream) {
+  return em_cb_propagate_ctx_batch_f32(x, past_ctx ? past_ctx + (size_t)l * d : nullptr,
+                                       next_ctx ? next_ctx + (size_t)l * d : nullptr, n_streams, n_blk_s, L, d, NL * d, stream);
+}
+
+// The per-operator sequences' scratch opens with xn [M][d] (a LayerNorm's output) and big [M][max(ff, 3d)] (an FFN's hidden
+// rows, or q | k | v), in the activation type; `row` = the bytes of one more [M][d] slot (the attention's output, ...).
+struct StreamWsHead { size_t xn, big, row; };
+inline StreamWsHead stream_ws_head(Bump& b, int dtype, int d, int ff, int M) {
+  const size_t es = dtype == EM_BF16 ? 2 : 4;
+  const size_t wide = ff > 3 * d ? ff : 3 * d;
+  StreamWsHead s;
+  s.row = (size_t)M * d * es;
+  s.xn = b.take(s.row);
+  s.big = b.take((size_t)M * wide * es);
+  return s;
+}
+
+// C = epi(LayerNorm(x) W^T + bias) on the f32 blocks x [M][d] of a per-operator sequence.  The pre-norm rides in the prologue
+// of the projection that consumes it (csrc/ln_gemm.hip) where that kernel has the shape: a launch less per projection.  A
+// step is ~200 dependent launches of ~5.6 us for 42 rows - launch latency, nothing else - so the count is what matters
+// (round 3: 1.30 -> see profiles/r03p).  ESPNET_AMD_STREAM_NO_LN_GEMM: developer A/B switch.
+struct StreamLnProj {
+  int dtype, M, d;
+  const float* x;
+  void* xn;  // [M][d] act: the LayerNorm's output where it is a launch of its own
+  void* stream;
+  bool lng = !em_sw().stream_no_ln_gemm && d % 64 == 0 && d <= 1024;
+  int operator()(int epi, const float* g, const float* be, const void* W, const float* bias, void* C, int N) const {
+    if (lng) return em_ln_gemm(dtype, epi, x, g, be, LN_EPS, W, bias, C, M, N, d, N, stream);
+    EM_TRY(em_layernorm(dtype, x, g, be, M, d, LN_EPS, xn, nullptr, stream));
+    return gemm(dtype, epi, xn, W, C, bias, M, N, d, d, N, 1.f, stream);
+  }
+};
 
 }  // namespace em_host

@@ -422,40 +422,19 @@ struct CbWs {
   int Tpad;
 };
 inline CbWs cb_layout(int dtype, const EmConformerWeights* w, int M) {
-  const size_t es = dtype == EM_BF16 ? 2 : 4;
-  const size_t d = w->d;
-  const size_t wide = (size_t)w->ff > 3 * d ? w->ff : 3 * d;
   CbWs s;
   em_host::Bump b;
-  s.xn = b.take((size_t)M * d * es);
-  s.big = b.take((size_t)M * wide * es);
-  s.g = b.take((size_t)M * d * es);
-  s.g2 = b.take((size_t)M * d * es);
-  s.ctx = b.take((size_t)M * d * es);
+  const em_host::StreamWsHead h = em_host::stream_ws_head(b, dtype, w->d, w->ff, M);
+  s.xn = h.xn;
+  s.big = h.big;
+  s.g = b.take(h.row);
+  s.g2 = b.take(h.row);
+  s.ctx = b.take(h.row);
   s.total = b.o;
   return s;
 }
 // ... plus the per-head operands of the fused layer (bf16, d = 256: csrc/block.hip): q / k [n_blk][4][Tpad][64],
-// V^T [n_blk][4][64][Tpad] with Tpad = the 32-row workgroups' reach
-// Shares of an FFN's hidden dimension per 32-row block in the fused streaming layers (EmBlockArgs.ffn_split, round 6).  A tick
-// of a few streams runs every launch on a few of the chip's 256 CUs, each pushing the whole 2 MiB of an FFN through ONE CU's
-// MFMA pipes (~8 us of a ~20 us launch); S workgroups per row block take 1 / S of it each and meet once (a store, a ticket,
-// the last one sums: 3 - 5 us, growing with S).  Measured per call of 12 layers (profiles/r06t_stream_split_sweep.txt):
-//   streams (row blocks)   1 (2)   8 (16)   16 (32)   32 (64)   64 (128)
-//   S = 1                  926     941      941       945       946   us
-//   S = 2                  788     807      846       874      1029
-//   S = 4                  720     772      840       996      1430
-//   S = 8                  742     826     1030      1429      2184
-// so: 4 up to 32 row blocks, 2 up to 64, 1 beyond; whole pairs of 64-wide chunks per share.
-// ESPNET_AMD_STREAM_FFN_SPLIT=n: developer switch (1 = off, n = forced).
-inline int cb_ffn_split(const EmConformerWeights* w, int row_blocks) {
-  const int forced = em_sw().stream_ffn_split;
-  const int pairs = (((w->ff >> 6) + 1) & ~1) / 2;
-  int S = forced > 0 ? forced : row_blocks <= 32 ? 4 : row_blocks <= 64 ? 2 : 1;
-  if (S > 16) S = 16;
-  while (S > 1 && pairs % S != 0) --S;
-  return S;
-}
+// V^T [n_blk][4][64][Tpad] with Tpad = the 32-row workgroups' reach, and the split FFN's meeting place (em_host::stream_ffn_split)
 inline CbWs cb_layout_fused(int dtype, const EmConformerWeights* w, int n_blk, int L) {
   CbWs s = cb_layout(dtype, w, n_blk * L);
   s.Tpad = (L + 63) / 64 * 64;
@@ -464,10 +443,7 @@ inline CbWs cb_layout_fused(int dtype, const EmConformerWeights* w, int n_blk, i
   s.qh = b.take(per_head);
   s.kh = b.take(per_head);
   s.vt = b.take(per_head);
-  // split FFN of the row-block launches (round 6, EmBlockArgs.ffn_split): partial sums [row blocks][S][8192] f32 + tickets
-  const int nrb = n_blk * ((L + 31) / 32), S = cb_ffn_split(w, nrb);
-  s.part = b.take(S > 1 ? (size_t)nrb * S * 8192 * 4 : 0);
-  s.ticket = b.take(S > 1 ? (size_t)nrb * 4 : 0);
+  em_host::stream_ffn_slots(b, w->ff, n_blk * ((L + 31) / 32), &s.part, &s.ticket);
   s.total = b.o;
   return s;
 }
@@ -477,7 +453,7 @@ inline CbWs cb_layout_fused(int dtype, const EmConformerWeights* w, int n_blk, i
 // weights through one CU, and with one block (one stream, one call) that was two workgroups on an otherwise empty chip - 1.47 ms
 // per call against 1.15 for the per-operator sequence, whose GEMMs spread every weight matrix over a hundred CUs
 // (profiles/r04i_stream_fused_ab.txt; equal in round 5 with the helper workgroups).  Round 6: with each FFN dealt to four
-// workgroups per row block (cb_ffn_split) the fused layers win from one block on - 720 us against 870 per call
+// workgroups per row block (em_host::stream_ffn_split) the fused layers win from one block on - 720 us against 870 per call
 // (profiles/r06t_stream_split_sweep.txt) - and the floor is gone.  ESPNET_AMD_STREAM_FUSED_MIN=n: developer A/B switch.
 inline bool cb_fusable(int dtype, const EmConformerWeights* w, int L, int n_blk) {
   const bool off = em_sw().stream_no_fused;  // developer A/B switch
@@ -496,55 +472,40 @@ inline bool cb_fusable(int dtype, const EmConformerWeights* w, int L, int n_blk)
 
 }  // namespace
 
+// The one launch behind the three em_cb_build_blocks_* entries: grid (n_blk, n_streams); the block count of stream s is
+// n_proc_dev[s * np_stride] where n_proc_dev is given (stride 0: one count on the device for the call), n_proc otherwise.
+static int cb_build_blocks(const float* xs, const float* pe, const float* prev_addin, int n_proc, const int32_t* n_proc_dev,
+                           int np_stride, int n_streams, int n_blk, int total, int bs, int hs, int d, float* x,
+                           float* addin_out, void* stream) {
+  if (!xs || !pe || !x || !addin_out || n_streams <= 0 || n_blk <= 0 || total <= 0 || bs <= 0 || hs <= 0 || d <= 0)
+    return EM_ERR_BAD_ARG;
+  if ((n_blk - 1) * hs >= total) return EM_ERR_BAD_ARG;  // every block holds at least one frame
+  const auto kernel = (d % 4 == 0 && d <= 1024) ? cb_build_blocks_kernel : cb_build_blocks_kernel_v1;
+  hipLaunchKernelGGL(kernel, dim3(n_blk, n_streams), dim3(256), 0, (hipStream_t)stream, xs, pe, prev_addin, n_proc,
+                     (const int*)n_proc_dev, np_stride, total, bs, hs, d, sqrtf((float)d), x, addin_out);
+  EM_CHECK_LAUNCH();
+  return EM_OK;
+}
+
 extern "C" int em_cb_build_blocks_f32(const float* xs, const float* pe, const float* prev_addin,
                                       int32_t n_proc, const int32_t* n_proc_dev, int32_t n_blk,
                                       int32_t total, int32_t bs,
                                       int32_t hs, int32_t d, float* x, float* addin_out,
                                       void* stream) {
-  if (!xs || !pe || !x || !addin_out || n_blk <= 0 || total <= 0 || bs <= 0 || hs <= 0 || d <= 0)
-    return EM_ERR_BAD_ARG;
-  if ((n_blk - 1) * hs >= total) return EM_ERR_BAD_ARG;  // every block holds at least one frame
-  if (d % 4 == 0 && d <= 1024)
-    hipLaunchKernelGGL(cb_build_blocks_kernel, dim3(n_blk), dim3(256), 0, (hipStream_t)stream, xs, pe,
-                     prev_addin, n_proc, n_proc_dev, 0, total, bs, hs, d, sqrtf((float)d), x, addin_out);
-  else
-    hipLaunchKernelGGL(cb_build_blocks_kernel_v1, dim3(n_blk), dim3(256), 0, (hipStream_t)stream, xs, pe,
-                     prev_addin, n_proc, n_proc_dev, 0, total, bs, hs, d, sqrtf((float)d), x, addin_out);
-  EM_CHECK_LAUNCH();
-  return EM_OK;
+  return cb_build_blocks(xs, pe, prev_addin, n_proc, n_proc_dev, 0, 1, n_blk, total, bs, hs, d, x, addin_out, stream);
 }
 
 extern "C" int em_cb_build_blocks_batch_f32(const float* xs, const float* pe, const float* prev_addin, int32_t n_proc,
                                             int32_t n_streams, int32_t n_blk, int32_t total, int32_t bs, int32_t hs,
                                             int32_t d, float* x, float* addin_out, void* stream) {
-  if (!xs || !pe || !x || !addin_out || n_streams <= 0 || n_blk <= 0 || total <= 0 || bs <= 0 || hs <= 0 || d <= 0)
-    return EM_ERR_BAD_ARG;
-  if ((n_blk - 1) * hs >= total) return EM_ERR_BAD_ARG;  // every block holds at least one frame
-  if (d % 4 == 0 && d <= 1024)
-    hipLaunchKernelGGL(cb_build_blocks_kernel, dim3(n_blk, n_streams), dim3(256), 0, (hipStream_t)stream, xs, pe,
-                     prev_addin, n_proc, (const int*)nullptr, 0, total, bs, hs, d, sqrtf((float)d), x, addin_out);
-  else
-    hipLaunchKernelGGL(cb_build_blocks_kernel_v1, dim3(n_blk, n_streams), dim3(256), 0, (hipStream_t)stream, xs, pe,
-                     prev_addin, n_proc, (const int*)nullptr, 0, total, bs, hs, d, sqrtf((float)d), x, addin_out);
-  EM_CHECK_LAUNCH();
-  return EM_OK;
+  return cb_build_blocks(xs, pe, prev_addin, n_proc, nullptr, 0, n_streams, n_blk, total, bs, hs, d, x, addin_out, stream);
 }
 
 extern "C" int em_cb_build_blocks_rows_f32(const float* xs, const float* pe, const float* prev_addin,
                                            const int32_t* n_proc_rows, int32_t n_streams, int32_t n_blk, int32_t total,
                                            int32_t bs, int32_t hs, int32_t d, float* x, float* addin_out, void* stream) {
-  if (!xs || !pe || !x || !addin_out || !n_proc_rows || n_streams <= 0 || n_blk <= 0 || total <= 0 || bs <= 0 ||
-      hs <= 0 || d <= 0)
-    return EM_ERR_BAD_ARG;
-  if ((n_blk - 1) * hs >= total) return EM_ERR_BAD_ARG;  // every block holds at least one frame
-  if (d % 4 == 0 && d <= 1024)
-    hipLaunchKernelGGL(cb_build_blocks_kernel, dim3(n_blk, n_streams), dim3(256), 0, (hipStream_t)stream, xs, pe,
-                     prev_addin, 0, n_proc_rows, 1, total, bs, hs, d, sqrtf((float)d), x, addin_out);
-  else
-    hipLaunchKernelGGL(cb_build_blocks_kernel_v1, dim3(n_blk, n_streams), dim3(256), 0, (hipStream_t)stream, xs, pe,
-                     prev_addin, 0, n_proc_rows, 1, total, bs, hs, d, sqrtf((float)d), x, addin_out);
-  EM_CHECK_LAUNCH();
-  return EM_OK;
+  if (!n_proc_rows) return EM_ERR_BAD_ARG;
+  return cb_build_blocks(xs, pe, prev_addin, 0, n_proc_rows, 1, n_streams, n_blk, total, bs, hs, d, x, addin_out, stream);
 }
 
 extern "C" int em_stream_pos_enc_f32(const float* xs, const float* pe, int32_t start, int32_t n,
@@ -576,24 +537,26 @@ extern "C" int em_block_mha(int dtype, const void* qkv, int32_t n_blk, int32_t L
   return EM_OK;
 }
 
-extern "C" int em_cb_propagate_ctx_f32(float* x, const float* past_ctx, float* next_ctx,
-                                       int32_t n_blk, int32_t L, int32_t d, void* stream) {
-  if (!x || n_blk <= 0 || L < 2 || d <= 0) return EM_ERR_BAD_ARG;
-  hipLaunchKernelGGL(cb_propagate_ctx_kernel, dim3(n_blk), dim3(256), 0, (hipStream_t)stream, x,
-                     past_ctx, next_ctx, n_blk, L, d, 0);
-  EM_CHECK_LAUNCH();
-  return EM_OK;
-}
-
-// The same for n_streams lock-step streams of n_blk blocks each: x [n_streams][n_blk][L][d], the context vectors of stream s at
-// past_ctx / next_ctx + s * ctx_stride floats (the launch em_cb_encode_blocks_batch makes between layers; csrc/streaming_tf.hip)
-extern "C" int em_cb_propagate_ctx_batch_f32(float* x, const float* past_ctx, float* next_ctx, int32_t n_streams,
-                                             int32_t n_blk, int32_t L, int32_t d, int32_t ctx_stride, void* stream) {
+// x [n_streams][n_blk][L][d], the context vectors of stream s at past_ctx / next_ctx + s * ctx_stride floats
+static int cb_propagate_ctx(float* x, const float* past_ctx, float* next_ctx, int n_streams, int n_blk, int L, int d,
+                            int ctx_stride, void* stream) {
   if (!x || n_streams <= 0 || n_blk <= 0 || L < 2 || d <= 0 || ctx_stride < 0) return EM_ERR_BAD_ARG;
   hipLaunchKernelGGL(cb_propagate_ctx_kernel, dim3(n_blk, n_streams), dim3(256), 0, (hipStream_t)stream, x, past_ctx, next_ctx,
                      n_blk, L, d, ctx_stride);
   EM_CHECK_LAUNCH();
   return EM_OK;
+}
+
+extern "C" int em_cb_propagate_ctx_f32(float* x, const float* past_ctx, float* next_ctx,
+                                       int32_t n_blk, int32_t L, int32_t d, void* stream) {
+  return cb_propagate_ctx(x, past_ctx, next_ctx, 1, n_blk, L, d, 0, stream);
+}
+
+// The same for n_streams lock-step streams of n_blk blocks each (the launch both encoders make between layers:
+// em_host::stream_hand_over)
+extern "C" int em_cb_propagate_ctx_batch_f32(float* x, const float* past_ctx, float* next_ctx, int32_t n_streams,
+                                             int32_t n_blk, int32_t L, int32_t d, int32_t ctx_stride, void* stream) {
+  return cb_propagate_ctx(x, past_ctx, next_ctx, n_streams, n_blk, L, d, ctx_stride, stream);
 }
 
 extern "C" size_t em_cb_workspace_bytes(int dtype, const EmConformerWeights* w, int32_t n_blk,
@@ -630,8 +593,9 @@ static int cb_encode_blocks_impl(int dtype, const EmConformerWeights* w, float* 
     //                          linear_out + residual, norm_conv, pointwise_conv1 + GLU   (rounds 4 - 5: cb_mha_heads + block<C>)
     //   block<D | RELU>        depthwise conv (k = 15) + BN + Swish, pointwise_conv2 + residual, norm_ff, FFN, norm_final
     //   (propagate_ctx: the context hand-over between blocks, why D and the next layer's A stay separate launches; with one
-    //   block per stream and call it is folded into A and D: fold_ctx below)
-    // On a chip the launch does not fill, the FFNs of A and D are dealt to 2 - 4 workgroups per row block (cb_ffn_split).
+    //   block per stream and call it is folded into A and D: em_host::stream_fold_ctx)
+    // On a chip the launch does not fill, the FFNs of A and D are dealt to 2 - 4 workgroups per row block
+    // (em_host::stream_ffn_split; csrc/block.hip, "the S shares of this row block meet").
     // contextual_block_encoder_layer.py:197-310.  One stream, one block: 1.18 ms (round 4) -> 0.64 ms per call of 12 layers.
     EmBlockArgs ba = {};
     ba.B = n_blk; ba.T = L; ba.Tpad = s.Tpad; ba.d = d; ba.ff = ff; ba.kernel = w->kernel; ba.eps = LN_EPS;
@@ -642,23 +606,11 @@ static int cb_encode_blocks_impl(int dtype, const EmConformerWeights* w, float* 
     // ESPNET_AMD_STREAM_SPLIT_ATT: developer A/B switch - the attention launch of rounds 4 - 5 (bit for bit the same rows)
     const bool att_c = !mha_v1 && !em_sw().stream_split_att;
     ba.att_mask = mask_mode;
-    // One block per stream (the steady-state tick): the hand-over after layer l is "slot 0 := the previous call's context
-    // vector of layer l; this call's := the last slot" - block<A> of layer l + 1 reads its slot 0 from past_ctx and
-    // block<D> of layer l writes its last slot to next_ctx as well: twelve launches less per call (4.9 us each, 59 of a
-    // 32-stream tick's 1 170 us; profiles/r05x_stream_batch32_kernel_stats.csv).  What x[.][0] holds after the LAST layer
-    // is never read (slot 0 is not an output frame).  ESPNET_AMD_STREAM_NO_CTX_FOLD: developer A/B switch (read per call:
-    // tests/test_gpu_streaming.py compares the two bit for bit).
-    // (past_ctx == next_ctx: layer l + 1 would read THIS call's vector where it wants the previous call's - the hand-over launch reads
-    // before it writes and is safe in place, so an aliased call keeps it)
-    const bool fold_ctx = mask_mode && n_blk_s == 1 && past_ctx && next_ctx && past_ctx != next_ctx && !em_sw().stream_no_ctx_fold;
+    // folded hand-over: block<A> of layer l + 1 reads its slot 0 from past_ctx and block<D> of layer l writes its last slot to
+    // next_ctx as well.  What x[.][0] holds after the LAST layer is never read (slot 0 is not an output frame).
+    const bool fold_ctx = em_host::stream_fold_ctx(mask_mode, n_blk_s, past_ctx, next_ctx);
     ba.row_stride = NL * d;
-    // Round 6: a tick that leaves CUs idle deals each FFN's hidden dimension to S workgroups per row block (cb_ffn_split;
-    // csrc/block.hip, "the S shares of this row block meet").  The tickets start at zero and every launch leaves them there.
-    const int ffn_s = cb_ffn_split(w, n_blk * ((L + 31) / 32));
-    if (ffn_s > 1) {
-      ba.ffn_split = ffn_s; ba.ffn_part = (float*)(ws + s.part); ba.ffn_ticket = (int32_t*)(ws + s.ticket);
-      if (hipMemsetAsync(ba.ffn_ticket, 0, (size_t)n_blk * ((L + 31) / 32) * 4, (hipStream_t)stream) != hipSuccess) return EM_ERR_LAUNCH;
-    }
+    EM_TRY(em_host::stream_ffn_setup(ba, n_blk * ((L + 31) / 32), ws + s.part, ws + s.ticket, stream));
     for (int l = 0; l < NL; ++l) {
       const EmConformerLayer& q = w->layers[l];
       ba.ffm_w1 = q.ffm_w1p; ba.ffm_w2 = q.ffm_w2p; ba.wqkv = q.wqkvp; ba.ffm_b1g = q.ffm_b1; ba.params = q.fp_a;
@@ -684,26 +636,11 @@ static int cb_encode_blocks_impl(int dtype, const EmConformerWeights* w, float* 
       ba.last_dst = fold_ctx ? next_ctx + (size_t)l * d : nullptr;
       EM_TRY(em_conformer_block_fused(EM_BLOCK_D | EM_BLOCK_RELU, &ba, stream));
       ba.last_dst = nullptr;
-      if (mask_mode && !fold_ctx) {
-        hipLaunchKernelGGL(cb_propagate_ctx_kernel, dim3(n_blk_s, n_streams), dim3(256), 0, (hipStream_t)stream, x,
-                           past_ctx ? past_ctx + (size_t)l * d : nullptr, next_ctx ? next_ctx + (size_t)l * d : nullptr,
-                           n_blk_s, L, d, NL * d);
-        EM_CHECK_LAUNCH();
-      }
+      if (mask_mode && !fold_ctx) EM_TRY(em_host::stream_hand_over(x, past_ctx, next_ctx, l, n_streams, n_blk_s, L, d, NL, stream));
     }
     return EM_OK;
   }
-  // A pre-norm LayerNorm rides in the prologue of the projection that consumes it (csrc/ln_gemm.hip) where that kernel
-  // has the epilogue (plain / ReLU): three launches less per layer.  A step is ~200 dependent launches of ~5.6 us for
-  // 42 rows - launch latency, nothing else - so the count is what matters (round 3: 1.30 -> see profiles/r03p).
-  const bool no_lng = em_sw().stream_no_ln_gemm;  // developer A/B switch
-  const bool lng = !no_lng && d % 64 == 0 && d <= 1024;
-  auto ln_proj = [&](int epi, const float* g, const float* be, const void* W, const float* bias, void* C, int N) {
-    if (lng) return em_ln_gemm(dtype, epi, x, g, be, LN_EPS, W, bias, C, M, N, d, N, stream);
-    int rc = em_layernorm(dtype, x, g, be, M, d, LN_EPS, xn, nullptr, stream);
-    if (rc != EM_OK) return rc;
-    return gemm(dtype, epi, xn, W, C, bias, M, N, d, d, N, 1.f, stream);
-  };
+  const em_host::StreamLnProj ln_proj{dtype, M, d, x, xn, stream};  // (three launches less per layer where the pre-norm rides in the projection)
   for (int l = 0; l < NL; ++l) {
     const EmConformerLayer& q = w->layers[l];
     EM_TRY(ln_proj(EM_EPI_RELU, q.norm_ff_mac_g, q.norm_ff_mac_b, q.ffm_w1, q.ffm_b1, big, ff));
@@ -718,12 +655,7 @@ static int cb_encode_blocks_impl(int dtype, const EmConformerWeights* w, float* 
     EM_TRY(ln_proj(EM_EPI_RELU, q.norm_ff_g, q.norm_ff_b, q.ff_w1, q.ff_b1, big, ff));
     EM_TRY(gemm(dtype, EM_EPI_RESID_F32, big, q.ff_w2, x, q.ff_b2, M, d, ff, ff, d, 0.5f, stream));
     EM_TRY(em_layernorm_inplace_f32(x, q.norm_final_g, q.norm_final_b, M, d, LN_EPS, stream));
-    if (mask_mode) {
-      hipLaunchKernelGGL(cb_propagate_ctx_kernel, dim3(n_blk_s, n_streams), dim3(256), 0, (hipStream_t)stream, x,
-                         past_ctx ? past_ctx + (size_t)l * d : nullptr, next_ctx ? next_ctx + (size_t)l * d : nullptr,
-                         n_blk_s, L, d, NL * d);
-      EM_CHECK_LAUNCH();
-    }
+    if (mask_mode) EM_TRY(em_host::stream_hand_over(x, past_ctx, next_ctx, l, n_streams, n_blk_s, L, d, NL, stream));
   }
   return EM_OK;
 }

@@ -30,38 +30,24 @@ struct Ws {
   int Tpad;
 };
 inline Ws layout(int dtype, const EmTransformerWeights* w, int M) {
-  const size_t es = dtype == EM_BF16 ? 2 : 4;
-  const size_t d = w->d;
-  const size_t wide = (size_t)w->ff > 3 * d ? w->ff : 3 * d;
   Ws s = {};
   em_host::Bump b;
-  s.xn = b.take((size_t)M * d * es);
-  s.big = b.take((size_t)M * wide * es);
-  s.ctx = b.take((size_t)M * d * es);
+  const em_host::StreamWsHead h = em_host::stream_ws_head(b, dtype, w->d, w->ff, M);
+  s.xn = h.xn;
+  s.big = h.big;
+  s.ctx = b.take(h.row);
   s.total = b.o;
   return s;
 }
-// Shares of the FFN's hidden dimension per 32-row block: the rule csrc/streaming.hip measured for the Conformer layer's FFNs
-// (cb_ffn_split: 4 up to 32 row blocks, 2 up to 64, 1 beyond; ESPNET_AMD_STREAM_FFN_SPLIT forces it) - the same FFN, the
-// same launch shape.
-inline int ffn_split(const EmTransformerWeights* w, int row_blocks) {
-  const int forced = em_sw().stream_ffn_split;
-  const int pairs = (((w->ff >> 6) + 1) & ~1) / 2;
-  int S = forced > 0 ? forced : row_blocks <= 32 ? 4 : row_blocks <= 64 ? 2 : 1;
-  if (S > 16) S = 16;
-  while (S > 1 && pairs % S != 0) --S;
-  return S;
-}
 // The fused path keeps nothing of the per-operator scratch: per-head operands (bf16, two sets) + the split FFN's meeting place
+// (em_host::stream_ffn_split: the rule measured for the Conformer layer's FFNs - the same FFN, the same launch shape)
 inline Ws layout_fused(const EmTransformerWeights* w, int n_blk, int L) {
   Ws s = {};
   s.Tpad = (L + 63) / 64 * 64;
   s.per_head = align_up((size_t)n_blk * w->d * s.Tpad * 2);
   em_host::Bump b;
   for (int i = 0; i < 2; ++i) s.qkv[i] = b.take(3 * s.per_head);
-  const int nrb = n_blk * ((L + 31) / 32), S = ffn_split(w, nrb);
-  s.part = b.take(S > 1 ? (size_t)nrb * S * 8192 * 4 : 0);
-  s.ticket = b.take(S > 1 ? (size_t)nrb * 4 : 0);
+  em_host::stream_ffn_slots(b, w->ff, n_blk * ((L + 31) / 32), &s.part, &s.ticket);
   s.total = b.o;
   return s;
 }
@@ -77,12 +63,7 @@ inline bool fusable(int dtype, const EmTransformerWeights* w, int L, int n_blk) 
   }
   return true;
 }
-// One block per stream with both context buffers: the hand-over rides in the launches (row0_src / last_dst).  An aliased
-// call (past_ctx == next_ctx) keeps the hand-over launch, which reads before it writes.
-inline bool fold_ctx(int mask_mode, int n_blk_s, const float* past_ctx, const float* next_ctx) {
-  return mask_mode && n_blk_s == 1 && past_ctx && next_ctx && past_ctx != next_ctx && !em_sw().stream_no_ctx_fold;
-}
-// ... and then layer l's block<ATT|T> may take layer l + 1's block<Q> into its launch (num_blocks + 1 launches per call).
+// With the hand-over folded into the launches (em_host::stream_fold_ctx), layer l's block<ATT|T> may take layer l + 1's block<Q> into its launch (num_blocks + 1 launches per call).
 // ESPNET_AMD_STREAM_TF_MERGE: developer A/B switch (1 on, 0 off); DESIGN.md 4k has what each form measured.
 inline bool merge_default() { return true; }
 inline bool merged(bool fold) {
@@ -101,25 +82,15 @@ int encode_impl(int dtype, const EmTransformerWeights* w, float* x, int32_t n_st
   const int d = w->d, h = w->heads, ff = w->ff, NL = w->num_blocks, M = n_blk * L;
   if (d % 64 != 0 || ff % 64 != 0 || h <= 0 || d % h != 0 || (d / h != 64 && d / h != 32) || L > 64) return EM_ERR_UNSUPPORTED;
   unsigned char* ws = (unsigned char*)workspace;
-  // the hand-over as its own launch: x[b][0] := the block in front's last slot / past_ctx[l]; next_ctx[l] := the last slot
-  auto propagate = [&](int l) -> int {
-    int rc = em_cb_propagate_ctx_batch_f32(x, past_ctx ? past_ctx + (size_t)l * d : nullptr,
-                                           next_ctx ? next_ctx + (size_t)l * d : nullptr, n_streams, n_blk_s, L, d, NL * d,
-                                           stream);
-    return rc;
-  };
+  auto propagate = [&](int l) { return em_host::stream_hand_over(x, past_ctx, next_ctx, l, n_streams, n_blk_s, L, d, NL, stream); };
   if (fusable(dtype, w, L, n_blk)) {
     const Ws s = layout_fused(w, n_blk, L);
     if (workspace_bytes < s.total) return EM_ERR_WORKSPACE;
-    const bool fold = fold_ctx(mask_mode, n_blk_s, past_ctx, next_ctx), merge = merged(fold);
+    const bool fold = em_host::stream_fold_ctx(mask_mode, n_blk_s, past_ctx, next_ctx), merge = merged(fold);
     EmBlockArgs ba = {};
     ba.B = n_blk; ba.T = L; ba.Tpad = s.Tpad; ba.d = d; ba.ff = ff; ba.kernel = 0; ba.eps = LN_EPS;
     ba.x = x; ba.att_mask = mask_mode; ba.row_stride = NL * d;
-    const int ffn_s = ffn_split(w, n_blk * ((L + 31) / 32));
-    if (ffn_s > 1) {  // (the tickets start at zero and every launch leaves them there)
-      ba.ffn_split = ffn_s; ba.ffn_part = (float*)(ws + s.part); ba.ffn_ticket = (int32_t*)(ws + s.ticket);
-      if (hipMemsetAsync(ba.ffn_ticket, 0, (size_t)n_blk * ((L + 31) / 32) * 4, (hipStream_t)stream) != hipSuccess) return EM_ERR_LAUNCH;
-    }
+    EM_TRY(em_host::stream_ffn_setup(ba, n_blk * ((L + 31) / 32), ws + s.part, ws + s.ticket, stream));
     auto set_qkv = [&](int set, bool out) {
       unsigned char* p = ws + s.qkv[set];
       if (out) { ba.qh_out = p; ba.kh_out = p + s.per_head; ba.vt_out = p + 2 * s.per_head; }
@@ -157,13 +128,7 @@ int encode_impl(int dtype, const EmTransformerWeights* w, float* x, int32_t n_st
   const Ws s = layout(dtype, w, M);
   if (workspace_bytes < s.total) return EM_ERR_WORKSPACE;
   void *xn = ws + s.xn, *big = ws + s.big, *ctx = ws + s.ctx;
-  const bool lng = !em_sw().stream_no_ln_gemm && d % 64 == 0 && d <= 1024;  // (the pre-norm in the projection's prologue, csrc/ln_gemm.hip)
-  auto ln_proj = [&](int epi, const float* g, const float* be, const void* W, const float* bias, void* C, int N) {
-    if (lng) return em_ln_gemm(dtype, epi, x, g, be, LN_EPS, W, bias, C, M, N, d, N, stream);
-    int rc = em_layernorm(dtype, x, g, be, M, d, LN_EPS, xn, nullptr, stream);
-    if (rc != EM_OK) return rc;
-    return gemm(dtype, epi, xn, W, C, bias, M, N, d, d, N, 1.f, stream);
-  };
+  const em_host::StreamLnProj ln_proj{dtype, M, d, x, xn, stream};
   for (int l = 0; l < NL; ++l) {
     const EmTransformerLayer& q = w->layers[l];
     EM_TRY(ln_proj(EM_EPI_STORE, q.norm1_g, q.norm1_b, q.wqkv, q.bqkv, big, 3 * d));

@@ -89,12 +89,16 @@ def test_online_host_control_flow_matches_reference_per_call(name):
     assert bs.running is None and bs.n_enc == 0 and bs.ended_hyps == []
 
 
-@pytest.mark.parametrize("name", ["stream_frontend_gmvn", "stream_frontend_umvn"])
-def test_streaming_apply_frontend_host_logic_on_cpu(name):
+@pytest.mark.parametrize("name,streams", [("stream_frontend_gmvn", 1), ("stream_frontend_umvn", 1),
+                                          ("stream_frontend_gmvn", 2), ("stream_frontend_umvn", 2)],
+                         ids=["stream_frontend_gmvn", "stream_frontend_umvn", "stream_frontend_gmvn-batch2",
+                              "stream_frontend_umvn-batch2"])
+def test_streaming_apply_frontend_host_logic_on_cpu(name, streams):
     """Speech2TextStreaming.apply_frontend's HOST side (waveform overlap buffer, residual samples, trimming of the
     frames that see artificial chunk edges, asr_inference_streaming.py:205-293) with the feature extraction
     stubbed by the CPU oracle: per-call frame counts and values equal the reference's.  (The same test with the
-    HIP frontend is tests/test_gpu_streaming.py.)"""
+    HIP frontend is tests/test_gpu_streaming.py.)  `streams` = 2: `apply_frontend_batch` fed the same chunk in both rows
+    gives the same per-call frame counts, and each row equals what the single entry returns, bit for bit."""
     import types
 
     import numpy as np
@@ -114,7 +118,7 @@ def test_streaming_apply_frontend_host_logic_on_cpu(name):
             return stft_frame_lengths(ns, fc["n_fft"], fc["hop_length"])
 
         def forward_device(self, wav, flens_dev, wlens_dev=None):
-            f, _ = oc.frontend_feats(wav, torch.tensor([wav.size(1)]), mel, fc["n_fft"], fc["win_length"],
+            f, _ = oc.frontend_feats(wav, torch.tensor([wav.size(1)] * wav.size(0)), mel, fc["n_fft"], fc["win_length"],
                                      fc["hop_length"])
             return f
 
@@ -141,3 +145,18 @@ def test_streaming_apply_frontend_host_logic_on_cpu(name):
         pos = nxt
     assert lens == z["feat_lens"].tolist()
     np.testing.assert_allclose(torch.cat(feats, 0).numpy(), z["feats"], atol=3e-4, rtol=0)
+    if streams > 1:
+        single, feats, lens, state, pos = feats, [], [], None, 0
+        while pos < n:
+            nxt = min(n, pos + cs)
+            f, state = s2t.apply_frontend_batch(wav[pos:nxt].expand(streams, -1), state, is_final=(nxt == n))
+            lens.append(-1 if f is None else int(f.size(1)))
+            if f is not None:
+                assert f.size(0) == streams
+                feats.append(f)
+            pos = nxt
+        assert lens == z["feat_lens"].tolist()
+        assert len(feats) == len(single)
+        for f, want in zip(feats, single):
+            for row in f:
+                assert torch.equal(row, want)

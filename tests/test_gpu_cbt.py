@@ -203,7 +203,7 @@ def test_hand_over_in_the_launches_equals_its_own_launch():
 
 @pytest.mark.parametrize("name,dtype", [("recipe", "bfloat16"), ("tiny", "float32")])
 def test_step_graph_replay_equals_eager(name, dtype):
-    from espnet_amd.asr.encoder.contextual_block_conformer_encoder import StreamingStepGraph
+    from espnet_amd.asr.encoder._contextual_block_base import StreamingStepGraph
 
     enc, _ = build(name, dtype)
     feats = _feats(2).cuda()

@@ -130,7 +130,7 @@ def test_block_mha_kernel():
 def test_streaming_step_hipgraph_replay_equals_eager():
     """BASELINE config 5: the steady-state chunk step replayed from a hipGraph gives exactly the
     eager results (same kernels, same data), including across the eager -> graph -> final hand-over."""
-    from espnet_amd.asr.encoder.contextual_block_conformer_encoder import StreamingStepGraph
+    from espnet_amd.asr.encoder._contextual_block_base import StreamingStepGraph
 
     g = load_stream_golden("stream_small_6s")
     feats = stream_feats(int(g["utt_id"]), int(g["n_samples"])).cuda()
@@ -281,7 +281,7 @@ def test_batch_of_streams(name, dtype, atol):
 def test_batch_tick_context_hand_over_in_the_block_launches_equals_its_own_launch():
     """Round 5: with one block per stream and call, the fused streaming layer takes the context hand-over between layers
     (contextual_block_encoder_layer.py:292-304) into the launches either side of it - block<A> reads slot 0 from the
-    previous call's context vectors, block<D> writes the last slot to this call's (csrc/streaming.hip `fold_ctx`,
+    previous call's context vectors, block<D> writes the last slot to this call's (csrc/enc_host.h `stream_fold_ctx`,
     EmBlockArgs.row0_src / last_dst) - instead of a launch per layer that copies them.  Only WHERE rows are read and
     written changes: eight lock-step streams (8 blocks per call: the fused layers), chunk by chunk, bit for bit against
     the hand-over launches (ESPNET_AMD_STREAM_NO_CTX_FOLD, read per call); stream 0 against the reference fixture."""
@@ -323,7 +323,7 @@ def test_batch_tick_context_hand_over_in_the_block_launches_equals_its_own_launc
 @pytest.mark.parametrize("n_streams", [1, 8, 24])
 def test_split_ffn_of_the_block_launches(n_streams):
     """Round 6: a tick that leaves CUs idle deals each FFN's hidden dimension to S workgroups per 32-row block (grid z of
-    block<A | RELU> / block<D | RELU>, EmBlockArgs.ffn_split; csrc/streaming.hip `cb_ffn_split`: 4 shares up to 32 row blocks,
+    block<A | RELU> / block<D | RELU>, EmBlockArgs.ffn_split; csrc/enc_host.h `stream_ffn_split`: 4 shares up to 32 row blocks,
     2 up to 64): each leaves the partial sum of its share in the workspace and the LAST to arrive adds them in split order.
     Only the order of an f32 sum changes (contextual_block_encoder_layer.py:218-222, 280-284 are the FFNs): against the
     unsplit launches (ESPNET_AMD_STREAM_FFN_SPLIT=1) within bf16 round-off of the layers behind it, the same bits on a second
