@@ -370,6 +370,11 @@ _SIGNATURES = {
     "em_decoder_memory": (C.c_int, [C.c_int, C.POINTER(EmDecoderWeights), _vp, _i32, _i32, _i32, _vp, _vp, _vp]),
     "em_decoder_step": (C.c_int, [C.c_int, C.POINTER(EmDecoderWeights), C.POINTER(EmDecoderStepArgs), _vp]),
     "em_lm_step": (C.c_int, [C.c_int, C.POINTER(EmSearchParams), C.POINTER(EmSearchBuffers), _i32, _vp]),
+    "em_lm_causal_attention": (C.c_int, [C.c_int, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "em_lm_head_nll_workspace_bytes": (_sz, [C.c_int, _i32, _i32]),
+    "em_lm_head_nll": (C.c_int, [C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _sz, _vp]),
+    "em_lm_seq_nll_workspace_bytes": (_sz, [C.c_int, C.POINTER(EmLmWeights), _i32, _i32]),
+    "em_lm_seq_nll": (C.c_int, [C.c_int, C.POINTER(EmLmWeights), _vp, _vp, _i32, _i32, _vp, _vp, _sz, _vp]),
     "em_ctc_log_probs_t": (C.c_int, [C.c_int, _vp, _i32, _i32, _i32, _vp, _vp, _i32, _vp, _vp]),
     "em_ctc_prefix_init": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _vp]),
     "em_ctc_prefix_score": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32,

@@ -162,12 +162,96 @@ class TransformerLM(PackedModule, BatchScorerInterface):
         logp, st = self.batch_score(y.unsqueeze(0), [state], x.unsqueeze(0))
         return logp[0], st[0]
 
+    @torch.no_grad()
+    def sequence_nll(self, x: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+        """Per-token negative log-likelihoods of whole sentences in one enqueue (`em_lm_seq_nll`, csrc/lm_seq.hip): x
+        (B, Lp) integer input tokens with 0 behind a sentence's end, target (B, Lp) the token scored at every position,
+        negative where nothing is scored -> nll (B, Lp) f32, exactly 0.0 there.  What `forward` + cross-entropy
+        compute position by position, over all B * Lp rows at once."""
+        L.require_gpu(x, "x")
+        L.require_gpu(target, "target")
+        if x.dim() != 2 or x.shape != target.shape or x.numel() == 0:
+            raise ValueError(f"sequence_nll: x and target must be equal, non-empty (B, Lp) tensors, got {tuple(x.shape)} "
+                             f"and {tuple(target.shape)}")
+        dev = x.device
+        B, Lp = x.shape
+        pk = self.packed(dev, Lp + 1)
+        xi = x.to(torch.int32).contiguous()
+        ti = target.to(torch.int32).contiguous()
+        if bool(((xi < 0) | (xi >= self.vocab_size)).any() | (ti >= self.vocab_size).any()):
+            raise ValueError(f"sequence_nll: token ids must lie in [0, {self.vocab_size})")
+        lib = L.load()
+        need = lib.em_lm_seq_nll_workspace_bytes(pk.dtype, C.byref(pk.w), B, Lp)
+        if need == 0:
+            raise NotImplementedError(f"sequence_nll: a batch of {B} x {Lp} tokens is outside the device path's index "
+                                      "range; score it in slices (ESPnetLanguageModel.batchify_nll)")
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        nll = torch.empty(B, Lp, dtype=torch.float32, device=dev)
+        L.check(lib.em_lm_seq_nll(pk.dtype, C.byref(pk.w), L.ptr(xi), L.ptr(ti), B, Lp, L.ptr(nll), L.ptr(ws), need,
+                                  L.current_stream_ptr()), "em_lm_seq_nll")
+        return nll
+
+
+def build_nll_batch(text: torch.Tensor, text_lengths: torch.Tensor, sos: int, eos: int, ignore_id: int = 0,
+                    max_length: Optional[int] = None):
+    """The sentence pair of ESPnetLanguageModel.nll (espnet2/lm/espnet_model.py:38-66), plain tensor work on whatever
+    device `text` lives on: text (B, Lt) is cut to its longest sentence (or to `max_length` columns), then
+    x = [sos | text], t = [text | ignore_id] with t[i, text_lengths[i]] = eos, x_lengths = text_lengths + 1.
+    Returns (x (B, L + 1), t (B, L + 1), x_lengths (B,)).  A sentence longer than `max_length` raises ValueError (the
+    reference would write its eos out of range)."""
+    if text.dim() != 2 or text_lengths.dim() != 1 or text.size(0) != text_lengths.size(0):
+        raise ValueError(f"text (B, L) and text_lengths (B,) expected, got {tuple(text.shape)}, {tuple(text_lengths.shape)}")
+    longest = int(text_lengths.max())
+    width = longest if max_length is None else int(max_length)
+    if longest > width or longest > text.size(1):
+        raise ValueError(f"text_lengths up to {longest} exceed the {min(width, text.size(1))} columns of text that are scored")
+    text = text[:, :width]
+    x = torch.nn.functional.pad(text, [1, 0], "constant", sos)
+    t = torch.nn.functional.pad(text, [0, 1], "constant", ignore_id)
+    t[torch.arange(t.size(0), device=t.device), text_lengths.to(t.device).long()] = eos
+    return x, t, text_lengths + 1
+
 
 class ESPnetLanguageModel(torch.nn.Module):
-    """espnet2/lm/espnet_model.py:13-22 (inference attributes only)."""
+    """espnet2/lm/espnet_model.py:13-120: the scorer's container (`.lm`, sos / eos / ignore_id) and the reference's two
+    text-scoring calls, `nll` and `batchify_nll`, on the device."""
 
     def __init__(self, lm: TransformerLM, vocab_size: int, ignore_id: int = 0):
         super().__init__()
         self.lm = lm
         self.sos = self.eos = vocab_size - 1
         self.ignore_id = ignore_id
+
+    @torch.no_grad()
+    def nll(self, text: torch.Tensor, text_lengths: torch.Tensor, max_length: Optional[int] = None):
+        """espnet_model.py:38-80.  text (B, Lt) int64, text_lengths (B,) -> (nll (B, L + 1) f32, x_lengths (B,)):
+        nll[i, j] = -log_softmax(lm(x)[i, j])[t[i, j]] for j < x_lengths[i], exactly 0.0 behind.  The TransformerLM scores
+        all rows in one enqueue (`sequence_nll`); a recurrent LM goes position by position through its `forward`."""
+        L.require_gpu(text, "text")
+        x, t, x_lengths = build_nll_batch(text, text_lengths, self.sos, self.eos, self.ignore_id, max_length)
+        x_lengths = x_lengths.to(x.device)
+        scored = torch.arange(x.size(1), device=x.device).unsqueeze(0) < x_lengths.unsqueeze(1)
+        x = torch.where(scored, x, torch.zeros_like(x))  # whatever the caller padded with: nothing behind the end is a key
+        if isinstance(self.lm, TransformerLM):
+            return self.lm.sequence_nll(x, torch.where(scored, t, torch.full_like(t, -1))), x_lengths
+        logits, _ = self.lm(x, None)
+        B, Lp, V = logits.shape
+        rows = logits.reshape(B * Lp, V)
+        L.check(L.load().em_log_softmax_rows_f32(L.ptr(rows), B * Lp, V, L.current_stream_ptr()), "em_log_softmax_rows_f32")
+        nll = -rows.gather(1, t.reshape(-1, 1).long()).reshape(B, Lp)
+        return torch.where(scored, nll, torch.zeros_like(nll)), x_lengths
+
+    @torch.no_grad()
+    def batchify_nll(self, text: torch.Tensor, text_lengths: torch.Tensor, batch_size: int = 100):
+        """espnet_model.py:82-120: `nll` over slices of `batch_size` sentences, every slice as wide as the longest
+        sentence of the whole call, so that the slices concatenate."""
+        total = text.size(0)
+        if total <= batch_size:
+            return self.nll(text, text_lengths)
+        max_length = int(text_lengths.max())
+        nlls, lens = [], []
+        for s in range(0, total, batch_size):
+            n, xl = self.nll(text[s:s + batch_size], text_lengths[s:s + batch_size], max_length=max_length)
+            nlls.append(n)
+            lens.append(xl)
+        return torch.cat(nlls), torch.cat(lens)

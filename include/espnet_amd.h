@@ -1043,6 +1043,39 @@ int em_decoder_step(int dtype, const EmDecoderWeights* dw, const EmDecoderStepAr
  *   reads p->{B,W,V,Lmax} and b->{lm, tok, anc_a, anc_b, parent, lm_*, rnn_*}; writes LOGITS to
  *   b->lm_logp [n][V] and the step's K/V (or ring-slot i % 3 recurrent state).  b->step must be NULL.     */
 int em_lm_step(int dtype, const EmSearchParams* p, const EmSearchBuffers* b, int32_t i, void* stream);
+
+/* ---- language model over whole sentences (csrc/lm_seq.hip): ESPnetLanguageModel.nll (espnet2/lm/espnet_model.py) for
+ *      the TransformerLM, all M = B * Lp rows of a batch at once instead of one position per em_lm_step call.
+ *   x      [B][Lp] i32  the input tokens [sos | text], 0 behind a sentence's end (the host writes it);
+ *   target [B][Lp] i32  the token to score at every position ([text | eos]), negative where nothing is scored;
+ *   nll    [B][Lp] f32  out: -log_softmax(lm(x)[b][j])[target[b][j]], exactly 0.0 where target < 0.
+ *   A row depends on the tokens of its own sentence at positions <= its own and on nothing else (bit for bit, for a
+ *   given B and Lp).
+ *
+ *   em_lm_causal_attention: MultiHeadedAttention under TransformerLM._target_mask (transformer_lm.py:54-57): query j of
+ *     sentence b attends the keys k <= j with x[b][k] != 0; a masked key contributes an exact zero, a query without a visible
+ *     key gives a zero row.  qkv [B*Lp][3d] act (q | k | v per row), ctx [B*Lp][d] act out; d / heads in {32, 64}
+ *     (EM_ERR_UNSUPPORTED otherwise), any Lp >= 1.  EM_BF16: MFMA, f32 accumulation and online softmax, the key tiles
+ *     walked up to the diagonal, 4.5 KiB of LDS whatever Lp is; EM_F32: a plain kernel.
+ *   em_lm_head_nll: nll[r] = logsumexp_v(y[r][v]) - y[r][target[r]] with y = LN(xrows; norm_g, norm_b, eps 1e-12) out_w^T
+ *     + out_b, the [M][V] logits never stored: a row's running (maximum, sum of exponentials, target logit) per vocabulary
+ *     tile is all that is kept.  xrows [M][d] f32, out_w [V][d] act, target[r] in [0, V) or negative (then nll[r] = 0.0); any
+ *     M and V.  EM_BF16: d % 32 == 0, d <= 1024 (EM_ERR_UNSUPPORTED otherwise), ws of em_lm_head_nll_workspace_bytes bytes
+ *     (a smaller one: EM_ERR_WORKSPACE); EM_F32: no workspace (ws may be NULL).
+ *   em_lm_seq_nll: the whole chain, enqueue only: embedding, input Linear + LayerNorm(1e-5) + ReLU (+ x sqrt(d) + pe[j]),
+ *     the pre-norm layers, after_norm and the head.  lm->kind must be EM_LM_TRANSFORMER (EM_ERR_BAD_ARG otherwise); with
+ *     positional encoding lm->pe must hold at least Lp rows (the caller's pack).  ws: em_lm_seq_nll_workspace_bytes bytes
+ *     of device memory (0 = shape not covered: em_lm_seq_nll then returns EM_ERR_UNSUPPORTED and the caller splits the
+ *     batch); a smaller one: EM_ERR_WORKSPACE.                                                                          */
+int em_lm_causal_attention(int dtype, const void* qkv, const int32_t* x, int32_t B, int32_t Lp, int32_t d, int32_t heads,
+                           void* ctx, void* stream);
+size_t em_lm_head_nll_workspace_bytes(int dtype, int32_t M, int32_t V);
+int em_lm_head_nll(int dtype, const float* xrows, const float* norm_g, const float* norm_b, const void* out_w,
+                   const float* out_b, const int32_t* target, int32_t M, int32_t V, int32_t d, float* nll, void* ws,
+                   size_t ws_bytes, void* stream);
+size_t em_lm_seq_nll_workspace_bytes(int dtype, const EmLmWeights* lm, int32_t B, int32_t Lp);
+int em_lm_seq_nll(int dtype, const EmLmWeights* lm, const int32_t* x, const int32_t* target, int32_t B, int32_t Lp,
+                  float* nll, void* ws, size_t ws_bytes, void* stream);
 /*   CTC.log_softmax(enc) (espnet2/asr/ctc.py:197-205, scorers/ctc.py:96-98) TRANSPOSED: lpT [V][B*T] f32. */
 int em_ctc_log_probs_t(int dtype, const void* enc_act, int32_t B, int32_t T, int32_t d_model,
                        const void* ctc_w, const float* ctc_b, int32_t V, float* lpT, void* stream);
