@@ -12,7 +12,8 @@ Inside the fused device search (espnet_amd/nets/batch_beam_search.py) the decode
 Python.  The reference's scorer interface (`init_state`, `batch_init_state`, `select_state`, `score`,
 `batch_score`, `final_score`; legacy/nets/scorer_interface.py:29-122) is implemented on the same device code
 through `em_decoder_memory` + `em_decoder_step`, one call per search step, so the reference's own
-BatchBeamSearch can be driven by this class.
+BatchBeamSearch can be driven by this class.  A transcript that is known beforehand is scored whole:
+`sequence_nll` (`em_dec_seq_nll`, csrc/dec_seq.hip) runs all positions of a batch in one enqueue.
 """
 import ctypes as C
 import math
@@ -256,6 +257,61 @@ class TransformerDecoder(PackedModule, BatchScorerInterface):
             out[:, pos] = logits
         self._mem = None
         return out, ys_in_lens
+
+    @torch.no_grad()
+    def sequence_nll(self, hs_pad: torch.Tensor, hlens, x: torch.Tensor, keymask: torch.Tensor, target: torch.Tensor,
+                     mem_of=None) -> torch.Tensor:
+        """Per-token negative log-likelihoods of whole transcripts in one enqueue (`em_dec_seq_nll`, csrc/dec_seq.hip):
+        hs_pad (Bm, T, d) encoder memories on the GPU, hlens (Bm,) their valid frames; x (B, Lp) the input tokens
+        [sos | text], keymask (B, Lp) 1 below a transcript's length and 0 behind it, target (B, Lp) the token scored at
+        every position, negative where nothing is scored; mem_of (B,) the memory of each transcript (None: transcript b
+        uses memory b) -> nll (B, Lp) f32, exactly 0.0 where target < 0.  What `forward` + cross-entropy compute position
+        by position, over all B * Lp rows at once and without the (B, Lp, V) logits."""
+        L.require_gpu(hs_pad, "hs_pad")
+        if hs_pad.dim() != 3 or hs_pad.size(2) != self.d or hs_pad.size(0) == 0 or hs_pad.size(1) == 0:
+            raise ValueError(f"sequence_nll: hs_pad must be a non-empty (Bm, T, {self.d}) tensor, got {tuple(hs_pad.shape)}")
+        if x.dim() != 2 or x.numel() == 0 or x.shape != keymask.shape or x.shape != target.shape:
+            raise ValueError(f"sequence_nll: x, keymask and target must be equal, non-empty (B, Lp) tensors, got "
+                             f"{tuple(x.shape)}, {tuple(keymask.shape)}, {tuple(target.shape)}")
+        hs_pad = hs_pad.contiguous()  # (an expanded view would be taken for ONE shared memory by `_memory`)
+        dev = hs_pad.device
+        Bm, T, d = hs_pad.shape
+        B, Lp = x.shape
+        V = self.vocab_size
+        xi, ki, ti = (t.to(device=dev, dtype=torch.int32).contiguous() for t in (x, keymask, target))
+        kl = torch.as_tensor(hlens).to(device=dev, dtype=torch.int32).contiguous()
+        if kl.shape != (Bm,):
+            raise ValueError(f"sequence_nll: {tuple(kl.shape)} memory lengths for {Bm} memories")
+        bad = ((xi < 0) | (xi >= V)).any() | (ti >= V).any() | (kl < 1).any() | (kl > T).any()
+        mo = None
+        if mem_of is not None:
+            mo = torch.as_tensor(mem_of).to(device=dev, dtype=torch.int32).contiguous()
+            if mo.shape != (B,):
+                raise ValueError(f"sequence_nll: mem_of has shape {tuple(mo.shape)} for {B} transcripts")
+            bad = bad | (mo < 0).any() | (mo >= Bm).any()
+        elif Bm != B:
+            raise ValueError(f"sequence_nll: {B} transcripts for {Bm} memories need mem_of")
+        if bool(bad):
+            raise ValueError(f"sequence_nll: token ids must lie in [0, {V}), memory lengths in [1, {T}] and mem_of in "
+                             f"[0, {Bm})")
+        if d % self.heads or d // self.heads not in (32, 64):
+            raise NotImplementedError(f"sequence_nll: heads of {d // self.heads} channels (d {d}, {self.heads} heads); the "
+                                      "device path covers 32 and 64")
+        pk = self.packed(dev, Lp + 1)
+        lib = L.load()
+        need = lib.em_dec_seq_nll_workspace_bytes(pk.dtype, C.byref(pk.w), B, Lp)
+        if need == 0:
+            raise NotImplementedError(f"sequence_nll: a batch of {B} x {Lp} tokens is outside the device path's index "
+                                      "range; score it in slices (ESPnetASRModel.batchify_nll)")
+        self._mem = None
+        mem = self._memory(hs_pad if Bm > 1 else hs_pad[0:1], pk)
+        self._mem = None
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        nll = torch.empty(B, Lp, dtype=torch.float32, device=dev)
+        L.check(lib.em_dec_seq_nll(pk.dtype, C.byref(pk.w), L.ptr(mem["mem_kv"]), L.ptr(mem["mem_vT"]), L.ptr(kl), L.ptr(mo),
+                                   L.ptr(xi), L.ptr(ki), L.ptr(ti), B, Bm, Lp, T, mem["Tpad"], L.ptr(nll), L.ptr(ws), need,
+                                   L.current_stream_ptr()), "em_dec_seq_nll")
+        return nll
 
     def score(self, ys: torch.Tensor, state, x: torch.Tensor):
         """transformer_decoder.py:253-268: one hypothesis.  ys (L,), x (T, d)."""

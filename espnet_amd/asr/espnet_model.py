@@ -5,6 +5,9 @@ touches: `encode(speech, speech_lengths)`, `_extract_feats`, `.frontend/.normali
 .decoder/.ctc/.joint_network`, `.sos/.eos/.blank_id/.token_list/.vocab_size`, `.use_transducer_decoder`.  State-dict keys are the
 reference's (`frontend.logmel.melmat`, `encoder.*`, `decoder.*`, `ctc.ctc_lo.*`).
 
+`nll / batchify_nll` (the attention decoder's teacher-forced likelihood of given transcripts) keep the reference's
+signatures and run as one enqueue per batch (TransformerDecoder.sequence_nll, csrc/dec_seq.hip).
+
 `encode` keeps the reference signature (padded batch + lengths, any B); `encode_device` is the
 batched device-resident entry the MI355X drop-in adds (precedent in the reference:
 espnet2/bin/asr_inference_k2.py:233-262 and bin/s2t_inference_ctc.py:700-749).
@@ -26,6 +29,39 @@ class EncoderState:
         self.olens, self.olens_dev = olens, olens_dev
         self.feats, self.flens = feats, flens
         self.ctc_ids = ctc_ids  # (B, T) i32 per-frame CTC arg-max when the encoder's last kernel produced it
+
+
+def build_dec_nll_batch(ys_pad: torch.Tensor, ys_pad_lens: torch.Tensor, sos: int, eos: int,
+                        vocab_size: Optional[int] = None):
+    """The decoder's sentence pair of ESPnetASRModel.nll (espnet2/asr/espnet_model.py `nll`; add_sos_eos,
+    espnet2/asr/../nets_utils), plain tensor work on whatever device `ys_pad` lives on: ys_pad (B, Lt) is cut to its
+    longest transcript, then with Lp = longest + 1
+        x       = [sos | y], <eos> behind a transcript's end (the reference pads ys_in with <eos> too);
+        keymask = 1 at the positions below ys_in_lens = ys_pad_lens + 1, 0 behind;
+        target  = [y | eos], -1 behind (the reference's ignore_id positions: nothing is scored there).
+    Whatever ys_pad holds behind ys_pad_lens is not looked at.  An empty transcript is valid: it scores <eos> alone.
+    With `vocab_size`, a token id outside [0, vocab_size) raises ValueError.  Returns (x, keymask, target), (B, Lp) int32."""
+    if ys_pad.dim() != 2 or ys_pad_lens.dim() != 1 or ys_pad.size(0) != ys_pad_lens.size(0) or ys_pad.size(0) == 0:
+        raise ValueError(f"ys_pad (B, L) and ys_pad_lens (B,) expected, got {tuple(ys_pad.shape)}, {tuple(ys_pad_lens.shape)}")
+    dev = ys_pad.device
+    lens = ys_pad_lens.to(device=dev, dtype=torch.long)
+    longest, shortest = int(lens.max()), int(lens.min())
+    if shortest < 0 or longest > ys_pad.size(1):
+        raise ValueError(f"ys_pad_lens must lie in [0, {ys_pad.size(1)}], got {shortest} .. {longest}")
+    B, Lp = ys_pad.size(0), longest + 1
+    y = ys_pad[:, :longest].to(torch.long)
+    pos = torch.arange(Lp, device=dev).unsqueeze(0)
+    inside = pos[:, :longest] < lens.unsqueeze(1)
+    if vocab_size is not None and bool((((y < 0) | (y >= vocab_size)) & inside).any()):
+        raise ValueError(f"token ids must lie in [0, {vocab_size})")
+    x = torch.full((B, Lp), eos, dtype=torch.long, device=dev)
+    x[:, 0] = sos
+    x[:, 1:] = torch.where(inside, y, torch.full_like(y, eos))
+    target = torch.full((B, Lp), -1, dtype=torch.long, device=dev)
+    target[:, :longest] = torch.where(inside, y, torch.full_like(y, -1))
+    target.scatter_(1, lens.unsqueeze(1), eos)
+    keymask = pos <= lens.unsqueeze(1)
+    return x.to(torch.int32), keymask.to(torch.int32), target.to(torch.int32)
 
 
 class ESPnetASRModel(torch.nn.Module):
@@ -145,6 +181,45 @@ class ESPnetASRModel(torch.nn.Module):
         """espnet_model.py:450-467."""
         speech = speech[:, : int(speech_lengths.max())]
         return self.frontend(speech, speech_lengths)
+
+    # ------------------------------------------------------------------ attention-decoder likelihood of a transcript
+    def _nll_rows(self, encoder_out, encoder_out_lens, ys_pad, ys_pad_lens, mem_of=None) -> torch.Tensor:
+        """(B,) f32: transcript b under the attention decoder given memory mem_of[b] (None: memory b)."""
+        if self.use_transducer_decoder:
+            raise RuntimeError("nll: this is a transducer model (joint network); the teacher-forced attention likelihood "
+                               "needs an attention decoder")
+        if self.decoder is None:
+            raise RuntimeError("nll: the model has no attention decoder (ctc_weight == 1.0)")
+        if not hasattr(self.decoder, "sequence_nll"):
+            raise RuntimeError(f"nll: {type(self.decoder).__name__} has no whole-sequence scoring path")
+        x, keymask, target = build_dec_nll_batch(ys_pad, ys_pad_lens, self.sos, self.eos, self.vocab_size)
+        return self.decoder.sequence_nll(encoder_out, encoder_out_lens, x, keymask, target, mem_of=mem_of).sum(dim=1)
+
+    @torch.no_grad()
+    def nll(self, encoder_out: torch.Tensor, encoder_out_lens: torch.Tensor, ys_pad: torch.Tensor,
+            ys_pad_lens: torch.Tensor) -> torch.Tensor:
+        """espnet_model.py `nll`: the decoder's teacher-forced negative log-likelihood of every transcript given its
+        encoder output, (B,) f32.  encoder_out (B, T, d) on the GPU, encoder_out_lens (B,), ys_pad (B, Lmax) token ids,
+        ys_pad_lens (B,).  ys_in = [sos | y], ys_out = [y | eos], ys_in_lens = ys_pad_lens + 1; the memory is masked by
+        encoder_out_lens; the per-token cross-entropy is summed over the ys_pad_lens + 1 scored positions.  One enqueue for
+        the whole batch (TransformerDecoder.sequence_nll); the (B, L, V) scores of `decoder.forward` never exist."""
+        return self._nll_rows(encoder_out, encoder_out_lens, ys_pad, ys_pad_lens)
+
+    @torch.no_grad()
+    def batchify_nll(self, encoder_out: torch.Tensor, encoder_out_lens: torch.Tensor, ys_pad: torch.Tensor,
+                     ys_pad_lens: torch.Tensor, batch_size: int = 100) -> torch.Tensor:
+        """espnet_model.py `batchify_nll`: `nll` in slices of batch_size utterances, concatenated."""
+        total_num = encoder_out.size(0)
+        if batch_size < 1:
+            raise ValueError(f"batch_size must be positive, got {batch_size}")
+        if total_num <= batch_size:
+            return self.nll(encoder_out, encoder_out_lens, ys_pad, ys_pad_lens)
+        lens, ylens = torch.as_tensor(encoder_out_lens), torch.as_tensor(ys_pad_lens)
+        parts = []
+        for s in range(0, total_num, batch_size):
+            e = min(s + batch_size, total_num)
+            parts.append(self.nll(encoder_out[s:e], lens[s:e], ys_pad[s:e], ylens[s:e]))
+        return torch.cat(parts)
 
     # ------------------------------------------------------------------ greedy CTC (G1)
     def greedy_ctc_device(self, st: EncoderState, out=None):

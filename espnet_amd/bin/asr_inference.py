@@ -314,6 +314,54 @@ class Speech2Text:
                                 total=float(row[T + 3 * Lm])))
         return results
 
+    # ------------------------------------------------------------------ attention-decoder likelihood of given transcripts
+    nll_rows_per_call = 100  # candidates per enqueue (ESPnetASRModel.batchify_nll's default slice)
+
+    @staticmethod
+    def _is_one_transcript(t) -> bool:
+        if isinstance(t, str) or hasattr(t, "tolist"):
+            return True
+        return len(t) == 0 or all(isinstance(v, (int, np.integer)) for v in t)
+
+    @torch.no_grad()
+    def batch_nll(self, speech: torch.Tensor, speech_lengths: Sequence[int], texts):
+        """Teacher-forced negative log-likelihood of given transcripts under the attention decoder
+        (`ESPnetASRModel.nll`): speech (B, N) zero padded, lengths host ints; texts[b] is one transcript or a list of
+        candidate transcripts of utterance b (an n-best list to rescore), a transcript being a string (tokenised with
+        this object's tokenizer) or a sequence of token ids - an empty one scores <eos> alone.  Returns one list of
+        floats per utterance, a value per candidate.  The utterances are encoded as `batch_decode` encodes them; the
+        candidates of an utterance share its one projected memory.  One D2H copy per call."""
+        m = self.asr_model
+        B = int(speech.shape[0])
+        if len(texts) != B:
+            raise ValueError(f"{len(texts)} transcript entries for {B} utterances")
+        cands = [[t] if self._is_one_transcript(t) else list(t) for t in texts]
+        ids, mem_of = [], []
+        for b, group in enumerate(cands):
+            for t in group:
+                ids.append(self._target_ids(t))
+                mem_of.append(b)
+        if not ids:
+            return [[] for _ in range(B)]
+        speech = speech.to(self.device, torch.float32, non_blocking=True)
+        st = m.encode_device(speech, [int(n) for n in speech_lengths], isolate=True)
+        olens = torch.tensor(st.olens, dtype=torch.int32)
+        parts = []
+        for s in range(0, len(ids), self.nll_rows_per_call):
+            rows, mo = ids[s : s + self.nll_rows_per_call], mem_of[s : s + self.nll_rows_per_call]
+            u0, u1 = mo[0], mo[-1] + 1  # the slice's utterances: only their memories are projected
+            ys = torch.zeros(len(rows), max(max(len(y) for y in rows), 1), dtype=torch.long)
+            for i, y in enumerate(rows):
+                ys[i, : len(y)] = torch.tensor(y, dtype=torch.long)
+            parts.append(m._nll_rows(st.enc_act[u0:u1], olens[u0:u1], ys, torch.tensor([len(y) for y in rows]),
+                                     mem_of=torch.tensor([u - u0 for u in mo], dtype=torch.int32)))
+        vals = torch.cat(parts).cpu().tolist()
+        out, k = [], 0
+        for group in cands:
+            out.append(vals[k : k + len(group)])
+            k += len(group)
+        return out
+
     def decode_greedy_device(self, st):
         """Device-resident G1 result: (tokens (B,T) i32 padded with -1, token_lens (B,) i32)."""
         _, tokens, tlens = self.asr_model.greedy_ctc_device(st)

@@ -375,6 +375,12 @@ _SIGNATURES = {
     "em_lm_head_nll": (C.c_int, [C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _sz, _vp]),
     "em_lm_seq_nll_workspace_bytes": (_sz, [C.c_int, C.POINTER(EmLmWeights), _i32, _i32]),
     "em_lm_seq_nll": (C.c_int, [C.c_int, C.POINTER(EmLmWeights), _vp, _vp, _i32, _i32, _vp, _vp, _sz, _vp]),
+    "em_dec_seq_embed_f32": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "em_dec_seq_src_attention": (C.c_int, [C.c_int, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32,
+                                           _vp, _vp]),
+    "em_dec_seq_nll_workspace_bytes": (_sz, [C.c_int, C.POINTER(EmDecoderWeights), _i32, _i32]),
+    "em_dec_seq_nll": (C.c_int, [C.c_int, C.POINTER(EmDecoderWeights), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32,
+                                 _i32, _i32, _vp, _vp, _sz, _vp]),
     "em_ctc_log_probs_t": (C.c_int, [C.c_int, _vp, _i32, _i32, _i32, _vp, _vp, _i32, _vp, _vp]),
     "em_ctc_prefix_init": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _vp]),
     "em_ctc_prefix_score": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32,

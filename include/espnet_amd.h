@@ -1076,6 +1076,44 @@ int em_lm_head_nll(int dtype, const float* xrows, const float* norm_g, const flo
 size_t em_lm_seq_nll_workspace_bytes(int dtype, const EmLmWeights* lm, int32_t B, int32_t Lp);
 int em_lm_seq_nll(int dtype, const EmLmWeights* lm, const int32_t* x, const int32_t* target, int32_t B, int32_t Lp,
                   float* nll, void* ws, size_t ws_bytes, void* stream);
+
+/* ---- attention decoder over whole transcripts (csrc/dec_seq.hip): ESPnetASRModel.nll (espnet2/asr/espnet_model.py) - the
+ *      teacher-forced negative log-likelihood of transcripts given their encoder memories, all M = B * Lp rows of a batch at
+ *      once instead of one position per em_decoder_step call.
+ *   mem_kv, mem_vT, T, Tpad  the caller's em_decoder_memory of Bm memories;
+ *   klens   [Bm] i32     the valid frames of each memory;
+ *   mem_of  [B] i32      the memory of each sentence, or NULL: sentence b uses memory b (then Bm >= B).  With it the
+ *                        candidates of one utterance share one projected memory.  Values outside [0, Bm) are clamped;
+ *   x       [B][Lp] i32  the input tokens [sos | text], any id in [0, V) behind a sentence's end;
+ *   keymask [B][Lp] i32  1 at the positions below the sentence's length (ys_in_lens), 0 behind it;
+ *   target  [B][Lp] i32  the token to score at every position ([text | eos]), negative where nothing is scored;
+ *   nll     [B][Lp] f32  out: -log_softmax(decoder(x)[b][j])[target[b][j]], exactly 0.0 where target < 0.
+ *   A row depends on the tokens of its own sentence at positions <= its own, on its memory's frames below klens and on
+ *   nothing else (bit for bit, for given B, Lp and T).
+ *
+ *   em_dec_seq_embed_f32: x[r] = embed[tok[r]] * sqrt(d) + pe[r % Lp] for r < M (embedding.py:93 for M = B * Lp rows in one
+ *     launch); Lp <= pe_len (EM_ERR_BAD_ARG otherwise).
+ *   em_dec_seq_src_attention: MultiHeadedAttention of src_attn for whole sentences.  qs [B*Lp][d] act the projected
+ *     queries; kmem, ldk, vT, Tpad as em_decoder_memory leaves them and em_dec_src_attention takes them (one layer);
+ *     ctx [B*Lp][d] act out.  Query (b, j) attends the frames t < klens[mem_of[b]] and nothing else; a masked frame
+ *     contributes an exact zero whatever the memory holds there; a memory without a valid frame gives zero rows.
+ *     d / heads in {32, 64} (EM_ERR_UNSUPPORTED otherwise), any T >= 1 and Lp >= 1.  EM_BF16: MFMA, f32 accumulation and
+ *     online softmax over tiles of 32 frames, K and V^T operands straight from global memory: no LDS, whatever T is
+ *     (ldk % 8 == 0); EM_F32: a plain kernel.
+ *   em_dec_seq_nll: the whole chain, enqueue only: embedding, the pre-norm layers (em_lm_causal_attention with keymask as
+ *     its token array = the reference's tgt_mask; em_dec_seq_src_attention), after_norm and em_lm_head_nll, on the
+ *     row-major matrices of dw.  dw->pe must hold at least Lp rows.  ws: em_dec_seq_nll_workspace_bytes bytes of device
+ *     memory (0 = shape not covered: em_dec_seq_nll then returns EM_ERR_UNSUPPORTED and the caller splits the batch); a
+ *     smaller one: EM_ERR_WORKSPACE.                                                                                    */
+int em_dec_seq_embed_f32(const float* embed, const float* pe, const int32_t* tok, int32_t M, int32_t V, int32_t d,
+                         int32_t Lp, int32_t pe_len, float* x, void* stream);
+int em_dec_seq_src_attention(int dtype, const void* qs, const void* kmem, int32_t ldk, const void* vT,
+                             const int32_t* klens, const int32_t* mem_of, int32_t B, int32_t Bm, int32_t Lp, int32_t d,
+                             int32_t heads, int32_t T, int32_t Tpad, void* ctx, void* stream);
+size_t em_dec_seq_nll_workspace_bytes(int dtype, const EmDecoderWeights* dw, int32_t B, int32_t Lp);
+int em_dec_seq_nll(int dtype, const EmDecoderWeights* dw, const void* mem_kv, const void* mem_vT, const int32_t* klens,
+                   const int32_t* mem_of, const int32_t* x, const int32_t* keymask, const int32_t* target, int32_t B,
+                   int32_t Bm, int32_t Lp, int32_t T, int32_t Tpad, float* nll, void* ws, size_t ws_bytes, void* stream);
 /*   CTC.log_softmax(enc) (espnet2/asr/ctc.py:197-205, scorers/ctc.py:96-98) TRANSPOSED: lpT [V][B*T] f32. */
 int em_ctc_log_probs_t(int dtype, const void* enc_act, int32_t B, int32_t T, int32_t d_model,
                        const void* ctc_w, const float* ctc_b, int32_t V, float* lpT, void* stream);
