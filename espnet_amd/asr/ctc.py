@@ -1,6 +1,6 @@
 """CTC head on the MI355X.  Mirrors espnet2/asr/ctc.py:9-215 for inference (`ctc_lo`,
-`softmax`/`log_softmax`/`argmax`, `forced_align`); state-dict keys `ctc_lo.{weight,bias}`.  The loss is
-training only and out of scope."""
+`softmax`/`log_softmax`/`argmax`, `forced_align`); state-dict keys `ctc_lo.{weight,bias}`.  Of the loss only the
+per-utterance value exists (`nll`: scoring given transcripts); gradients and the reduced training loss are out of scope."""
 import os
 
 import torch
@@ -176,6 +176,80 @@ class CTC(PackedModule):
         act = self._to_act(hs_pad)
         host = [x.cpu() if torch.is_tensor(x) else x for x in (hlens, ys_pad, ylens)]
         return self.forced_align_device(act, host[0], host[1], host[2], int(blank_idx))[0].to(torch.int64)
+
+    # ------------------------------------------------------------------ likelihood of given transcripts (csrc/ctc_nll.hip)
+    def nll_device(self, enc_act: torch.Tensor, olens, targets, ylens, blank: int, mem_of=None) -> torch.Tensor:
+        """-log p_ctc(targets[n] | utterance mem_of[n]) for N candidate transcripts, (N,) f32 on the device, by
+        `em_ctc_log_probs_t` -> `em_ctc_seq_nll` (include/espnet_amd.h states the recursion); only enqueues work.
+
+        enc_act (Bm,T,d) in the compute dtype; olens (Bm,); targets (N, Lmax) ids padded with anything, ylens (N,);
+        mem_of (N,) the utterance of each candidate, None: candidate n belongs to utterance n (N == Bm).  The argument
+        forms are `forced_align_device`'s: HOST data (lists or CPU tensors) is checked first - ids in [0, V) and not the
+        blank, lengths inside their rows, mem_of in [0, Bm): ValueError before any launch - and copied over; int32
+        DEVICE tensors are taken as they are.  A transcript its utterance has too few frames for is no error here: its
+        value is +inf, as the reference's ctc_loss has it."""
+        L.require_gpu(enc_act, "enc_act")
+        Bm, T, d = enc_act.shape
+        dev, V = enc_act.device, self.odim
+        given = (olens, targets, ylens) + (() if mem_of is None else (mem_of,))
+        on_dev = [torch.is_tensor(x) and x.is_cuda for x in given]
+        if all(on_dev):
+            if any(x.dtype != torch.int32 for x in given) or targets.dim() != 2:
+                raise ValueError("device-side olens / targets / ylens / mem_of must be int32, targets (N, Lmax)")
+            olens_d, tg_d, ylens_d = olens.contiguous(), targets.contiguous(), ylens.contiguous()
+            mo_d = None if mem_of is None else mem_of.contiguous()
+            N, Lmax = int(targets.shape[0]), int(targets.shape[1])
+            if int(olens_d.numel()) != Bm or int(ylens_d.numel()) != N or (mo_d is not None and int(mo_d.numel()) != N):
+                raise ValueError(f"olens must have {Bm} entries, ylens and mem_of {N}")
+        elif any(on_dev):
+            raise ValueError("olens, targets, ylens and mem_of must be all host data or all device tensors")
+        else:
+            ol, rows, yl, mo = [x.tolist() if torch.is_tensor(x) else list(x) for x in given] + ([None] if mem_of is None else [])
+            N = len(rows)
+            if len(ol) != Bm or len(yl) != N or (mo is not None and len(mo) != N):
+                raise ValueError(f"olens must have {Bm} entries, ylens and mem_of as many as targets ({N})")
+            if any(n < 0 or n > len(r) for n, r in zip(yl, rows)) or any(n < 0 or n > T for n in ol):
+                raise ValueError("a length lies outside its row")
+            if mo is not None and any(u < 0 or u >= Bm for u in mo):
+                raise ValueError(f"mem_of must lie in [0, {Bm})")
+            rows = [[int(v) for v in r[:n]] for r, n in zip(rows, yl)]
+            self.check_alignable([2 ** 31] * N, rows, blank, V)  # (the ids only: too few frames give +inf, not an error)
+            Lmax = max(yl) if yl else 0
+            tg = torch.zeros(max(N, 1), max(Lmax, 1), dtype=torch.int32)
+            for n, r in enumerate(rows):
+                tg[n, : len(r)] = torch.tensor(r, dtype=torch.int32)
+            olens_d = torch.tensor(ol, dtype=torch.int32).to(dev, non_blocking=True)
+            ylens_d = torch.tensor(yl, dtype=torch.int32).to(dev, non_blocking=True)
+            tg_d = tg[:, : max(Lmax, 1)].contiguous().to(dev, non_blocking=True)
+            mo_d = None if mo is None else torch.tensor(mo, dtype=torch.int32).to(dev, non_blocking=True)
+        if N == 0:
+            return torch.empty(0, dtype=torch.float32, device=dev)
+        if mo_d is None and N != Bm:
+            raise ValueError(f"{N} transcripts for {Bm} utterances need mem_of")
+        p = self.packed(dev)
+        lpT = torch.empty(V, Bm * T, dtype=torch.float32, device=dev)
+        L.check(L.load().em_ctc_log_probs_t(self.em_dtype, L.ptr(enc_act), Bm, T, d, L.ptr(p.weight), L.ptr(p.bias), V,
+                                            L.ptr(lpT), L.current_stream_ptr()), "em_ctc_log_probs_t")
+        return self.nll_log_probs_t(lpT, Bm * T, olens_d, Bm, T, tg_d, Lmax, ylens_d, mo_d, N, blank)
+
+    @staticmethod
+    def nll_log_probs_t(lpT, ldT, olens_d, Bm, T, tg_d, Lmax, ylens_d, mem_of_d, N, blank) -> torch.Tensor:
+        """`em_ctc_seq_nll` on given transposed log-posteriors lpT [V][ldT] (device tensors throughout; tg_d's row stride
+        is Lmax, or 1 when Lmax == 0)."""
+        nll = torch.empty(N, dtype=torch.float32, device=lpT.device)
+        L.check(L.load().em_ctc_seq_nll(L.ptr(lpT), ldT, L.ptr(olens_d), Bm, T, L.ptr(tg_d), Lmax, L.ptr(ylens_d),
+                                        L.ptr(mem_of_d), N, blank, L.ptr(nll), L.current_stream_ptr()), "em_ctc_seq_nll")
+        return nll
+
+    def nll(self, hs_pad: torch.Tensor, hlens, ys_pad, ys_lens, blank_idx: int = 0) -> torch.Tensor:
+        """The per-utterance value of the reference's CTC.forward with reduce=False under the builtin ctc_loss
+        (espnet2/asr/ctc.py; there the values are summed and divided by the batch size): hs_pad (B,T,d) encoder output
+        on the device, hlens (B,), ys_pad (B,Lmax) target ids, ys_lens (B,) -> (B,) f32 on the device, +inf where the
+        frames cannot carry the transcript (ctc_loss with zero_infinity=False).  Ids equal to the blank or outside
+        [0, V) raise ValueError."""
+        act = self._to_act(hs_pad)
+        host = [x.cpu() if torch.is_tensor(x) else x for x in (hlens, ys_pad, ys_lens)]
+        return self.nll_device(act, host[0], host[1], host[2], int(blank_idx))
 
     @staticmethod
     def _token_outputs(B, T, dev, out):

@@ -96,7 +96,7 @@ class Speech2Text:
             self.tokenizer = build_tokenizer(token_type=token_type, bpemodel=bpemodel)
         self.converter = TokenIDConverter(token_list=token_list)
         self.beam_search = self.beam_search_transducer = None
-        self.lm = self.ngram = None
+        self.lm = self.lm_model = self.ngram = None
         if asr_model.use_transducer_decoder:  # asr_inference.py: BeamSearchTransducer in place of the joint search
             if lm_train_config is not None or ngram_file is not None:
                 raise NotImplementedError("lm_train_config / ngram_file with a transducer model: language-model fusion in "
@@ -118,6 +118,7 @@ class Speech2Text:
 
                 lm_model, _ = LMTask.build_model_from_file(lm_train_config, lm_file, device, compute_dtype=dtype)
                 lm = lm_model.lm
+                self.lm_model = lm_model  # (its `nll`: the LM term of `batch_rescore`)
             self.lm = lm
             if ngram_file is not None:  # asr_inference.py:193-207
                 from espnet_amd.nets.scorers.ngram import NgramFullScorer, NgramPartScorer
@@ -360,6 +361,82 @@ class Speech2Text:
         for group in cands:
             out.append(vals[k : k + len(group)])
             k += len(group)
+        return out
+
+    # ------------------------------------------------------------------ the joint score of given transcripts
+    @torch.no_grad()
+    def batch_rescore(self, speech: torch.Tensor, speech_lengths: Sequence[int], texts):
+        """The joint search's own score of given transcripts - an n-best list of another system, of a first pass with a
+        small beam - from the three whole-sequence scorers: `CTC.nll_device`, `ESPnetASRModel.nll`'s decoder route and the
+        LM's `nll`.  speech, speech_lengths and texts as `batch_nll` takes them.  Returns one list per utterance with a
+        dict per candidate, in the caller's order (nothing is sorted, no length normalisation):
+          token_int  the candidate's ids;
+          scores     keys, sign and meaning of `Hypothesis.scores` as the search fills them: ctc = log p_ctc(y|x),
+                     decoder = log p_att(y <eos>|x), lm = log p_lm(y <eos>), length_bonus = len(y) + 1; a scorer whose
+                     weight is zero or that the model lacks is absent, as in the search;
+          score      the sum of `scores` weighted with `self.beam_search.weights` (accumulated on the host, in key order).
+        A candidate its utterance has too few frames for has ctc = -inf.  Needs an object built with the joint search;
+        whole-sentence n-gram scoring does not exist (NotImplementedError for an object with `ngram_file`).  The
+        utterances are encoded as `batch_decode` encodes them; the candidates go through in slices of
+        `nll_rows_per_call`, a slice's candidates sharing their utterance's CTC log-probabilities and projected memory.
+        Every scorer only enqueues; one D2H copy per call."""
+        if self.ctc_greedy:
+            raise RuntimeError("batch_rescore: this object decodes greedy CTC (ctc_greedy=True) and has no joint search whose "
+                               "score it could give")
+        if self.beam_search is None:
+            raise RuntimeError("batch_rescore: this is a transducer model; the joint CTC/attention score needs the joint "
+                               "search's scorers")
+        if self.ngram is not None:
+            raise NotImplementedError("batch_rescore with ngram_file: whole-sentence n-gram scoring is not implemented")
+        m, bs = self.asr_model, self.beam_search
+        B = int(speech.shape[0])
+        if len(texts) != B:
+            raise ValueError(f"{len(texts)} transcript entries for {B} utterances")
+        cands = [[t] if self._is_one_transcript(t) else list(t) for t in texts]
+        ids, mem_of = [], []
+        for b, group in enumerate(cands):
+            for t in group:
+                ids.append(self._target_ids(t))
+                mem_of.append(b)
+        if not ids:
+            return [[] for _ in range(B)]
+        keys = [k for k in ("decoder", "ctc", "length_bonus", "lm") if k in bs.scorers]
+        speech = speech.to(self.device, torch.float32, non_blocking=True)
+        st = m.encode_device(speech, [int(n) for n in speech_lengths], isolate=True)
+        olens = torch.tensor(st.olens, dtype=torch.int32)
+        parts = []
+        for s in range(0, len(ids), self.nll_rows_per_call):
+            rows, mo = ids[s : s + self.nll_rows_per_call], mem_of[s : s + self.nll_rows_per_call]
+            u0, u1 = mo[0], mo[-1] + 1  # the slice's utterances
+            rel = [u - u0 for u in mo]
+            ylens = [len(y) for y in rows]
+            ys = torch.zeros(len(rows), max(max(ylens), 1), dtype=torch.long)
+            for i, y in enumerate(rows):
+                ys[i, : len(y)] = torch.tensor(y, dtype=torch.long)
+            col = {}
+            if "decoder" in keys:
+                col["decoder"] = -m._nll_rows(st.enc_act[u0:u1], olens[u0:u1], ys, torch.tensor(ylens),
+                                              mem_of=torch.tensor(rel, dtype=torch.int32))
+            if "ctc" in keys:
+                col["ctc"] = -m.ctc.nll_device(st.enc_act[u0:u1].contiguous(), st.olens[u0:u1], rows, ylens, m.blank_id,
+                                               mem_of=rel)
+            if "lm" in keys:
+                nll, _ = self.lm_model.nll(ys.to(self.device, non_blocking=True), torch.tensor(ylens))
+                col["lm"] = -nll.sum(dim=1)
+            if "length_bonus" in keys:
+                col["length_bonus"] = torch.tensor([n + 1.0 for n in ylens], dtype=torch.float32).to(self.device,
+                                                                                                     non_blocking=True)
+            parts.append(torch.stack([col[k] for k in keys], dim=1))
+        vals = torch.cat(parts).cpu().tolist()  # the one D2H copy
+        out, k = [], 0
+        for group in cands:
+            res = []
+            for _ in group:
+                scores = dict(zip(keys, vals[k]))
+                res.append(dict(token_int=ids[k], scores=scores,
+                                score=sum(float(bs.weights[kk]) * v for kk, v in scores.items())))
+                k += 1
+            out.append(res)
         return out
 
     def decode_greedy_device(self, st):

@@ -394,6 +394,7 @@ _SIGNATURES = {
                                       _sz, _vp]),
     "em_ctc_forced_align_workspace_bytes": (_sz, [_i32, _i32, _i32]),
     "em_ctc_forced_align_max_tokens": (_i32, []),
+    "em_ctc_seq_nll": (C.c_int, [_vp, _i32, _vp, _i32, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _vp, _vp]),
     "em_ngram_score": (C.c_int, [C.POINTER(EmNgramModel), _i32, _vp, _vp, _vp, _vp, _i32, _vp, _vp]),
     "em_arpa_count": (C.c_int, [C.c_char_p, _vp, _vp, _vp]),
     "em_arpa_load": (C.c_int, [C.c_char_p, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),

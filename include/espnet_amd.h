@@ -1171,6 +1171,31 @@ int em_ctc_forced_align(const float* lpT, int32_t ldT, const int32_t* xlens, con
 size_t em_ctc_forced_align_workspace_bytes(int32_t B, int32_t T, int32_t Lmax);
 int32_t em_ctc_forced_align_max_tokens(void);
 
+/* ---- CTC likelihood of given transcripts (csrc/ctc_nll.hip): the forward (sum-product) trellis, the per-utterance value
+ *      of CTC.forward with reduce=False under the builtin ctc_loss (espnet2/asr/ctc.py; torch.nn.functional.ctc_loss,
+ *      reduction "none", zero_infinity False), for a ragged batch of N candidate transcripts in one launch.
+ *      lpT [V][ldT] f32 = em_ctc_log_probs_t's output of Bm utterances (ldT >= Bm*T; utterance u's frames are the columns
+ *      u*T .. u*T + xlens[u] - 1), xlens [Bm]; targets [N][Lmax] (ids in [0, V), none equal to blank; the caller checks
+ *      that), ylens [N]; mem_of [N] the utterance of each candidate, or NULL: candidate n belongs to utterance n (then
+ *      N <= Bm).  With mem_of the candidates of an n-best list share their utterance's log-probabilities (as
+ *      em_dec_seq_nll's mem_of shares a memory); values outside [0, Bm) are clamped.  All on the device.
+ *   Per candidate n, u = mem_of[n], T_b = xlens[u], L = ylens[n], lp[t][v] = lpT[v][u*T + t]:
+ *      states s = 0 .. S-1, S = 2L + 1, lab[s] = blank (s even) or y[s >> 1] (s odd);
+ *      alpha[0][0] = lp[0][blank], alpha[0][1] = lp[0][y[0]] (L > 0), every other state -inf;
+ *      alpha[t][s] = logsumexp(alpha[t-1][s], alpha[t-1][s-1], alpha[t-1][s-2]) + lp[t][lab[s]], the move by two only for
+ *      odd s >= 3 with lab[s] != lab[s-2];
+ *      nll[n] = -logsumexp(alpha[T_b-1][S-1], alpha[T_b-1][S-2]), or -alpha[T_b-1][0] when L == 0.
+ *   All f32; every logsumexp is shifted by its largest term, and terms of -inf (all of them too) give -inf, never NaN.
+ *   (The kernel keeps alpha in the base-2 logarithm: each lp is multiplied by log2(e) once, the result by ln(2) once.)
+ *   A candidate that admits no path (T_b < L + number of adjacent equal tokens, or T_b == 0) is a defined result:
+ *      nll = +inf.  A row's value depends on its own transcript and its utterance's columns and on nothing else (bit for
+ *      bit, whatever N, Lmax and the companions are).
+ *   Transcripts up to Lmax = em_ctc_forced_align_max_tokens() (4 095) tokens; above: EM_ERR_UNSUPPORTED.  Any T, any N;
+ *   no workspace.  Enqueue only.                                                                                         */
+int em_ctc_seq_nll(const float* lpT, int32_t ldT, const int32_t* xlens, int32_t Bm, int32_t T, const int32_t* targets,
+                   int32_t Lmax, const int32_t* ylens, const int32_t* mem_of, int32_t N, int32_t blank, float* nll,
+                   void* stream);
+
 /* ---- transducer (RNN-T) decoding (csrc/transducer.hip): the prediction network as a decoder, the joint network and the
  *      greedy search.  Reference: espnet2/asr/decoder/transducer_decoder.py (TransducerDecoder), espnet2/asr_transducer/
  *      joint_network.py (JointNetwork), espnet2/asr/transducer/beam_search_transducer.py (BeamSearchTransducer), wired by
