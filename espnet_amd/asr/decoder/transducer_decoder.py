@@ -127,6 +127,36 @@ class TransducerDecoder(PackedModule):
                                                 L.current_stream_ptr()), "em_transducer_dec_step")
         return out[0], out[1], (hs_out, cs_out)
 
+    @torch.no_grad()
+    def teacher_forced_proj(self, ys: torch.Tensor, ylens: torch.Tensor, device=None) -> torch.Tensor:
+        """The prediction network run over given transcripts: ys (N, Lmax) token ids, ylens (N,) -> dec_proj
+        (Lmax + 1, N, jpad) f32 on the device, row (u, n) = lin_dec after candidate n has read blank, y_0 .. y_{u-1}
+        (what `em_transducer_lattice_logp` reads).  Lmax + 1 enqueued calls of `em_transducer_dec_step` over all N rows,
+        each writing its slice in place; the token column at u is blank at u = 0, then y_{u-1}, blank beyond a row's
+        length (those rows' slices are never read).  No read-back."""
+        if self.joint_network is None:
+            raise RuntimeError("TransducerDecoder needs its joint network (set_joint_network) for a device step")
+        ys = torch.as_tensor(ys)
+        N, Lmax = int(ys.shape[0]), int(ys.shape[1])
+        dev = torch.device(device) if device is not None else (ys.device if ys.is_cuda else torch.device("cuda"))
+        ys = ys.to(dev, torch.long, non_blocking=True)
+        lens = torch.as_tensor(ylens).to(dev, torch.long, non_blocking=True)
+        cols = torch.full((Lmax + 1, N), self.blank_id, dtype=torch.long, device=dev)
+        if Lmax > 0:
+            inside = torch.arange(Lmax, device=dev).unsqueeze(0) < lens.unsqueeze(1)
+            cols[1:] = torch.where(inside, ys, torch.full_like(ys, self.blank_id)).t()
+        cols = cols.to(torch.int32).contiguous()
+        w, keep = self.weights(dev)
+        out = torch.empty(Lmax + 1, N, w.jp, dtype=torch.float32, device=dev)
+        cur, nxt = self.init_state(N, dev), self.init_state(N, dev)
+        lib, stream = L.load(), L.current_stream_ptr()
+        for u in range(Lmax + 1):
+            L.check(lib.em_transducer_dec_step(self.em_dtype, C.byref(w), L.ptr(cols[u]), None, N, L.ptr(cur[0]),
+                                               L.ptr(cur[1]), L.ptr(nxt[0]), L.ptr(nxt[1]), None, L.ptr(out[u]), stream),
+                    "em_transducer_dec_step")
+            cur, nxt = nxt, cur
+        return out
+
     # ------------------------------------------------------------------ the reference's decoder interface
     def select_state(self, states, idx: int):
         """The state of row idx of a batch of states, (layers, 1, dpad) each."""

@@ -187,7 +187,7 @@ class ESPnetASRModel(torch.nn.Module):
         """(B,) f32: transcript b under the attention decoder given memory mem_of[b] (None: memory b)."""
         if self.use_transducer_decoder:
             raise RuntimeError("nll: this is a transducer model (joint network); the teacher-forced attention likelihood "
-                               "needs an attention decoder")
+                               "needs an attention decoder (the transducer's own likelihood: transducer_nll)")
         if self.decoder is None:
             raise RuntimeError("nll: the model has no attention decoder (ctc_weight == 1.0)")
         if not hasattr(self.decoder, "sequence_nll"):
@@ -219,6 +219,92 @@ class ESPnetASRModel(torch.nn.Module):
         for s in range(0, total_num, batch_size):
             e = min(s + batch_size, total_num)
             parts.append(self.nll(encoder_out[s:e], lens[s:e], ys_pad[s:e], ylens[s:e]))
+        return torch.cat(parts)
+
+    # ------------------------------------------------------------------ transducer likelihood of a transcript
+    @torch.no_grad()
+    def transducer_nll(self, encoder_out: torch.Tensor, encoder_out_lens, ys_pad, ys_pad_lens,
+                       mem_of=None, enc_proj=None) -> torch.Tensor:
+        """-log p(y | x) of every transcript under the transducer, the forward value of the RNN-T loss
+        (espnet_model.py `_calc_transducer_loss`), (N,) f32 on the device.  encoder_out (Bm, T, d) on the GPU,
+        encoder_out_lens (Bm,), ys_pad (N, Lmax) token ids, ys_pad_lens (N,); mem_of (N,) names the utterance of every
+        transcript (None: transcript n belongs to utterance n), so the candidates of an n-best list share their
+        utterance's projection.  A transcript may be empty; an utterance without frames gives +inf.  Token ids outside
+        [0, vocab_size) or equal to blank inside a transcript raise ValueError on the host.  Everything is enqueued: the
+        teacher-forced prediction network (`TransducerDecoder.teacher_forced_proj`), `em_transducer_lattice_logp` and
+        `em_transducer_seq_nll`; the (N, T, U, V) joint output never exists.  A batch whose lattice is outside the
+        shapes of one call goes through in slices of candidates.  `enc_proj`: `joint_network.enc_proj_device(encoder_out)`
+        when the caller holds it already (several calls on one batch of utterances)."""
+        if not self.use_transducer_decoder:
+            raise RuntimeError("transducer_nll: the model has no joint network (decoder: transducer); the attention "
+                               "decoder's likelihood is `nll`")
+        ys = torch.as_tensor(ys_pad).detach().to("cpu", torch.long)
+        ylens = torch.as_tensor(ys_pad_lens).detach().to("cpu", torch.long)
+        xlens = torch.as_tensor(encoder_out_lens).detach().to("cpu", torch.long)
+        if ys.dim() != 2 or ylens.dim() != 1 or ys.size(0) != ylens.size(0) or ys.size(0) == 0:
+            raise ValueError(f"ys_pad (N, L) and ys_pad_lens (N,) expected, got {tuple(ys.shape)}, {tuple(ylens.shape)}")
+        N, Bm, T = int(ys.size(0)), int(encoder_out.shape[0]), int(encoder_out.shape[1])
+        if xlens.dim() != 1 or xlens.numel() != Bm or int(xlens.min()) < 0 or int(xlens.max()) > T:
+            raise ValueError(f"encoder_out_lens must hold {Bm} lengths in [0, {T}]")
+        longest, shortest = int(ylens.max()), int(ylens.min())
+        if shortest < 0 or longest > ys.size(1):
+            raise ValueError(f"ys_pad_lens must lie in [0, {ys.size(1)}], got {shortest} .. {longest}")
+        ys = ys[:, :longest]
+        inside = torch.arange(longest).unsqueeze(0) < ylens.unsqueeze(1)
+        if bool((((ys < 0) | (ys >= self.vocab_size)) & inside).any()):
+            raise ValueError(f"token ids must lie in [0, {self.vocab_size})")
+        if bool(((ys == self.blank_id) & inside).any()):
+            raise ValueError(f"token id {self.blank_id} (<blank>) cannot be part of a transcript")
+        if mem_of is None:
+            if N > Bm:
+                raise ValueError(f"{N} transcripts for {Bm} utterances need mem_of")
+            mo = None
+        else:
+            mo = torch.as_tensor(mem_of).detach().to("cpu", torch.long)
+            if mo.dim() != 1 or mo.numel() != N or int(mo.min()) < 0 or int(mo.max()) >= Bm:
+                raise ValueError(f"mem_of must hold {N} utterance numbers in [0, {Bm})")
+        L.require_gpu(encoder_out, "encoder_out")
+        dev, dec, jn = encoder_out.device, self.decoder, self.joint_network
+        cap = int(L.load().em_transducer_seq_nll_max_tokens())
+        if longest > cap:
+            raise NotImplementedError(f"transducer_nll: a transcript of {longest} tokens, the recursion takes up to {cap}")
+        rows = N
+        while rows > 1 and jn.lattice_workspace_bytes(dec, dev, rows, T, longest) == 0:
+            rows = (rows + 1) // 2
+        if jn.lattice_workspace_bytes(dec, dev, rows, T, longest) == 0:
+            raise NotImplementedError(f"transducer_nll: the lattice of one candidate, {T} frames x {longest} tokens, is "
+                                      "outside the shapes of one call")
+        if enc_proj is None:
+            enc_proj = jn.enc_proj_device(encoder_out)
+        xl = xlens.to(torch.int32).to(dev, non_blocking=True)
+        parts = []
+        for s in range(0, N, rows):
+            e = min(s + rows, N)
+            if mo is None and rows < N:  # (a slice of candidates that own their utterances: name them)
+                mem = torch.arange(s, e, dtype=torch.int32).to(dev, non_blocking=True)
+            else:
+                mem = None if mo is None else mo[s:e].to(torch.int32).to(dev, non_blocking=True)
+            yl = ylens[s:e].to(torch.int32).to(dev, non_blocking=True)
+            tg = ys[s:e].to(torch.int32).contiguous().to(dev, non_blocking=True)
+            dec_proj = dec.teacher_forced_proj(tg, yl, device=dev)
+            lat = jn.lattice_logp_device(dec, enc_proj, xl, dec_proj, tg, yl, mem)
+            parts.append(jn.seq_nll_device(lat, xl, yl, mem))
+        return parts[0] if len(parts) == 1 else torch.cat(parts)
+
+    @torch.no_grad()
+    def batchify_transducer_nll(self, encoder_out: torch.Tensor, encoder_out_lens, ys_pad, ys_pad_lens,
+                                batch_size: int = 100) -> torch.Tensor:
+        """`transducer_nll` in slices of batch_size utterances, concatenated (the shape of `batchify_nll`)."""
+        total_num = encoder_out.size(0)
+        if batch_size < 1:
+            raise ValueError(f"batch_size must be positive, got {batch_size}")
+        if total_num <= batch_size:
+            return self.transducer_nll(encoder_out, encoder_out_lens, ys_pad, ys_pad_lens)
+        lens, ys, ylens = torch.as_tensor(encoder_out_lens), torch.as_tensor(ys_pad), torch.as_tensor(ys_pad_lens)
+        parts = []
+        for s in range(0, total_num, batch_size):
+            e = min(s + batch_size, total_num)
+            parts.append(self.transducer_nll(encoder_out[s:e], lens[s:e], ys[s:e], ylens[s:e]))
         return torch.cat(parts)
 
     # ------------------------------------------------------------------ greedy CTC (G1)

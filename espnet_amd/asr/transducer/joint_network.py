@@ -83,6 +83,49 @@ class JointNetwork(PackedModule):
                 "em_transducer_joint_logp")
         return logp
 
+    # ------------------------------------------------------------------ likelihood of given transcripts (csrc/transducer_nll.hip)
+    def lattice_workspace_bytes(self, decoder, device, N: int, T: int, Lmax: int) -> int:
+        """`em_transducer_lattice_logp_workspace_bytes`: 0 when the shape is not covered in one call."""
+        w, keep = decoder.weights(device)
+        return int(L.load().em_transducer_lattice_logp_workspace_bytes(self.em_dtype, C.byref(w), N, T, Lmax))
+
+    @torch.no_grad()
+    def lattice_logp_device(self, decoder, enc_proj, xlens, dec_proj, targets, ylens, mem_of=None, out=None, ws=None):
+        """`em_transducer_lattice_logp`: the blank's and the next label's log-probability at every node (t < xlens[m],
+        u <= ylens[n]) of N candidates' lattices, lat (N, T, Lmax + 1, 2) f32; the other nodes are not written.
+        enc_proj (Bm, T, jpad) f32 (`enc_proj_device`), xlens (Bm,) int32, dec_proj (Lmax + 1, N, jpad) f32
+        (`TransducerDecoder.teacher_forced_proj`), targets (N, Lmax) int32, ylens (N,) int32, mem_of (N,) int32 or None,
+        all on the device.  `out`: a lattice to write into; `ws`: a uint8 workspace (default: one of the size the library
+        asks for)."""
+        L.require_gpu(enc_proj, "enc_proj")
+        dev = enc_proj.device
+        Bm, T = int(enc_proj.shape[0]), int(enc_proj.shape[1])
+        N, Lmax = int(dec_proj.shape[1]), int(dec_proj.shape[0]) - 1
+        w, keep = decoder.weights(dev)
+        lib = L.load()
+        if ws is None:
+            need = int(lib.em_transducer_lattice_logp_workspace_bytes(self.em_dtype, C.byref(w), N, T, Lmax))
+            if need == 0:
+                raise NotImplementedError(f"em_transducer_lattice_logp: {N} candidates x {T} frames x {Lmax} tokens are "
+                                          "outside the shapes of one call")
+            ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        lat = out if out is not None else torch.empty(N, T, Lmax + 1, 2, dtype=torch.float32, device=dev)
+        L.check(lib.em_transducer_lattice_logp(self.em_dtype, C.byref(w), L.ptr(enc_proj), L.ptr(xlens), Bm, T, L.ptr(dec_proj),
+                                               L.ptr(targets), Lmax, L.ptr(ylens), L.ptr(mem_of), N, L.ptr(lat), L.ptr(ws),
+                                               int(ws.numel()), L.current_stream_ptr()), "em_transducer_lattice_logp")
+        return lat
+
+    @torch.no_grad()
+    def seq_nll_device(self, lat, xlens, ylens, mem_of=None) -> torch.Tensor:
+        """`em_transducer_seq_nll`: the forward recursion over lat (N, T, Lmax + 1, 2) f32 -> -log p(y | x), (N,) f32;
+        +inf for a candidate whose utterance has no frame.  xlens (Bm,), ylens (N,), mem_of (N,) or None: int32, device."""
+        L.require_gpu(lat, "lat")
+        N, T, Lmax = int(lat.shape[0]), int(lat.shape[1]), int(lat.shape[2]) - 1
+        nll = torch.empty(N, dtype=torch.float32, device=lat.device)
+        L.check(L.load().em_transducer_seq_nll(L.ptr(lat), L.ptr(xlens), int(xlens.numel()), T, Lmax, L.ptr(ylens),
+                                               L.ptr(mem_of), N, L.ptr(nll), L.current_stream_ptr()), "em_transducer_seq_nll")
+        return nll
+
     @torch.no_grad()
     def forward(self, enc_out: torch.Tensor, dec_out: torch.Tensor) -> torch.Tensor:
         raise NotImplementedError("JointNetwork.forward on broadcast (B, T, U) lattices is training only; decoding goes "

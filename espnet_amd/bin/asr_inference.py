@@ -363,6 +363,52 @@ class Speech2Text:
             k += len(group)
         return out
 
+    # ------------------------------------------------------------------ transducer likelihood of given transcripts
+    @torch.no_grad()
+    def batch_transducer_nll(self, speech: torch.Tensor, speech_lengths: Sequence[int], texts):
+        """-log p(y | x) of given transcripts under a transducer model (`ESPnetASRModel.transducer_nll`, the forward value of
+        the RNN-T loss): speech, speech_lengths and texts as `batch_nll` takes them - texts[b] one transcript or a list of
+        candidates of utterance b, strings or token ids, an empty transcript allowed.  Returns one list of floats per
+        utterance, a value per candidate.  The utterances are encoded as `batch_decode` encodes them; the candidates go
+        through in slices of `nll_rows_per_call` and share their utterance's joint-network projection.  One D2H copy per
+        call."""
+        m = self.asr_model
+        if not getattr(m, "use_transducer_decoder", False):
+            raise RuntimeError("batch_transducer_nll: the model has no joint network (decoder: transducer); the attention "
+                               "decoder's likelihood is batch_nll")
+        B = int(speech.shape[0])
+        if len(texts) != B:
+            raise ValueError(f"{len(texts)} transcript entries for {B} utterances")
+        cands = [[t] if self._is_one_transcript(t) else list(t) for t in texts]
+        ids, mem_of = [], []
+        for b, group in enumerate(cands):
+            for t in group:
+                y = self._target_ids(t)
+                if any(v < 0 or v >= m.vocab_size for v in y):
+                    raise ValueError(f"token ids must lie in [0, {m.vocab_size})")
+                ids.append(y)
+                mem_of.append(b)
+        if not ids:
+            return [[] for _ in range(B)]
+        speech = speech.to(self.device, torch.float32, non_blocking=True)
+        st = m.encode_device(speech, [int(n) for n in speech_lengths], isolate=True)
+        olens = torch.tensor(st.olens, dtype=torch.int32)
+        enc_proj = m.joint_network.enc_proj_device(st.enc_act)  # once for the batch: every slice reads the same rows
+        parts = []
+        for s in range(0, len(ids), self.nll_rows_per_call):
+            rows, mo = ids[s : s + self.nll_rows_per_call], mem_of[s : s + self.nll_rows_per_call]
+            ys = torch.zeros(len(rows), max(len(y) for y in rows), dtype=torch.long)
+            for i, y in enumerate(rows):
+                ys[i, : len(y)] = torch.tensor(y, dtype=torch.long)
+            parts.append(m.transducer_nll(st.enc_act, olens, ys, torch.tensor([len(y) for y in rows]),
+                                          mem_of=torch.tensor(mo, dtype=torch.int32), enc_proj=enc_proj))
+        vals = torch.cat(parts).cpu().tolist()  # the one D2H copy
+        out, k = [], 0
+        for group in cands:
+            out.append(vals[k : k + len(group)])
+            k += len(group)
+        return out
+
     # ------------------------------------------------------------------ the joint score of given transcripts
     @torch.no_grad()
     def batch_rescore(self, speech: torch.Tensor, speech_lengths: Sequence[int], texts):
@@ -385,7 +431,7 @@ class Speech2Text:
                                "score it could give")
         if self.beam_search is None:
             raise RuntimeError("batch_rescore: this is a transducer model; the joint CTC/attention score needs the joint "
-                               "search's scorers")
+                               "search's scorers (the transducer's own likelihood: batch_transducer_nll)")
         if self.ngram is not None:
             raise NotImplementedError("batch_rescore with ngram_file: whole-sentence n-gram scoring is not implemented")
         m, bs = self.asr_model, self.beam_search

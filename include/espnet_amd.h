@@ -1246,6 +1246,48 @@ int em_transducer_greedy(int dtype, const EmTransducerWeights* w, const float* e
                          float* frame_margin, void* ws, size_t ws_bytes, void* stream);
 size_t em_transducer_greedy_workspace_bytes(int dtype, const EmTransducerWeights* w, int32_t B, int32_t T);
 
+/* ---- transducer likelihood of given transcripts (csrc/transducer_nll.hip): log p(y | x) of a ragged batch of N candidate
+ *      transcripts, the forward value of the RNN-T loss (espnet2/asr/espnet_model.py `_calc_transducer_loss`), in two
+ *      calls: the joint network's two wanted log-probabilities at every lattice node, then the forward (sum-product)
+ *      recursion over the lattice.  All pointers on the device; both calls only enqueue.
+ *   em_transducer_lattice_logp.  enc_proj [Bm][T][jp] f32 the caller's product (see above), xlens [Bm]; dec_proj
+ *      [Lmax+1][N][jp] f32, row (u, n) = lin_dec of the prediction network after it has read blank, y_0 .. y_{u-1} of
+ *      candidate n (Lmax + 1 calls of em_transducer_dec_step over all N rows); targets [N][Lmax] (ids in [0, vocab), none
+ *      equal to w->blank; the caller checks that), ylens [N]; mem_of [N] the utterance of each candidate, or NULL:
+ *      candidate n belongs to utterance n (then N <= Bm), with the meaning and the clamping of em_ctc_seq_nll's - the
+ *      candidates of an n-best list share their utterance's enc_proj.  Of w only lin_out, out_b, vocab, joint, jp and
+ *      blank are read.
+ *   Per candidate n, m = mem_of[n], T_b = xlens[m] (clamped to [0, T]), U = ylens[n] (clamped to [0, Lmax]), for every
+ *      t < T_b and u <= U:
+ *        z        = tanh(enc_proj[m][t] + dec_proj[u][n]) in f32, rounded once to the compute dtype;
+ *        logit[v] = z . lin_out[v] + out_b[v], accumulated in f32;  lse = logsumexp over v < vocab;
+ *        lat[((n*T + t)*(Lmax+1) + u)*2 + 0] = logit[blank] - lse;
+ *        lat[((n*T + t)*(Lmax+1) + u)*2 + 1] = logit[targets[n][u]] - lse for u < U, -inf for u == U.
+ *      Nodes with t >= T_b or u > U are neither computed nor written: only valid nodes form the row tiles of the launch.
+ *      The logits and the (node, jp) matrix z never reach memory.  A node's two values depend on its own two projection
+ *      rows and the weights and on nothing else: bit for bit the same whatever N, Lmax, mem_of and the other nodes are.
+ *      bf16 runs on the matrix cores (jp <= 1 024), f32 is the parity path.
+ *   N * T * (Lmax+1) <= 2^28 nodes and Lmax <= em_transducer_seq_nll_max_tokens(); other shapes: EM_ERR_UNSUPPORTED, and
+ *      em_transducer_lattice_logp_workspace_bytes returns 0 for them.  ws: that many bytes of device memory (the row list
+ *      of the valid nodes); a smaller one: EM_ERR_WORKSPACE.
+ *   em_transducer_seq_nll.  With b = lat[..][0], e = lat[..][1] of candidate n, T_b and U as above:
+ *        alpha[0][0] = 0
+ *        alpha[t][u] = logaddexp(alpha[t-1][u] + b[t-1][u], alpha[t][u-1] + e[t][u-1])   (a missing neighbour is -inf)
+ *        nll[n]      = -(alpha[T_b-1][U] + b[T_b-1][U]);  T_b == 0: +inf.
+ *      All f32; every logaddexp is shifted by its larger term, and terms of -inf (both too) give -inf, never NaN.  Only
+ *      the nodes t < T_b, u <= U are read.  One launch for all candidates; a row's value depends on its own lattice only
+ *      (bit for bit, whatever N, Lmax and the companions are).  Transcripts up to Lmax =
+ *      em_transducer_seq_nll_max_tokens() (1 023) tokens; above: EM_ERR_UNSUPPORTED.  No workspace.                       */
+int em_transducer_lattice_logp(int dtype, const EmTransducerWeights* w, const float* enc_proj, const int32_t* xlens,
+                               int32_t Bm, int32_t T, const float* dec_proj, const int32_t* targets, int32_t Lmax,
+                               const int32_t* ylens, const int32_t* mem_of, int32_t N, float* lat, void* ws, size_t ws_bytes,
+                               void* stream);
+size_t em_transducer_lattice_logp_workspace_bytes(int dtype, const EmTransducerWeights* w, int32_t N, int32_t T,
+                                                  int32_t Lmax);
+int em_transducer_seq_nll(const float* lat, const int32_t* xlens, int32_t Bm, int32_t T, int32_t Lmax, const int32_t* ylens,
+                          const int32_t* mem_of, int32_t N, float* nll, void* stream);
+int32_t em_transducer_seq_nll_max_tokens(void);
+
 /* ---- §8(f) rank 3: block-synchronous streaming search, BatchBeamSearchOnline
  *      (espnet2/legacy/nets/batch_beam_search_online.py:155-534).  The host mirrors the reference's
  *      control flow (block loop :296-376, process_one_block :394-493: repetition / local-<eos> breaks,
