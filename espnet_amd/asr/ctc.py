@@ -101,6 +101,50 @@ class CTC(PackedModule):
                 raise ValueError(f"utterance {b}: {int(T_b)} encoder frames cannot carry {len(y)} tokens "
                                  f"({need} frames needed)")
 
+    def _trellis_inputs(self, enc_act, olens, targets, ylens, blank, mem_of, align: bool):
+        """The arguments of `forced_align_device` (align: one transcript per utterance, enough frames for it) and
+        `nll_device` (N transcripts, mem_of or None) as device tensors: all HOST data is checked and copied over, all
+        int32 DEVICE tensors are taken as they are, a mixture is refused.  Returns (olens_d, tg_d, ylens_d, mem_of_d or
+        None, N, Lmax); tg_d's row stride is max(Lmax, 1)."""
+        Bm, T, _ = enc_act.shape
+        dev = enc_act.device
+        given = (olens, targets, ylens) + (() if mem_of is None else (mem_of,))
+        names = ["olens", "targets", "ylens"] + ([] if align else ["mem_of"])
+        on_dev = [torch.is_tensor(x) and x.is_cuda for x in given]
+        if all(on_dev):
+            if any(x.dtype != torch.int32 for x in given) or targets.dim() != 2:
+                raise ValueError(f"device-side {' / '.join(names)} must be int32, targets ({'B' if align else 'N'}, Lmax)")
+            olens_d, tg_d, ylens_d = olens.contiguous(), targets.contiguous(), ylens.contiguous()
+            mo_d = None if mem_of is None else mem_of.contiguous()
+            N, Lmax = int(targets.shape[0]), int(targets.shape[1])
+            if not align and (int(olens_d.numel()) != Bm or int(ylens_d.numel()) != N
+                              or (mo_d is not None and int(mo_d.numel()) != N)):
+                raise ValueError(f"olens must have {Bm} entries, ylens and mem_of {N}")
+            return olens_d, tg_d, ylens_d, mo_d, N, Lmax
+        if any(on_dev):
+            raise ValueError(f"{', '.join(names[:-1])} and {names[-1]} must be all host data or all device tensors")
+        ol, rows, yl, mo = [x.tolist() if torch.is_tensor(x) else list(x) for x in given] + ([None] if mem_of is None else [])
+        N = len(rows)
+        if align:
+            if len(ol) != Bm or len(yl) != Bm or N != Bm:
+                raise ValueError(f"olens, targets and ylens must have {Bm} rows")
+        elif len(ol) != Bm or len(yl) != N or (mo is not None and len(mo) != N):
+            raise ValueError(f"olens must have {Bm} entries, ylens and mem_of as many as targets ({N})")
+        if any(n < 0 or n > len(r) for n, r in zip(yl, rows)) or any(n < 0 or n > T for n in ol):
+            raise ValueError("a length lies outside its row")
+        if mo is not None and any(u < 0 or u >= Bm for u in mo):
+            raise ValueError(f"mem_of must lie in [0, {Bm})")
+        rows = [[int(v) for v in r[:n]] for r, n in zip(rows, yl)]
+        # (the likelihood checks the ids only: too few frames give +inf there, not an error)
+        self.check_alignable(ol if align else [2 ** 31] * N, rows, blank, self.odim)
+        Lmax = max(yl) if yl else 0
+        tg = torch.zeros(max(N, 1), max(Lmax, 1), dtype=torch.int32)
+        for n, r in enumerate(rows):
+            tg[n, : len(r)] = torch.tensor(r, dtype=torch.int32)
+        olens_d, ylens_d, tg_d = (torch.as_tensor(v, dtype=torch.int32).to(dev, non_blocking=True) for v in (ol, yl, tg))
+        mo_d = None if mo is None else torch.tensor(mo, dtype=torch.int32).to(dev, non_blocking=True)
+        return olens_d, tg_d, ylens_d, mo_d, N, Lmax
+
     def forced_align_device(self, enc_act: torch.Tensor, olens, targets, ylens, blank: int):
         """Viterbi alignment of `targets` to the CTC posteriors of enc_act (B,T,d) (compute dtype, on the device) for a
         ragged batch, by `em_ctc_log_probs_t` -> `em_ctc_forced_align` (include/espnet_amd.h states the recursion and
@@ -114,31 +158,7 @@ class CTC(PackedModule):
         L.require_gpu(enc_act, "enc_act")
         B, T, d = enc_act.shape
         dev, V = enc_act.device, self.odim
-        on_dev = [torch.is_tensor(x) and x.is_cuda for x in (olens, targets, ylens)]
-        if all(on_dev):
-            if any(x.dtype != torch.int32 for x in (olens, targets, ylens)) or targets.dim() != 2:
-                raise ValueError("device-side olens / targets / ylens must be int32, targets (B, Lmax)")
-            olens_d, tg_d, ylens_d = olens.contiguous(), targets.contiguous(), ylens.contiguous()
-            Lmax = int(targets.shape[1])
-        elif any(on_dev):
-            raise ValueError("olens, targets and ylens must be all host data or all device tensors")
-        else:
-            ol = [int(v) for v in (olens.tolist() if torch.is_tensor(olens) else olens)]
-            yl = [int(v) for v in (ylens.tolist() if torch.is_tensor(ylens) else ylens)]
-            rows = targets.tolist() if torch.is_tensor(targets) else [list(r) for r in targets]
-            if len(ol) != B or len(yl) != B or len(rows) != B:
-                raise ValueError(f"olens, targets and ylens must have {B} rows")
-            if any(n < 0 or n > len(r) for n, r in zip(yl, rows)) or any(n < 0 or n > T for n in ol):
-                raise ValueError("a length lies outside its row")
-            rows = [r[:n] for r, n in zip(rows, yl)]
-            self.check_alignable(ol, rows, blank, V)
-            Lmax = max(yl) if yl else 0
-            tg = torch.zeros(B, max(Lmax, 1), dtype=torch.int32)
-            for b, r in enumerate(rows):
-                tg[b, : len(r)] = torch.tensor(r, dtype=torch.int32)
-            olens_d = torch.tensor(ol, dtype=torch.int32).to(dev, non_blocking=True)
-            ylens_d = torch.tensor(yl, dtype=torch.int32).to(dev, non_blocking=True)
-            tg_d = tg[:, :Lmax].contiguous().to(dev, non_blocking=True) if Lmax else tg.to(dev, non_blocking=True)
+        olens_d, tg_d, ylens_d, _, _, Lmax = self._trellis_inputs(enc_act, olens, targets, ylens, blank, None, align=True)
         lib, st = L.load(), L.current_stream_ptr()
         ws_bytes = int(lib.em_ctc_forced_align_workspace_bytes(B, T, Lmax))
         p = self.packed(dev)
@@ -191,37 +211,7 @@ class CTC(PackedModule):
         L.require_gpu(enc_act, "enc_act")
         Bm, T, d = enc_act.shape
         dev, V = enc_act.device, self.odim
-        given = (olens, targets, ylens) + (() if mem_of is None else (mem_of,))
-        on_dev = [torch.is_tensor(x) and x.is_cuda for x in given]
-        if all(on_dev):
-            if any(x.dtype != torch.int32 for x in given) or targets.dim() != 2:
-                raise ValueError("device-side olens / targets / ylens / mem_of must be int32, targets (N, Lmax)")
-            olens_d, tg_d, ylens_d = olens.contiguous(), targets.contiguous(), ylens.contiguous()
-            mo_d = None if mem_of is None else mem_of.contiguous()
-            N, Lmax = int(targets.shape[0]), int(targets.shape[1])
-            if int(olens_d.numel()) != Bm or int(ylens_d.numel()) != N or (mo_d is not None and int(mo_d.numel()) != N):
-                raise ValueError(f"olens must have {Bm} entries, ylens and mem_of {N}")
-        elif any(on_dev):
-            raise ValueError("olens, targets, ylens and mem_of must be all host data or all device tensors")
-        else:
-            ol, rows, yl, mo = [x.tolist() if torch.is_tensor(x) else list(x) for x in given] + ([None] if mem_of is None else [])
-            N = len(rows)
-            if len(ol) != Bm or len(yl) != N or (mo is not None and len(mo) != N):
-                raise ValueError(f"olens must have {Bm} entries, ylens and mem_of as many as targets ({N})")
-            if any(n < 0 or n > len(r) for n, r in zip(yl, rows)) or any(n < 0 or n > T for n in ol):
-                raise ValueError("a length lies outside its row")
-            if mo is not None and any(u < 0 or u >= Bm for u in mo):
-                raise ValueError(f"mem_of must lie in [0, {Bm})")
-            rows = [[int(v) for v in r[:n]] for r, n in zip(rows, yl)]
-            self.check_alignable([2 ** 31] * N, rows, blank, V)  # (the ids only: too few frames give +inf, not an error)
-            Lmax = max(yl) if yl else 0
-            tg = torch.zeros(max(N, 1), max(Lmax, 1), dtype=torch.int32)
-            for n, r in enumerate(rows):
-                tg[n, : len(r)] = torch.tensor(r, dtype=torch.int32)
-            olens_d = torch.tensor(ol, dtype=torch.int32).to(dev, non_blocking=True)
-            ylens_d = torch.tensor(yl, dtype=torch.int32).to(dev, non_blocking=True)
-            tg_d = tg[:, : max(Lmax, 1)].contiguous().to(dev, non_blocking=True)
-            mo_d = None if mo is None else torch.tensor(mo, dtype=torch.int32).to(dev, non_blocking=True)
+        olens_d, tg_d, ylens_d, mo_d, N, Lmax = self._trellis_inputs(enc_act, olens, targets, ylens, blank, mem_of, align=False)
         if N == 0:
             return torch.empty(0, dtype=torch.float32, device=dev)
         if mo_d is None and N != Bm:

@@ -294,6 +294,14 @@ class TransformerDecoder(PackedModule, BatchScorerInterface):
         if bool(bad):
             raise ValueError(f"sequence_nll: token ids must lie in [0, {V}), memory lengths in [1, {T}] and mem_of in "
                              f"[0, {Bm})")
+        return self._sequence_nll(hs_pad, kl, xi, ki, ti, mo)
+
+    def _sequence_nll(self, hs_pad, kl, xi, ki, ti, mo) -> torch.Tensor:
+        """`sequence_nll` behind its checks: hs_pad (Bm, T, d) contiguous, the rest contiguous int32 device tensors taken
+        as given (the caller has checked their values), mo None or (B,).  Only enqueues."""
+        dev = hs_pad.device
+        Bm, T, d = hs_pad.shape
+        B, Lp = xi.shape
         if d % self.heads or d // self.heads not in (32, 64):
             raise NotImplementedError(f"sequence_nll: heads of {d // self.heads} channels (d {d}, {self.heads} heads); the "
                                       "device path covers 32 and 64")

@@ -183,8 +183,10 @@ class ESPnetASRModel(torch.nn.Module):
         return self.frontend(speech, speech_lengths)
 
     # ------------------------------------------------------------------ attention-decoder likelihood of a transcript
-    def _nll_rows(self, encoder_out, encoder_out_lens, ys_pad, ys_pad_lens, mem_of=None) -> torch.Tensor:
-        """(B,) f32: transcript b under the attention decoder given memory mem_of[b] (None: memory b)."""
+    def _nll_rows(self, encoder_out, encoder_out_lens, ys_pad, ys_pad_lens, mem_of=None, checked=False) -> torch.Tensor:
+        """(B,) f32: transcript b under the attention decoder given memory mem_of[b] (None: memory b).  `checked`: the
+        caller vouches for HOST ys_pad (ids in the vocabulary), lengths in [1, T] and mem_of, so nothing is verified on
+        the device and no verdict is read back - the call only enqueues."""
         if self.use_transducer_decoder:
             raise RuntimeError("nll: this is a transducer model (joint network); the teacher-forced attention likelihood "
                                "needs an attention decoder (the transducer's own likelihood: transducer_nll)")
@@ -193,6 +195,11 @@ class ESPnetASRModel(torch.nn.Module):
         if not hasattr(self.decoder, "sequence_nll"):
             raise RuntimeError(f"nll: {type(self.decoder).__name__} has no whole-sequence scoring path")
         x, keymask, target = build_dec_nll_batch(ys_pad, ys_pad_lens, self.sos, self.eos, self.vocab_size)
+        if checked:
+            dev = encoder_out.device
+            kl, xi, ki, ti, mo = (None if v is None else v.to(torch.int32).contiguous().to(dev, non_blocking=True)
+                                  for v in (encoder_out_lens, x, keymask, target, mem_of))
+            return self.decoder._sequence_nll(encoder_out.contiguous(), kl, xi, ki, ti, mo).sum(dim=1)
         return self.decoder.sequence_nll(encoder_out, encoder_out_lens, x, keymask, target, mem_of=mem_of).sum(dim=1)
 
     @torch.no_grad()
@@ -209,17 +216,19 @@ class ESPnetASRModel(torch.nn.Module):
     def batchify_nll(self, encoder_out: torch.Tensor, encoder_out_lens: torch.Tensor, ys_pad: torch.Tensor,
                      ys_pad_lens: torch.Tensor, batch_size: int = 100) -> torch.Tensor:
         """espnet_model.py `batchify_nll`: `nll` in slices of batch_size utterances, concatenated."""
+        return self._in_slices(self.nll, batch_size, encoder_out, encoder_out_lens, ys_pad, ys_pad_lens)
+
+    @staticmethod
+    def _in_slices(score, batch_size: int, encoder_out: torch.Tensor, *per_utt) -> torch.Tensor:
+        """score(encoder_out, *per_utt) over slices of batch_size utterances, concatenated."""
         total_num = encoder_out.size(0)
         if batch_size < 1:
             raise ValueError(f"batch_size must be positive, got {batch_size}")
         if total_num <= batch_size:
-            return self.nll(encoder_out, encoder_out_lens, ys_pad, ys_pad_lens)
-        lens, ylens = torch.as_tensor(encoder_out_lens), torch.as_tensor(ys_pad_lens)
-        parts = []
-        for s in range(0, total_num, batch_size):
-            e = min(s + batch_size, total_num)
-            parts.append(self.nll(encoder_out[s:e], lens[s:e], ys_pad[s:e], ylens[s:e]))
-        return torch.cat(parts)
+            return score(encoder_out, *per_utt)
+        per_utt = [torch.as_tensor(v) for v in per_utt]
+        return torch.cat([score(encoder_out[s : s + batch_size], *(v[s : s + batch_size] for v in per_utt))
+                          for s in range(0, total_num, batch_size)])
 
     # ------------------------------------------------------------------ transducer likelihood of a transcript
     @torch.no_grad()
@@ -295,17 +304,7 @@ class ESPnetASRModel(torch.nn.Module):
     def batchify_transducer_nll(self, encoder_out: torch.Tensor, encoder_out_lens, ys_pad, ys_pad_lens,
                                 batch_size: int = 100) -> torch.Tensor:
         """`transducer_nll` in slices of batch_size utterances, concatenated (the shape of `batchify_nll`)."""
-        total_num = encoder_out.size(0)
-        if batch_size < 1:
-            raise ValueError(f"batch_size must be positive, got {batch_size}")
-        if total_num <= batch_size:
-            return self.transducer_nll(encoder_out, encoder_out_lens, ys_pad, ys_pad_lens)
-        lens, ys, ylens = torch.as_tensor(encoder_out_lens), torch.as_tensor(ys_pad), torch.as_tensor(ys_pad_lens)
-        parts = []
-        for s in range(0, total_num, batch_size):
-            e = min(s + batch_size, total_num)
-            parts.append(self.transducer_nll(encoder_out[s:e], lens[s:e], ys[s:e], ylens[s:e]))
-        return torch.cat(parts)
+        return self._in_slices(self.transducer_nll, batch_size, encoder_out, encoder_out_lens, ys_pad, ys_pad_lens)
 
     # ------------------------------------------------------------------ greedy CTC (G1)
     def greedy_ctc_device(self, st: EncoderState, out=None):

@@ -15,6 +15,7 @@ Decoding modes
     espnet2/legacy/nets/batch_beam_search.py) — see espnet_amd/nets/.
 The log markers "speech length: N" and "best hypo: ..." that utils/calculate_rtf.py parses are kept.
 """
+import functools
 import logging
 from pathlib import Path
 from typing import Any, Dict, List, NamedTuple, Optional, Sequence, Tuple, Union
@@ -24,6 +25,7 @@ import torch
 
 from espnet_amd.lib import TooShortUttError
 from espnet_amd.nets.beam_search import Hypothesis
+from espnet_amd.nets.candidates import CandidateBatch, is_one_transcript
 from espnet_amd.nets_utils import SUBSAMPLING_CONVS
 from espnet_amd.tasks.asr import ASRTask
 from espnet_amd.text.token_id_converter import TokenIDConverter, build_tokenizer
@@ -318,11 +320,29 @@ class Speech2Text:
     # ------------------------------------------------------------------ attention-decoder likelihood of given transcripts
     nll_rows_per_call = 100  # candidates per enqueue (ESPnetASRModel.batchify_nll's default slice)
 
-    @staticmethod
-    def _is_one_transcript(t) -> bool:
-        if isinstance(t, str) or hasattr(t, "tolist"):
-            return True
-        return len(t) == 0 or all(isinstance(v, (int, np.integer)) for v in t)
+    _is_one_transcript = staticmethod(is_one_transcript)
+
+    def _candidates(self, speech, texts, lm: bool = False) -> CandidateBatch:
+        """texts -> the checked candidate batch of the `batch_*` scorers: every ValueError of theirs, before any encode.
+        The ids are bounded by the model's vocabulary (`lm`: and the LM's), so no scorer has to verify them on the device."""
+        V = getattr(self.asr_model, "vocab_size", None)
+        if lm and V is not None:
+            V = min(V, getattr(self.lm_model.lm, "vocab_size", V))
+        return CandidateBatch(texts, int(speech.shape[0]), self._target_ids, V)
+
+    def _enqueue_candidates(self, speech, speech_lengths, cb: CandidateBatch, score, min_width: int = 1) -> torch.Tensor:
+        """The shared driver of the `batch_*` scorers up to their one D2H copy: encodes the utterances once (as
+        `batch_decode` does) and runs the candidates through score(st, olens, sl) in slices of `nll_rows_per_call` - st
+        the EncoderState, olens its (B,) int32 host lengths, sl a `CandidateSlice`.  Returns the slices' device tensors
+        concatenated; only enqueues."""
+        speech = speech.to(self.device, torch.float32, non_blocking=True)
+        st = self.asr_model.encode_device(speech, [int(n) for n in speech_lengths], isolate=True)
+        olens = torch.tensor(st.olens, dtype=torch.int32)
+        return torch.cat([score(st, olens, sl) for sl in cb.slices(self.nll_rows_per_call, min_width)])
+
+    def _score_candidates(self, speech, speech_lengths, cb: CandidateBatch, score, min_width: int = 1) -> list:
+        """`_enqueue_candidates` and the one D2H copy of a `batch_*` call: a value (or row of values) per candidate."""
+        return self._enqueue_candidates(speech, speech_lengths, cb, score, min_width).cpu().tolist() if len(cb) else []
 
     @torch.no_grad()
     def batch_nll(self, speech: torch.Tensor, speech_lengths: Sequence[int], texts):
@@ -332,36 +352,16 @@ class Speech2Text:
         this object's tokenizer) or a sequence of token ids - an empty one scores <eos> alone.  Returns one list of
         floats per utterance, a value per candidate.  The utterances are encoded as `batch_decode` encodes them; the
         candidates of an utterance share its one projected memory.  One D2H copy per call."""
-        m = self.asr_model
-        B = int(speech.shape[0])
-        if len(texts) != B:
-            raise ValueError(f"{len(texts)} transcript entries for {B} utterances")
-        cands = [[t] if self._is_one_transcript(t) else list(t) for t in texts]
-        ids, mem_of = [], []
-        for b, group in enumerate(cands):
-            for t in group:
-                ids.append(self._target_ids(t))
-                mem_of.append(b)
-        if not ids:
-            return [[] for _ in range(B)]
-        speech = speech.to(self.device, torch.float32, non_blocking=True)
-        st = m.encode_device(speech, [int(n) for n in speech_lengths], isolate=True)
-        olens = torch.tensor(st.olens, dtype=torch.int32)
-        parts = []
-        for s in range(0, len(ids), self.nll_rows_per_call):
-            rows, mo = ids[s : s + self.nll_rows_per_call], mem_of[s : s + self.nll_rows_per_call]
-            u0, u1 = mo[0], mo[-1] + 1  # the slice's utterances: only their memories are projected
-            ys = torch.zeros(len(rows), max(max(len(y) for y in rows), 1), dtype=torch.long)
-            for i, y in enumerate(rows):
-                ys[i, : len(y)] = torch.tensor(y, dtype=torch.long)
-            parts.append(m._nll_rows(st.enc_act[u0:u1], olens[u0:u1], ys, torch.tensor([len(y) for y in rows]),
-                                     mem_of=torch.tensor([u - u0 for u in mo], dtype=torch.int32)))
-        vals = torch.cat(parts).cpu().tolist()
-        out, k = [], 0
-        for group in cands:
-            out.append(vals[k : k + len(group)])
-            k += len(group)
-        return out
+        cb = self._candidates(speech, texts)
+        return cb.regroup(self._score_candidates(speech, speech_lengths, cb, self._decoder_nll))
+
+    def _decoder_nll(self, st, olens, sl):
+        """A slice's candidates under the attention decoder, against the memories of the slice's own utterances (only
+        those are projected).  The candidates are checked, the lengths are checked here: nothing is verified on the device."""
+        if min(st.olens[sl.u0 : sl.u1]) < 1:
+            raise ValueError("an utterance without encoder frames has no memory to attend to")
+        return self.asr_model._nll_rows(st.enc_act[sl.u0 : sl.u1], olens[sl.u0 : sl.u1], sl.ys, torch.tensor(sl.ylens),
+                                        mem_of=torch.tensor(sl.mem_rel, dtype=torch.int32), checked=True)
 
     # ------------------------------------------------------------------ transducer likelihood of given transcripts
     @torch.no_grad()
@@ -376,38 +376,17 @@ class Speech2Text:
         if not getattr(m, "use_transducer_decoder", False):
             raise RuntimeError("batch_transducer_nll: the model has no joint network (decoder: transducer); the attention "
                                "decoder's likelihood is batch_nll")
-        B = int(speech.shape[0])
-        if len(texts) != B:
-            raise ValueError(f"{len(texts)} transcript entries for {B} utterances")
-        cands = [[t] if self._is_one_transcript(t) else list(t) for t in texts]
-        ids, mem_of = [], []
-        for b, group in enumerate(cands):
-            for t in group:
-                y = self._target_ids(t)
-                if any(v < 0 or v >= m.vocab_size for v in y):
-                    raise ValueError(f"token ids must lie in [0, {m.vocab_size})")
-                ids.append(y)
-                mem_of.append(b)
-        if not ids:
-            return [[] for _ in range(B)]
-        speech = speech.to(self.device, torch.float32, non_blocking=True)
-        st = m.encode_device(speech, [int(n) for n in speech_lengths], isolate=True)
-        olens = torch.tensor(st.olens, dtype=torch.int32)
-        enc_proj = m.joint_network.enc_proj_device(st.enc_act)  # once for the batch: every slice reads the same rows
-        parts = []
-        for s in range(0, len(ids), self.nll_rows_per_call):
-            rows, mo = ids[s : s + self.nll_rows_per_call], mem_of[s : s + self.nll_rows_per_call]
-            ys = torch.zeros(len(rows), max(len(y) for y in rows), dtype=torch.long)
-            for i, y in enumerate(rows):
-                ys[i, : len(y)] = torch.tensor(y, dtype=torch.long)
-            parts.append(m.transducer_nll(st.enc_act, olens, ys, torch.tensor([len(y) for y in rows]),
-                                          mem_of=torch.tensor(mo, dtype=torch.int32), enc_proj=enc_proj))
-        vals = torch.cat(parts).cpu().tolist()  # the one D2H copy
-        out, k = [], 0
-        for group in cands:
-            out.append(vals[k : k + len(group)])
-            k += len(group)
-        return out
+        cb = self._candidates(speech, texts)
+        enc_proj = []  # projected at the first slice, once for the batch: every slice reads the same rows
+
+        def score(st, olens, sl):  # against the whole batch
+            if not enc_proj:
+                enc_proj.append(m.joint_network.enc_proj_device(st.enc_act))
+            return m.transducer_nll(st.enc_act, olens, sl.ys, torch.tensor(sl.ylens),
+                                    mem_of=torch.tensor(sl.mem_of, dtype=torch.int32), enc_proj=enc_proj[0])
+
+        # (the transducer takes a slice of empty transcripts as zero columns)
+        return cb.regroup(self._score_candidates(speech, speech_lengths, cb, score, min_width=0))
 
     # ------------------------------------------------------------------ the joint score of given transcripts
     @torch.no_grad()
@@ -434,56 +413,33 @@ class Speech2Text:
                                "search's scorers (the transducer's own likelihood: batch_transducer_nll)")
         if self.ngram is not None:
             raise NotImplementedError("batch_rescore with ngram_file: whole-sentence n-gram scoring is not implemented")
-        m, bs = self.asr_model, self.beam_search
-        B = int(speech.shape[0])
-        if len(texts) != B:
-            raise ValueError(f"{len(texts)} transcript entries for {B} utterances")
-        cands = [[t] if self._is_one_transcript(t) else list(t) for t in texts]
-        ids, mem_of = [], []
-        for b, group in enumerate(cands):
-            for t in group:
-                ids.append(self._target_ids(t))
-                mem_of.append(b)
-        if not ids:
-            return [[] for _ in range(B)]
-        keys = [k for k in ("decoder", "ctc", "length_bonus", "lm") if k in bs.scorers]
-        speech = speech.to(self.device, torch.float32, non_blocking=True)
-        st = m.encode_device(speech, [int(n) for n in speech_lengths], isolate=True)
-        olens = torch.tensor(st.olens, dtype=torch.int32)
-        parts = []
-        for s in range(0, len(ids), self.nll_rows_per_call):
-            rows, mo = ids[s : s + self.nll_rows_per_call], mem_of[s : s + self.nll_rows_per_call]
-            u0, u1 = mo[0], mo[-1] + 1  # the slice's utterances
-            rel = [u - u0 for u in mo]
-            ylens = [len(y) for y in rows]
-            ys = torch.zeros(len(rows), max(max(ylens), 1), dtype=torch.long)
-            for i, y in enumerate(rows):
-                ys[i, : len(y)] = torch.tensor(y, dtype=torch.long)
-            col = {}
-            if "decoder" in keys:
-                col["decoder"] = -m._nll_rows(st.enc_act[u0:u1], olens[u0:u1], ys, torch.tensor(ylens),
-                                              mem_of=torch.tensor(rel, dtype=torch.int32))
-            if "ctc" in keys:
-                col["ctc"] = -m.ctc.nll_device(st.enc_act[u0:u1].contiguous(), st.olens[u0:u1], rows, ylens, m.blank_id,
-                                               mem_of=rel)
-            if "lm" in keys:
-                nll, _ = self.lm_model.nll(ys.to(self.device, non_blocking=True), torch.tensor(ylens))
-                col["lm"] = -nll.sum(dim=1)
-            if "length_bonus" in keys:
-                col["length_bonus"] = torch.tensor([n + 1.0 for n in ylens], dtype=torch.float32).to(self.device,
-                                                                                                     non_blocking=True)
-            parts.append(torch.stack([col[k] for k in keys], dim=1))
-        vals = torch.cat(parts).cpu().tolist()  # the one D2H copy
-        out, k = [], 0
-        for group in cands:
-            res = []
-            for _ in group:
-                scores = dict(zip(keys, vals[k]))
-                res.append(dict(token_int=ids[k], scores=scores,
-                                score=sum(float(bs.weights[kk]) * v for kk, v in scores.items())))
-                k += 1
-            out.append(res)
-        return out
+        bs = self.beam_search
+        keys = self._rescore_keys()
+        cb = self._candidates(speech, texts, lm="lm" in keys)
+        vals = self._score_candidates(speech, speech_lengths, cb, functools.partial(self._rescore_columns, keys))
+        res = []
+        for y, row in zip(cb.ids, vals):
+            scores = dict(zip(keys, row))
+            res.append(dict(token_int=y, scores=scores, score=sum(float(bs.weights[k]) * v for k, v in scores.items())))
+        return cb.regroup(res)
+
+    def _rescore_keys(self):
+        return [k for k in ("decoder", "ctc", "length_bonus", "lm") if k in self.beam_search.scorers]
+
+    def _rescore_columns(self, keys, st, olens, sl):
+        """A slice's (n, len(keys)) scores for `batch_rescore`, the columns in `keys` order."""
+        m, dev = self.asr_model, self.device
+        col = {}
+        if "decoder" in keys:
+            col["decoder"] = -self._decoder_nll(st, olens, sl)
+        if "ctc" in keys:
+            col["ctc"] = -m.ctc.nll_device(st.enc_act[sl.u0 : sl.u1].contiguous(), st.olens[sl.u0 : sl.u1], sl.ids, sl.ylens,
+                                           m.blank_id, mem_of=sl.mem_rel)
+        if "lm" in keys:
+            col["lm"] = -self.lm_model.nll_of_checked(sl.ys, torch.tensor(sl.ylens), dev).sum(dim=1)
+        if "length_bonus" in keys:
+            col["length_bonus"] = torch.tensor([n + 1.0 for n in sl.ylens], dtype=torch.float32).to(dev, non_blocking=True)
+        return torch.stack([col[k] for k in keys], dim=1)
 
     def decode_greedy_device(self, st):
         """Device-resident G1 result: (tokens (B,T) i32 padded with -1, token_lens (B,) i32)."""

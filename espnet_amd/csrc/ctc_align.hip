@@ -2,17 +2,9 @@
 // one launch.  Reference: CTC.forced_align, espnet2/asr/ctc.py (a wrapper of torchaudio.functional.forced_align, one
 // utterance per call on the CPU); the contract (states, recursion, tie rule, outputs) is include/espnet_amd.h's.
 //
-// Layout of the work.  One workgroup per utterance, the T frames in sequence, the S = 2 L + 1 trellis states spread
-// over the lanes: thread i owns the 8 states 8 i .. 8 i + 7 in registers, that is four blanks and the four tokens
-// y[4 i .. 4 i + 3].  Of its neighbours a thread needs only alpha[8 i - 1] (state 8 i is a blank: stay or one; state
-// 8 i + 1 skips from 8 i - 1), which is one lane shift (DPP wave_shr:1) per frame and, across waves, one LDS word and
-// one barrier per frame.  S <= 512 runs as ONE wave64 with no workgroup barrier anywhere; longer transcripts run as
-// ceil(S / 512) <= 16 waves, so the largest transcript taken is L = CA_MAX_L = 4 095 tokens.
-//
-// Emissions come straight from lpT [V][ldT] (em_ctc_log_probs_t): a token's row is frame-contiguous, so one 16-byte
-// load brings four frames of it; every lane loads the same four frames of the blank row (one request per wave).  The
-// loads of frame group k + 1 are issued before the chain of group k, so the per-frame chain is compare / select / add
-// and the shift.  (Rows whose stride or base is not 16-byte aligned take 4-byte loads, same values.)
+// Layout of the work: the shared trellis walk of ctc_trellis.h - one workgroup per utterance, 8 states per lane, one
+// wave up to S = 512 and up to 16 waves beyond (L <= 4 095), emissions from the frame-contiguous lpT rows four frames
+// per load - with the Viterbi cell: of stay / one / two the first strictly larger predecessor wins, its move is 2 bits.
 //
 // Back-pointers are 2 bits per (t, s): the 8 of a thread in one 16-bit store per frame, to LDS when T * threads * 2
 // bytes fit CA_LDS_BP_BYTES (T = 249, one wave: 31.9 KB), else to the caller's workspace.  The back-trace walks
@@ -23,16 +15,16 @@
 // one row, the order the contract fixes; a token that lasts thousands of frames (long form) is accepted as that.
 //
 // hipcc -O3 --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage (ROCm 7.2):
-//   ctc_align_kernel<false> (one wave)  : 84 VGPRs, 101 SGPRs, 0 bytes of scratch, no spills, 8 976 B of LDS, no s_barrier
-//   ctc_align_kernel<true>  (2-16 waves): 86 VGPRs, 105 SGPRs, 0 bytes of scratch, no spills, 9 104 B of LDS
+//   ctc_align_kernel<false> (one wave)  : 86 VGPRs, 88 SGPRs, 0 bytes of scratch, no spills, 8 976 B of LDS, no s_barrier
+//   ctc_align_kernel<true>  (2-16 waves): 89 VGPRs, 90 SGPRs, 0 bytes of scratch, no spills, 9 104 B of LDS
 // (LDS: the static part; the one-wave form adds T * 128 bytes of back-pointers, 31.9 KB at T = 249.)
-#include "em_common.h"
+#include "ctc_trellis.h"
 
 namespace {
 
-constexpr int CA_SPL = 8;                                        // states per lane
-constexpr int CA_MAX_WAVES = 16;                                 // 1 024 threads
-constexpr int CA_MAX_L = (CA_MAX_WAVES * 64 * CA_SPL - 1) / 2;   // 4 095 tokens (S = 8 191 <= 8 192)
+using ctc_trellis::group_sync;
+using ctc_trellis::NINF;
+constexpr int CA_SPL = ctc_trellis::SPL;                         // states per lane: 2 bits each in a 16-bit word
 constexpr int CA_LDS_BP_BYTES = 48 * 1024;                       // back-pointers kept in LDS up to this size
 constexpr int CA_CH = 128;                                       // frames per back-trace chunk
 constexpr int CA_WIN = 2 * CA_CH / CA_SPL + 2;                   // 16-bit words per frame that a chunk's window can span
@@ -46,40 +38,47 @@ struct AlignArgs {
   unsigned short* ws;  // [B][T][threads] back-pointer words when !lds_bp
 };
 
-constexpr float NINF = -INFINITY;
-
-static inline int ca_waves(int Lmax) { return em_cdiv(2 * Lmax + 1, 64 * CA_SPL); }
-
-// four consecutive columns c0 .. c0 + 3 of one lpT row
-__device__ __forceinline__ f32x4 load4(const float* row, long c0, bool vec, long ldT) {
-  if (vec) return *(const f32x4*)(row + c0);
-  f32x4 r;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) r[i] = c0 + i < ldT ? row[c0 + i] : 0.f;
-  return r;
-}
-
-template <bool MULTI>
-__device__ __forceinline__ void group_sync() {
-  if (MULTI) {
-    __syncthreads();
-  } else {  // one wave: LDS and global traffic of its own lanes, ordered without a barrier
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+// the Viterbi cell: the best of stay / one / two in this order under strict >, and the 8 moves of a thread's frame in
+// one 16-bit store, to LDS or to the workspace
+struct ViterbiCell {
+  unsigned short *bp_lds, *wsb;  // [T][NT] back-pointer words: LDS when lds_bp, else the workspace
+  int lds_bp, NT, tid;
+  unsigned bp = 0;
+  static __device__ __forceinline__ f32x4 prepare(f32x4 e) { return e; }
+  __device__ __forceinline__ float blank(int j, float stay, float one, float e) { return token(j, stay, one, NINF, e); }
+  __device__ __forceinline__ float token(int j, float stay, float one, float two, float e) {
+    float best = stay;
+    unsigned mv = 0;
+    if (one > best) {
+      best = one;
+      mv = 1;
+    }
+    if (two > best) {
+      best = two;
+      mv = 2;
+    }
+    bp |= mv << (2 * j);
+    return best + e;
   }
-}
+  __device__ __forceinline__ void frame(int t) {
+    if (lds_bp)
+      bp_lds[(size_t)t * NT + tid] = (unsigned short)bp;
+    else
+      wsb[(size_t)t * NT + tid] = (unsigned short)bp;
+    bp = 0;
+  }
+};
 
 template <bool MULTI>
 __global__ __launch_bounds__(MULTI ? 1024 : 64) void ctc_align_kernel(const AlignArgs a) {
   extern __shared__ unsigned short bp_lds[];  // [T][NT] when a.lds_bp
   __shared__ unsigned short win[CA_CH * CA_WIN];
   __shared__ unsigned short pth[CA_CH + 1];
-  __shared__ float xch[2][CA_MAX_WAVES];
+  __shared__ float xch[2][ctc_trellis::MAX_WAVES];
   __shared__ float fin[2];
   __shared__ int s_carry;
 
-  const int b = blockIdx.x, tid = threadIdx.x, NT = blockDim.x, lane = tid & 63, wave = tid >> 6;
+  const int b = blockIdx.x, tid = threadIdx.x, NT = blockDim.x;
   const int T = a.T, blank = a.blank, Lmax = a.Lmax;
   const int Tb = min(max(a.xlens[b], 0), T);
   const int L = min(max(a.ylens[b], 0), Lmax);
@@ -88,106 +87,9 @@ __global__ __launch_bounds__(MULTI ? 1024 : 64) void ctc_align_kernel(const Alig
   const long ldT = a.ldT, colb = (long)b * T;
   unsigned short* wsb = a.lds_bp ? nullptr : a.ws + (size_t)b * T * NT;
 
-  if (tid < 2) fin[tid] = NINF;
-  group_sync<MULTI>();
-
   // ---- forward pass
-  float al[CA_SPL];
-#pragma unroll
-  for (int j = 0; j < CA_SPL; ++j) al[j] = NINF;
-  if (Tb > 0) {
-    const float* rows[4];
-    float cap[4];  // +inf where the move by two states is allowed, -inf where not
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int i = 4 * tid + q;
-      const int lab = i < L ? y[i] : blank;
-      rows[q] = a.lpT + (size_t)lab * ldT;
-      cap[q] = (i >= 1 && i < L && y[i - 1] != lab) ? INFINITY : NINF;
-    }
-    const float* rowb = a.lpT + (size_t)blank * ldT;
-    const bool vec = a.vec != 0;
-    const long col0 = vec ? (colb & ~3L) : colb;
-    const int off = (int)(colb - col0);
-    const int NG = (off + Tb + 3) >> 2;
-
-    f32x4 cur[5], nxt[5];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) cur[q] = load4(rows[q], col0, vec, ldT);
-    cur[4] = load4(rowb, col0, vec, ldT);
-#pragma unroll
-    for (int q = 0; q < 5; ++q) nxt[q] = cur[q];
-    for (int k = 0; k < NG; ++k) {
-      if (k + 1 < NG) {
-        const long c = col0 + 4L * (k + 1);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) nxt[q] = load4(rows[q], c, vec, ldT);
-        nxt[4] = load4(rowb, c, vec, ldT);
-      }
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int t = 4 * k + i - off;
-        if (t < 0 || t >= Tb) continue;  // the same in every thread of the workgroup
-        const float eb = cur[4][i];
-        if (t == 0) {
-          if (tid == 0) {
-            al[0] = eb;
-            if (L > 0) al[1] = cur[0][i];
-          }
-        } else {
-          // alpha[t-1] of the state below this thread's run
-          float p7 = __builtin_bit_cast(
-              float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, NINF), __builtin_bit_cast(int, al[7]), 0x138,
-                                                 0xf, 0xf, false));  // wave_shr:1; lane 0 keeps -inf
-          if (MULTI) {
-            if (lane == 0 && wave > 0) p7 = xch[(t - 1) & 1][wave - 1];
-          }
-          float nw[CA_SPL];
-          unsigned bp = 0;
-#pragma unroll
-          for (int j = 0; j < CA_SPL; ++j) {
-            const float one = j == 0 ? p7 : al[j - 1];
-            float best = al[j];
-            unsigned mv = 0;
-            if (one > best) {
-              best = one;
-              mv = 1;
-            }
-            if (j & 1) {
-              const float two = fminf(j == 1 ? p7 : al[j - 2], cap[j >> 1]);
-              if (two > best) {
-                best = two;
-                mv = 2;
-              }
-              nw[j] = best + cur[j >> 1][i];
-            } else {
-              nw[j] = best + eb;
-            }
-            bp |= mv << (2 * j);
-          }
-#pragma unroll
-          for (int j = 0; j < CA_SPL; ++j) al[j] = nw[j];
-          if (a.lds_bp)
-            bp_lds[(size_t)t * NT + tid] = (unsigned short)bp;
-          else
-            wsb[(size_t)t * NT + tid] = (unsigned short)bp;
-        }
-        if (MULTI) {
-          if (lane == 63) xch[t & 1][wave] = al[7];
-          __syncthreads();
-        }
-      }
-#pragma unroll
-      for (int q = 0; q < 5; ++q) cur[q] = nxt[q];
-    }
-#pragma unroll
-    for (int j = 0; j < CA_SPL; ++j) {
-      const int s = CA_SPL * tid + j;
-      if (s == S - 1) fin[0] = al[j];
-      if (s == S - 2) fin[1] = al[j];
-    }
-  }
-  group_sync<MULTI>();
+  ViterbiCell cell{bp_lds, wsb, a.lds_bp, NT, tid};
+  ctc_trellis::forward<MULTI>(a.lpT, ldT, colb, a.vec != 0, y, L, Tb, blank, xch, fin, cell);
 
   // ---- outputs: the padding first (the output pointers are formed only here: the forward loop is short of scalar registers)
   int32_t* align = a.align + (size_t)b * T;
@@ -276,11 +178,11 @@ __global__ __launch_bounds__(MULTI ? 1024 : 64) void ctc_align_kernel(const Alig
 
 }  // namespace
 
-extern "C" int32_t em_ctc_forced_align_max_tokens(void) { return CA_MAX_L; }
+extern "C" int32_t em_ctc_forced_align_max_tokens(void) { return ctc_trellis::MAX_L; }
 
 extern "C" size_t em_ctc_forced_align_workspace_bytes(int32_t B, int32_t T, int32_t Lmax) {
-  if (B <= 0 || T <= 0 || Lmax < 0 || Lmax > CA_MAX_L) return 0;
-  const size_t per_utt = (size_t)T * ca_waves(Lmax) * 64 * sizeof(unsigned short);
+  if (B <= 0 || T <= 0 || Lmax < 0 || Lmax > ctc_trellis::MAX_L) return 0;
+  const size_t per_utt = (size_t)T * ctc_trellis::waves(Lmax) * 64 * sizeof(unsigned short);
   return per_utt <= (size_t)CA_LDS_BP_BYTES ? 0 : per_utt * B;
 }
 
@@ -292,10 +194,10 @@ extern "C" int em_ctc_forced_align(const float* lpT, int32_t ldT, const int32_t*
     return EM_ERR_BAD_ARG;
   if (Lmax > 0 && (!targets || !tok_start || !tok_end || !tok_lp)) return EM_ERR_BAD_ARG;
   if ((long)ldT < (long)B * T) return EM_ERR_BAD_ARG;
-  if (Lmax > CA_MAX_L) return EM_ERR_UNSUPPORTED;
+  if (Lmax > ctc_trellis::MAX_L) return EM_ERR_UNSUPPORTED;
   const size_t need = em_ctc_forced_align_workspace_bytes(B, T, Lmax);
   if (need > 0 && (!ws || ws_bytes < need)) return EM_ERR_WORKSPACE;
-  const int nw = ca_waves(Lmax);
+  const int nw = ctc_trellis::waves(Lmax);
   AlignArgs a;
   a.lpT = lpT; a.xlens = xlens; a.targets = targets; a.ylens = ylens;
   a.ldT = ldT; a.Lmax = Lmax; a.T = T; a.blank = blank;

@@ -173,13 +173,18 @@ class TransformerLM(PackedModule, BatchScorerInterface):
         if x.dim() != 2 or x.shape != target.shape or x.numel() == 0:
             raise ValueError(f"sequence_nll: x and target must be equal, non-empty (B, Lp) tensors, got {tuple(x.shape)} "
                              f"and {tuple(target.shape)}")
-        dev = x.device
-        B, Lp = x.shape
-        pk = self.packed(dev, Lp + 1)
         xi = x.to(torch.int32).contiguous()
         ti = target.to(torch.int32).contiguous()
         if bool(((xi < 0) | (xi >= self.vocab_size)).any() | (ti >= self.vocab_size).any()):
             raise ValueError(f"sequence_nll: token ids must lie in [0, {self.vocab_size})")
+        return self._sequence_nll(xi, ti)
+
+    def _sequence_nll(self, xi: torch.Tensor, ti: torch.Tensor) -> torch.Tensor:
+        """`sequence_nll` behind its checks: contiguous int32 (B, Lp) device tensors taken as given (the caller has
+        checked their values).  Only enqueues."""
+        dev = xi.device
+        B, Lp = xi.shape
+        pk = self.packed(dev, Lp + 1)
         lib = L.load()
         need = lib.em_lm_seq_nll_workspace_bytes(pk.dtype, C.byref(pk.w), B, Lp)
         if need == 0:
@@ -222,16 +227,32 @@ class ESPnetLanguageModel(torch.nn.Module):
         self.sos = self.eos = vocab_size - 1
         self.ignore_id = ignore_id
 
+    def _masked_pair(self, text, text_lengths, max_length=None):
+        """`build_nll_batch` on text's device, with x zeroed behind x_lengths -> (x, t, x_lengths, scored)."""
+        x, t, x_lengths = build_nll_batch(text, text_lengths, self.sos, self.eos, self.ignore_id, max_length)
+        x_lengths = x_lengths.to(x.device)
+        scored = torch.arange(x.size(1), device=x.device).unsqueeze(0) < x_lengths.unsqueeze(1)
+        x = torch.where(scored, x, torch.zeros_like(x))  # whatever the caller padded with: nothing behind the end is a key
+        return x, t, x_lengths, scored
+
+    @torch.no_grad()
+    def nll_of_checked(self, text: torch.Tensor, text_lengths: torch.Tensor, device) -> torch.Tensor:
+        """`nll`'s first result for HOST text / text_lengths whose ids the caller has checked against the vocabulary:
+        the sentence pair is built on the host and the TransformerLM only enqueues (no verdict is read back).  A
+        recurrent LM goes through `nll`."""
+        if not isinstance(self.lm, TransformerLM):
+            return self.nll(text.to(device, non_blocking=True), text_lengths)[0]
+        x, t, _, scored = self._masked_pair(text, text_lengths)
+        t = torch.where(scored, t, torch.full_like(t, -1))
+        return self.lm._sequence_nll(*(v.to(torch.int32).contiguous().to(device, non_blocking=True) for v in (x, t)))
+
     @torch.no_grad()
     def nll(self, text: torch.Tensor, text_lengths: torch.Tensor, max_length: Optional[int] = None):
         """espnet_model.py:38-80.  text (B, Lt) int64, text_lengths (B,) -> (nll (B, L + 1) f32, x_lengths (B,)):
         nll[i, j] = -log_softmax(lm(x)[i, j])[t[i, j]] for j < x_lengths[i], exactly 0.0 behind.  The TransformerLM scores
         all rows in one enqueue (`sequence_nll`); a recurrent LM goes position by position through its `forward`."""
         L.require_gpu(text, "text")
-        x, t, x_lengths = build_nll_batch(text, text_lengths, self.sos, self.eos, self.ignore_id, max_length)
-        x_lengths = x_lengths.to(x.device)
-        scored = torch.arange(x.size(1), device=x.device).unsqueeze(0) < x_lengths.unsqueeze(1)
-        x = torch.where(scored, x, torch.zeros_like(x))  # whatever the caller padded with: nothing behind the end is a key
+        x, t, x_lengths, scored = self._masked_pair(text, text_lengths, max_length)
         if isinstance(self.lm, TransformerLM):
             return self.lm.sequence_nll(x, torch.where(scored, t, torch.full_like(t, -1))), x_lengths
         logits, _ = self.lm(x, None)

@@ -11,6 +11,7 @@ project's convention for E_* constants).  Every test prints what it measured.
 Shapes are the smallest that reach every path of the kernel: S around the 8-state lane runs and the 64-lane wave (L = 31
 .. 64), around the one-wave form (L = 255 / 256), several waves, frame counts that end inside a group of four prefetched
 frames, unaligned utterance starts and the 4-byte load path in ragged batches."""
+import functools
 import json
 import math
 
@@ -295,6 +296,36 @@ def test_batch_rescore_nbest_list_equals_single_calls_and_slices(rescore_case):
         del s2t.nll_rows_per_call
     for i, (a, b) in enumerate(zip(sliced[0] + sliced[1], res[0] + res[1])):
         same(a, b, ("sliced", i))
+
+
+def test_batch_rescore_only_enqueues_up_to_its_one_copy(rescore_case):
+    """The shared driver of the batch_* calls (encode, every scorer of every slice, the concatenation) under torch's
+    sync debug mode "error": nothing synchronises before the one D2H copy.  In slices of 2, so that a slice boundary lies
+    inside utterance 0's list and a slice spans both utterances."""
+    g, s2t, speech, lengths = rescore_case
+    s2t.nll_rows_per_call = 2
+    try:
+        want = s2t.batch_rescore(speech, lengths, [CANDS, OTHER])  # (and the weights are packed, the lengths cached)
+        keys = s2t._rescore_keys()
+        cb = s2t._candidates(speech, [CANDS, OTHER], lm="lm" in keys)
+        probe = torch.ones(1, device="cuda")
+        before = torch.cuda.get_sync_debug_mode()
+        torch.cuda.set_sync_debug_mode("error")
+        try:
+            try:
+                probe.item()
+                honoured = False
+            except RuntimeError:
+                honoured = True
+            if honoured:
+                vals = s2t._enqueue_candidates(speech, lengths, cb, functools.partial(s2t._rescore_columns, keys))
+        finally:
+            torch.cuda.set_sync_debug_mode(before)
+    finally:
+        del s2t.nll_rows_per_call
+    if not honoured:
+        pytest.skip("this torch build does not honour torch.cuda.set_sync_debug_mode('error'): .item() did not raise")
+    assert vals.is_cuda and vals.cpu().tolist() == [list(r["scores"].values()) for r in want[0] + want[1]]
 
 
 def test_batch_rescore_agrees_with_the_search_on_its_own_nbest(tmp_path):
