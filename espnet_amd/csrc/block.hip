@@ -261,6 +261,53 @@ __global__ __launch_bounds__(NT, 1) void block_kernel(const EmBlockArgs a_in, lo
         for (int f = 0; f < 4; ++f) *(float4*)(xdst + mrow[mi] * D + 64 * f + ncol) = xr[mi][f];
       }
   };
+  // ---- row stores that hipcc can COUNT (the Conformer instantiations, unfolded): a store under `if (row_ok[mi])` is, to
+  // the wait-count pass, a store that may not have been issued - every s_waitcnt behind it assumes it is NOT outstanding,
+  // i.e. waits for it as well (what the file says about loads under a branch, ffn() below).  So the rows of an utterance
+  // are written through a buffer resource whose range ends with frame T - 1 of THAT utterance, unconditionally: a masked
+  // lane's offset lies past the range and the memory pipeline drops its store (csrc/subsample2.hip stores the same way).
+  // No clamped address: a tail row's values differ from frame T - 1's (its depthwise-conv window differs).
+  // Round 12 (profiles/r12a_switch_ab.txt, r12a_bench_pair.txt; B = 32 x 10 s, the default bench line, ms per step, builds
+  // taken round-robin in one call on one box):
+  //   x of the A part behind the macaron module, x of the C part behind linear_out (this build)  0.877 - 0.882
+  //   the parent commit (both stored at the end of the kernel, under row_ok)                     0.900 - 0.904
+  //   -DEM_BLOCK_VAR=0x30000 (both switches below)                                               0.898 - 0.905
+  //   -DEM_BLOCK_VAR=0x10000: the A part's x at the end again   0.899 - 0.903 against 0.880 - 0.882 in that call
+  //   -DEM_BLOCK_VAR=0x20000: the C part's x at the end again   0.884 - 0.886 against 0.880 - 0.882
+  //   -DEM_BLOCK_VAR=0x40000: the GLU stores counted as well    0.880 - 0.882 against 0.880 - 0.883: no gain, not built in
+  // Tried and taken out again, no faster: block<D|FINAL|CTC> with the CTC head's units 0 - 2 requested inside the
+  // feed-forward module and enc_out / enc_act stored counted behind them (kernel 50.8 against 50.7 us, step 0.880 -
+  // 0.882 with and without it: the walk's waits, joined over its loop, give the stores two units' time, and they are
+  // one launch of 25); the A part's x behind norm_mha's normalisation instead of in front of the LayerNorm (0.892 -
+  // 0.898 against 0.885 - 0.888 in that call), and half of it either side (0.891 - 0.895).
+  constexpr bool PLAIN = !RELU && !FOLD;
+  constexpr bool X_EARLY_A = PLAIN && HAS_A && !(EM_BLOCK_VAR & 0x10000);
+  constexpr bool X_EARLY_C = PLAIN && HAS_C && !(EM_BLOCK_VAR & 0x20000);
+  constexpr bool GLU_COUNTED = PLAIN && HAS_C && (EM_BLOCK_VAR & 0x40000) != 0;
+  typedef __attribute__((ext_vector_type(2))) unsigned su32x2;
+  typedef __attribute__((ext_vector_type(4))) unsigned su32x4;
+  constexpr unsigned ROW_MASKED = 0x80000000u;  // (the host refuses T * 1 KiB >= 2 GiB: past every range, and no wrap-around with the column offsets added)
+  // byte offset of (frame mi * 16 + lr, column ncol) in the utterance's [T][256] f32 rows (bf16 rows: half of it)
+  unsigned rowoff[2];
+#pragma unroll
+  for (int mi = 0; mi < 2; ++mi) rowoff[mi] = row_ok[mi] ? (unsigned)(t0 + mi * 16 + lr) * (D * 4u) + ncol * 4u : ROW_MASKED;
+  auto rows_rsrc = [&](const void* base, int esz) __attribute__((always_inline)) {
+    const unsigned char* p = em_uniform_ptr((const unsigned char*)base + (size_t)b * T * D * esz);
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(p), 0, T * D * esz, 0x00020000);
+  };
+  auto put_f32x4 = [&](__amdgpu_buffer_rsrc_t rs, int mi, int f, const float4& v) __attribute__((always_inline)) {
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(su32x4, v), rs, rowoff[mi] + 256 * f, 0, 0);
+  };
+  auto put_bf16x4 = [&](__amdgpu_buffer_rsrc_t rs, int mi, int f, const bf16x4& v) __attribute__((always_inline)) {
+    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(su32x2, v), rs, (rowoff[mi] >> 1) + 128 * f, 0, 0);
+  };
+  auto store_x_counted = [&]() __attribute__((always_inline)) {
+    const __amdgpu_buffer_rsrc_t rs = rows_rsrc(xdst, 4);
+#pragma unroll
+    for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+      for (int f = 0; f < 4; ++f) put_f32x4(rs, mi, f, xr[mi][f]);
+  };
   auto load_act = [&]() __attribute__((always_inline)) {  // from abuf, after a barrier
 #pragma unroll
     for (int mi = 0; mi < 2; ++mi)
@@ -1326,7 +1373,13 @@ __global__ __launch_bounds__(NT, 1) void block_kernel(const EmBlockArgs a_in, lo
       if (j < 3) read_unit(a.pw1f, j, ring[j]);
     });
     fstamp(50);
-    // (x is stored at the end of the kernel, behind the last weight request: see the A part)
+    // x is final and pointwise_conv1's units 0 - 2 are in flight (requested inside linear_out): its rows leave HERE, counted
+    // (store_x_counted; the reasoning is the A part's, above norm_mha) - younger than every load the pw1 stream waits for
+    // before its fourth unit, draining under norm_conv instead of behind the last GLU store, where every CU of the launch
+    // stored its 32 KiB at once (until round 12; block<ATT|C> 19.2 -> 18.9 us, the step 0.885 against 0.881, see the table
+    // at store_x_counted).  The streaming instantiation keeps the closing store.
+    if constexpr (X_EARLY_C) store_x_counted();
+    const __amdgpu_buffer_rsrc_t glu_rs = rows_rsrc(a.glu, 2);
     ln_to_act(pb0, 256, 512, 0);
     fstamp(15);
     // pointwise_conv1 + GLU (convolution.py:66-69): unit 2j = value rows 64j.., unit 2j+1 = their gates
@@ -1340,18 +1393,22 @@ __global__ __launch_bounds__(NT, 1) void block_kernel(const EmBlockArgs a_in, lo
         const float4 bv = *(const float4*)(pb0 + 768 + (2 * j) * 64 + ncol);
         const float4 bg = *(const float4*)(pb0 + 768 + (2 * j + 1) * 64 + ncol);
         // (8-byte pieces, as they come: traded into 16-byte stores through v_permlane16_swap like q / k / v in the A part
-        // this kernel got SLOWER, 12.46 -> 12.83 us - its tail is the 32 KiB of x, not the 16 KiB of glu; profiles/r03ac)
+        // this kernel got SLOWER, 12.46 -> 12.83 us; profiles/r03ac.  Its tail then was the 32 KiB of x stored behind the
+        // last of these, not the 16 KiB of glu; x has left behind linear_out since round 12.)
 #pragma unroll
         for (int mi = 0; mi < 2; ++mi) {
           bf16x4 pk = {(bf16)((v[mi][0] + bv.x) * sigmoidf_(gt[mi][0] + bg.x)),
                        (bf16)((v[mi][1] + bv.y) * sigmoidf_(gt[mi][1] + bg.y)),
                        (bf16)((v[mi][2] + bv.z) * sigmoidf_(gt[mi][2] + bg.z)),
                        (bf16)((v[mi][3] + bv.w) * sigmoidf_(gt[mi][3] + bg.w))};
-          if (row_ok[mi]) *(bf16x4*)((bf16*)a.glu + mrow[mi] * D + 64 * j + ncol) = pk;
+          // (under row_ok every wait of the stream behind the first GLU store waits for these stores too; counted - the
+          // developer build -DEM_BLOCK_VAR=0x40000 - the step measured the same: the product keeps the branch)
+          if constexpr (GLU_COUNTED) put_bf16x4(glu_rs, mi, j, pk);
+          else if (row_ok[mi]) *(bf16x4*)((bf16*)a.glu + mrow[mi] * D + 64 * j + ncol) = pk;
         }
       }
     });
-    store_x();
+    if constexpr (!X_EARLY_C) store_x();
     if constexpr (ATT) stamp(51);
     else fstamp(51);
     touch_done();
@@ -2028,20 +2085,37 @@ __global__ __launch_bounds__(NT, 1) void block_kernel(const EmBlockArgs a_in, lo
     }
     stamp(15);
     // x += 0.5 * FFN_macaron(norm_ff_macaron(x))  (encoder_layer.py:108-121); the ring goes over to the q / k / v projections
-    ffn(pa0, 512, 1536, 0.5f, ffm_w1, ffm_w2, true, ffm_b1g, a.wqkv, [&] { read_unit(a.wqkv, 2, ring[2]); });
+    ffn(pa0, 512, 1536, 0.5f, ffm_w1, ffm_w2, !X_EARLY_A, ffm_b1g, a.wqkv, [&] { read_unit(a.wqkv, 2, ring[2]); });
     if constexpr (RELU) {
       if (ffn_exit) return;
     }
+    // Where x leaves the chip.  Round 3 stored it at the very END of the kernel, from an LDS parking place: its eight
+    // 16-byte stores per lane, issued in front of the q / k / v weight requests, sat in the same in-order count the waits
+    // for those requests use and their slow acknowledgement from L2 stalled the stream - norm_mha took 4 300 cycles to
+    // its first barrier against 3 100 for the other LayerNorms (profiles/r03c_*).  Since round 5 the q / k / v stream's
+    // units 0 - 2 are requested INSIDE the macaron module (nbase / after() above), so here, behind its reduction, x is
+    // final and those three units are already in flight: stores issued now are YOUNGER than every load the stream waits
+    // for before its fourth unit - a LayerNorm and three units away.  Round 12 stores x here, through store_x_counted():
+    // unconditional, so that the waits behind count the stores instead of waiting for them (under `if (row_ok)` the
+    // first wait of the q / k / v stream stayed vmcnt(13), with the stores counted it is 21), in straight-line code behind
+    // the reduction's switch (a store inside one of its cases is as uncounted as one under row_ok).  The 8 MB of x
+    // drain under norm_mha, where a CU asks memory for nothing else, instead of in one burst with the last of q / k / v;
+    // the re-park, the closing reload and the closing stores go.  Measured (profiles/r12a_*, one stream): block<D|A>
+    // 42.0 -> 39.9 us, block<A> 24.6 -> 23.7 us; stamps of workgroup (0, 0): norm_mha (22 -> 15) 2 200 -> 3 750 cycles
+    // - the stores' issue, and the first barrier waits for the wave that issues last - the q / k / v stream (15 -> 40)
+    // 10 000 -> 8 800, and every stage in front of it shorter as well (entry -> 22: 72 100 -> 67 800) although its code
+    // is the same - presumably the launch in front no longer ends in a burst that this one starts under; that part is
+    // an observation, its cause was not isolated.  Behind norm_mha's
+    // normalisation, or half either side of the LayerNorm, the step was slower (table at store_x_counted).
+    // The streaming and the folded instantiations keep the round-3 form: a few workgroups, no chip-wide burst.  The
+    // q / k / v stores themselves stay inside the stream: batched behind it they cost MORE, a store-issue tail of 3 300
+    // cycles that the stream otherwise hides (profiles/r03c_*).
     stamp(22);
-    // (x is stored at the very END of the kernel, from its LDS parking place: its eight 16-byte stores per lane, issued
-    // in front of the q / k / v weight requests, sat in the same in-order count the waits for those requests use and
-    // their slow acknowledgement from L2 stalled the stream - norm_mha took 4 300 cycles to its first barrier against
-    // 3 100 for the other LayerNorms.  The q / k / v stores themselves stay inside the stream: batched behind it they
-    // cost MORE, a store-issue tail of 3 300 cycles that the stream otherwise hides; profiles/r03c_*)
+    if constexpr (X_EARLY_A) store_x_counted();
     ln_to_act(pa1, 0, 256, 0);                     // norm_mha (encoder_layer.py:123-127)
     stamp(15);
     qkv_proj(pa1, a.qh, a.kh, a.vt);
-    {
+    if constexpr (!X_EARLY_A) {
       const float4* const xp = (const float4*)(smem + TILE_OFF) + tid;
 #pragma unroll
       for (int mi = 0; mi < 2; ++mi)
@@ -2149,6 +2223,7 @@ extern "C" int em_conformer_block_fused(int mode, const EmBlockArgs* a, void* st
     if (!relu || a->ffn_split > 16 || nch_all % (2 * a->ffn_split) != 0 || !a->ffn_part || !a->ffn_ticket) return EM_ERR_BAD_ARG;
   }
   if (!relu && mode == EM_BLOCK_D) return EM_ERR_UNSUPPORTED;
+  if (!relu && (long long)a->T * D * 4 >= (1ll << 31)) return EM_ERR_UNSUPPORTED;  // (an utterance's rows are one buffer resource: store_x_counted)
   if (need_a) {
     if (!a->ffm_w1 || !a->ffm_w2 || !a->wqkv || !a->qh || !a->kh || !a->vt) return EM_ERR_BAD_ARG;
     if (a->Tpad % 64 != 0 || a->Tpad < em_cdiv(a->T, BM) * BM) return EM_ERR_BAD_ARG;

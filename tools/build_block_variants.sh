@@ -3,7 +3,10 @@
 #   espnet_amd/lib/dbg/lib_nt.so     -DEM_BLOCK_NO_TOUCH   (no L2 warm-up)
 #   espnet_amd/lib/dbg/lib_<d>.so    -DEM_BLOCK_DBG=<d>    (1 no MFMA / epilogue, 4 no FFN barrier, 8 no H exchange, 16 no Swish)
 #   espnet_amd/lib/dbg/lib_v<n>.so   -DEM_BLOCK_VAR=<n>    (A/B variants: 1 pinned-group FFN iteration, 4 FFN chunk order
-#                                                           rotated per utterance, 16 packed-f32 depthwise conv; sums combine)
+#                                                           rotated per utterance, 16 packed-f32 depthwise conv; sums combine;
+#                                                           round 12, where the row stores go: 0x10000 x of the A part at
+#                                                           the end of the kernel again, 0x20000 x of the C part at the end
+#                                                           again, 0x40000 the GLU stores counted too, e.g. v0x30000)
 #   espnet_amd/lib/dbg/lib_fine.so   -DEM_BLOCK_FINE=1     (EM_BLOCK_STAMPS=1 prints sub-stage stamps of all four waves)
 # Used for profiles/r02l, r02m, r02o, r02q and the round-3 A/B calls (tools/gpu_calls.sh).  dbg builds give wrong results by
 # design: timing only.   usage: bash tools/build_block_variants.sh nt 4 v1 v16 fine
