@@ -13,6 +13,27 @@
  *   - return value: EM_OK or a negative EM_ERR_* code; nothing throws across the ABI;
  *   - dtype: EM_F32 (exact-f32 MFMA, parity mode) or EM_BF16 (bf16 MFMA, f32 accumulate).
  *     "act" buffers hold elements of that dtype; residual stream / features / logits are f32.
+ *
+ * Scratch memory (every `workspace` / `ws` / `z_ws` parameter, and the members of EmSearchBuffers)
+ *   - What scratch holds on entry is ignored: no output bit of an entry point depends on it.  A caller may hand over
+ *     memory that was never initialised, that holds NaN or huge bit patterns, or that an earlier call of any shape left
+ *     behind; where a launch sequence needs zeros or finite padding in its scratch it writes them itself (the head slabs
+ *     of the batch encoders, the walk's states, the streaming tickets).  Every index the library loads from scratch it
+ *     has written earlier in the same call, or clamps where it is used.
+ *   - Outputs are written whole within the regions stated per function, whatever they held before; outside those
+ *     regions they are not touched.  The regions (tests/test_gpu_scratch_independence.py holds the library to them):
+ *       em_conformer_encode, em_ebranchformer_encode, em_transformer_encode: enc_out, enc_act [B][T][d] whole - the
+ *         frames at and behind olens[b] too (the padded batch's values, finite); w->ctc_ids [B][T] whole when planned;
+ *       em_cb_encode_blocks[_batch], em_cbt_encode_blocks[_batch]: the blocks in place and next_ctx whole;
+ *       em_dec_seq_nll, em_lm_seq_nll, em_lm_head_nll: nll whole (exactly 0.0 where nothing is scored);
+ *       em_ctc_forced_align: every output whole (labels -1, spans -1, scores 0 behind the lengths);
+ *       em_transducer_greedy: ylens and score whole, tokens[b][< ylens[b]], the traces [b][< olens[b]];
+ *       em_transducer_lattice_logp: the nodes t < xlens[mem_of[n]], u <= ylens[n] (the label of u == ylens[n]: -inf).
+ *   - EmSearchBuffers: the caller writes xlens / maxlens / minlens per search and ZEROES ONCE, at allocation, mem_vT,
+ *     rnn_hs, rnn_cs and rnn_hin (and again mem_vT whenever Tpad changes under it: the streaming search).  The library
+ *     leaves their zero regions zero - the columns T .. Tpad of mem_vT, the channels nhid .. d of every recurrent state
+ *     row - so the same set serves any number of searches.  Every other member may hold anything when em_search_init
+ *     is called; the host reads the ended lists up to end_count only.
  */
 #ifndef ESPNET_AMD_H_
 #define ESPNET_AMD_H_
@@ -334,7 +355,7 @@ int em_conformer_encode_plan(int dtype, const EmConformerWeights* w, int32_t fla
  *   the shape there.  Equal to em_conformer_encode_plan for every other model.                                          */
 int em_conformer_encode_plan_for(int dtype, const EmConformerWeights* w, int32_t flags, int32_t B, int32_t T_f);
 
-/* bytes of scratch em_conformer_encode needs for (B, T_f) */
+/* bytes of scratch em_conformer_encode needs for (B, T_f); what `workspace` holds on entry is ignored ("Scratch memory" above) */
 size_t em_conformer_workspace_bytes(int dtype, const EmConformerWeights* w, int32_t B, int32_t T_f);
 
 /*   feats      [B][T_f][n_mels] f32 (log-mel, not yet mean-normalised)
@@ -934,6 +955,7 @@ typedef struct EmRnnLayer {
   const float* bias; /* [G*nhid] */
 } EmRnnLayer;
 
+/* (which members the caller zeroes once, and what may hold anything at em_search_init: "Scratch memory" above) */
 typedef struct EmSearchBuffers {
   const int32_t *xlens, *maxlens, *minlens; /* [B] valid memory frames, max / min output length */
   float* ctc_lpT;                           /* [V][B*T] CTC.log_softmax(enc) (scorers/ctc.py:96), TRANSPOSED:
@@ -1066,7 +1088,7 @@ int em_lm_step(int dtype, const EmSearchParams* p, const EmSearchBuffers* b, int
  *     the pre-norm layers, after_norm and the head.  lm->kind must be EM_LM_TRANSFORMER (EM_ERR_BAD_ARG otherwise); with
  *     positional encoding lm->pe must hold at least Lp rows (the caller's pack).  ws: em_lm_seq_nll_workspace_bytes bytes
  *     of device memory (0 = shape not covered: em_lm_seq_nll then returns EM_ERR_UNSUPPORTED and the caller splits the
- *     batch); a smaller one: EM_ERR_WORKSPACE.                                                                          */
+ *     batch); a smaller one: EM_ERR_WORKSPACE.  Contents of ws on entry: ignored ("Scratch memory" above).              */
 int em_lm_causal_attention(int dtype, const void* qkv, const int32_t* x, int32_t B, int32_t Lp, int32_t d, int32_t heads,
                            void* ctx, void* stream);
 size_t em_lm_head_nll_workspace_bytes(int dtype, int32_t M, int32_t V);
@@ -1104,7 +1126,7 @@ int em_lm_seq_nll(int dtype, const EmLmWeights* lm, const int32_t* x, const int3
  *     its token array = the reference's tgt_mask; em_dec_seq_src_attention), after_norm and em_lm_head_nll, on the
  *     row-major matrices of dw.  dw->pe must hold at least Lp rows.  ws: em_dec_seq_nll_workspace_bytes bytes of device
  *     memory (0 = shape not covered: em_dec_seq_nll then returns EM_ERR_UNSUPPORTED and the caller splits the batch); a
- *     smaller one: EM_ERR_WORKSPACE.                                                                                    */
+ *     smaller one: EM_ERR_WORKSPACE.  Contents of ws on entry: ignored ("Scratch memory" above).                        */
 int em_dec_seq_embed_f32(const float* embed, const float* pe, const int32_t* tok, int32_t M, int32_t V, int32_t d,
                          int32_t Lp, int32_t pe_len, float* x, void* stream);
 int em_dec_seq_src_attention(int dtype, const void* qs, const void* kmem, int32_t ldk, const void* vT,
@@ -1240,7 +1262,8 @@ int em_transducer_joint_logp(int dtype, const EmTransducerWeights* w, const floa
  *   at frames t < olens[b] only: frame_tok [B][T] the arg-max, frame_top [B][T] its log-probability, frame_margin [B][T]
  *   the top-1 minus top-2 logit.  Per frame: one launch over the vocabulary tiles, one decision launch, one launch per
  *   layer and one for lin_dec + the next frame's tanh.  B <= 64 (EM_ERR_UNSUPPORTED above; the caller splits the batch);
- *   ws: em_transducer_greedy_workspace_bytes(dtype, w, B, T) bytes of device memory, a smaller one: EM_ERR_WORKSPACE.  */
+ *   ws: em_transducer_greedy_workspace_bytes(dtype, w, B, T) bytes of device memory, a smaller one: EM_ERR_WORKSPACE;
+ *   its contents on entry are ignored ("Scratch memory" above).                                                         */
 int em_transducer_greedy(int dtype, const EmTransducerWeights* w, const float* enc_proj, const int32_t* olens, int32_t B,
                          int32_t T, int32_t* tokens, int32_t* ylens, float* score, int32_t* frame_tok, float* frame_top,
                          float* frame_margin, void* ws, size_t ws_bytes, void* stream);
