@@ -244,9 +244,15 @@ class ESPnetASRModel(torch.nn.Module):
         `em_transducer_seq_nll`; the (N, T, U, V) joint output never exists.  A batch whose lattice is outside the
         shapes of one call goes through in slices of candidates.  `enc_proj`: `joint_network.enc_proj_device(encoder_out)`
         when the caller holds it already (several calls on one batch of utterances)."""
-        if not self.use_transducer_decoder:
-            raise RuntimeError("transducer_nll: the model has no joint network (decoder: transducer); the attention "
-                               "decoder's likelihood is `nll`")
+        parts = self._transducer_lattice_parts(
+            "transducer_nll", "the attention decoder's likelihood is `nll`",
+            lambda jn, lat, xl, yl, mem: jn.seq_nll_device(lat, xl, yl, mem),
+            encoder_out, encoder_out_lens, ys_pad, ys_pad_lens, mem_of, enc_proj)
+        return parts[0] if len(parts) == 1 else torch.cat(parts)
+
+    def _check_transducer_candidates(self, encoder_out, encoder_out_lens, ys_pad, ys_pad_lens, mem_of):
+        """The host checks of a batch of candidate transcripts: host tensors (ys cut to the longest length, ylens, xlens,
+        mem_of or None) and the longest length, or ValueError."""
         ys = torch.as_tensor(ys_pad).detach().to("cpu", torch.long)
         ylens = torch.as_tensor(ys_pad_lens).detach().to("cpu", torch.long)
         xlens = torch.as_tensor(encoder_out_lens).detach().to("cpu", torch.long)
@@ -272,16 +278,36 @@ class ESPnetASRModel(torch.nn.Module):
             mo = torch.as_tensor(mem_of).detach().to("cpu", torch.long)
             if mo.dim() != 1 or mo.numel() != N or int(mo.min()) < 0 or int(mo.max()) >= Bm:
                 raise ValueError(f"mem_of must hold {N} utterance numbers in [0, {Bm})")
+        return ys, ylens, xlens, mo, longest
+
+    def _transducer_lattice_parts(self, what, other_route, score, encoder_out, encoder_out_lens, ys_pad, ys_pad_lens,
+                                  mem_of, enc_proj, checked=False) -> list:
+        """What `transducer_nll` and `transducer_align` share: the host checks of the candidates (every ValueError before
+        anything is launched), the slicing over candidates when the lattice is outside the shapes of one call, and per
+        slice the chain `teacher_forced_proj` -> `lattice_logp_device` -> score(joint_network, lat, xlens, ylens, mem_of),
+        all on the device.  Returns the slices' results in order.  `what` names the caller in the messages.  `checked`:
+        the caller vouches for the lengths and for ys_pad (ids of the vocabulary, no blank inside a transcript; all its
+        columns become lattice columns) - they may then live on the device, as the greedy walk leaves them, and nothing
+        is read back."""
+        if not self.use_transducer_decoder:
+            raise RuntimeError(f"{what}: the model has no joint network (decoder: transducer); {other_route}")
+        if checked:
+            ys, ylens, xlens, mo = ys_pad, ys_pad_lens, encoder_out_lens, mem_of
+            N, T, longest = int(ys.shape[0]), int(encoder_out.shape[1]), int(ys.shape[1])
+        else:
+            ys, ylens, xlens, mo, longest = self._check_transducer_candidates(encoder_out, encoder_out_lens, ys_pad,
+                                                                              ys_pad_lens, mem_of)
+            N, T = int(ys.size(0)), int(encoder_out.shape[1])
         L.require_gpu(encoder_out, "encoder_out")
         dev, dec, jn = encoder_out.device, self.decoder, self.joint_network
         cap = int(L.load().em_transducer_seq_nll_max_tokens())
         if longest > cap:
-            raise NotImplementedError(f"transducer_nll: a transcript of {longest} tokens, the recursion takes up to {cap}")
+            raise NotImplementedError(f"{what}: a transcript of {longest} tokens, the recursion takes up to {cap}")
         rows = N
         while rows > 1 and jn.lattice_workspace_bytes(dec, dev, rows, T, longest) == 0:
             rows = (rows + 1) // 2
         if jn.lattice_workspace_bytes(dec, dev, rows, T, longest) == 0:
-            raise NotImplementedError(f"transducer_nll: the lattice of one candidate, {T} frames x {longest} tokens, is "
+            raise NotImplementedError(f"{what}: the lattice of one candidate, {T} frames x {longest} tokens, is "
                                       "outside the shapes of one call")
         if enc_proj is None:
             enc_proj = jn.enc_proj_device(encoder_out)
@@ -297,8 +323,33 @@ class ESPnetASRModel(torch.nn.Module):
             tg = ys[s:e].to(torch.int32).contiguous().to(dev, non_blocking=True)
             dec_proj = dec.teacher_forced_proj(tg, yl, device=dev)
             lat = jn.lattice_logp_device(dec, enc_proj, xl, dec_proj, tg, yl, mem)
-            parts.append(jn.seq_nll_device(lat, xl, yl, mem))
-        return parts[0] if len(parts) == 1 else torch.cat(parts)
+            parts.append(score(jn, lat, xl, yl, mem))
+        return parts
+
+    @torch.no_grad()
+    def transducer_align(self, encoder_out: torch.Tensor, encoder_out_lens, ys_pad, ys_pad_lens,
+                         mem_of=None, enc_proj=None):
+        """WHEN the transducer emits each token of given transcripts: the best (Viterbi) path of every transcript through
+        its lattice, `em_transducer_seq_align` - the max-product twin of `transducer_nll`, which sums over all paths.
+        Arguments, host checks (every ValueError before anything is launched), the chain on the device
+        (`TransducerDecoder.teacher_forced_proj`, `em_transducer_lattice_logp`, then the alignment launch) and the slicing
+        over candidates are `transducer_nll`'s.  Returns device tensors, everything only enqueued:
+          tok_frame (N, L) int32  the encoder frame at which token u is emitted, -1 behind the transcript (L: the longest
+                                  transcript's length);
+          tok_logp  (N, L) f32    the token's log-probability at that lattice node, 0 behind the transcript;
+          frame_u   (N, T) int32  the number of tokens emitted when the path leaves frame t, -1 behind the utterance;
+          total     (N,)   f32    the path's log-probability (<= -transducer_nll), -inf for an utterance without frames."""
+        return self._transducer_align_rows(encoder_out, encoder_out_lens, ys_pad, ys_pad_lens, mem_of, enc_proj)
+
+    def _transducer_align_rows(self, encoder_out, encoder_out_lens, ys_pad, ys_pad_lens, mem_of=None, enc_proj=None,
+                               checked=False):
+        """`transducer_align`; `checked`: lengths and transcripts are the caller's own (`_transducer_lattice_parts`), on the
+        device or the host, and nothing is verified or read back."""
+        parts = self._transducer_lattice_parts(
+            "transducer_align", "CTC forced alignment is `ctc.forced_align_device`",
+            lambda jn, lat, xl, yl, mem: jn.seq_align_device(lat, xl, yl, mem),
+            encoder_out, encoder_out_lens, ys_pad, ys_pad_lens, mem_of, enc_proj, checked=checked)
+        return parts[0] if len(parts) == 1 else tuple(torch.cat(cols) for cols in zip(*parts))
 
     @torch.no_grad()
     def batchify_transducer_nll(self, encoder_out: torch.Tensor, encoder_out_lens, ys_pad, ys_pad_lens,

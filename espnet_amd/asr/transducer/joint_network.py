@@ -127,6 +127,31 @@ class JointNetwork(PackedModule):
         return nll
 
     @torch.no_grad()
+    def seq_align_device(self, lat, xlens, ylens, mem_of=None, ws=None):
+        """`em_transducer_seq_align`: the best path through lat (N, T, Lmax + 1, 2) f32 and its back-trace.  Returns device
+        tensors (tok_frame (N, Lmax) int32: the frame at which token u is emitted, -1 behind the transcript; tok_logp
+        (N, Lmax) f32: the label's log-probability there, 0 behind it; frame_u (N, T) int32: the tokens emitted when the
+        path leaves frame t, -1 behind the utterance; total (N,) f32: the path's log-probability, -inf without a path).
+        xlens (Bm,), ylens (N,), mem_of (N,) or None: int32, device.  `ws`: a uint8 workspace for the back-pointers
+        (default: one of the size the library asks for)."""
+        L.require_gpu(lat, "lat")
+        dev = lat.device
+        N, T, Lmax = int(lat.shape[0]), int(lat.shape[1]), int(lat.shape[2]) - 1
+        lib = L.load()
+        if ws is None:
+            ws = torch.empty(max(int(lib.em_transducer_seq_align_workspace_bytes(N, T, Lmax)), 1), dtype=torch.uint8,
+                             device=dev)
+        tok_frame = torch.empty(N, Lmax, dtype=torch.int32, device=dev)
+        tok_logp = torch.empty(N, Lmax, dtype=torch.float32, device=dev)
+        frame_u = torch.empty(N, T, dtype=torch.int32, device=dev)
+        total = torch.empty(N, dtype=torch.float32, device=dev)
+        L.check(lib.em_transducer_seq_align(L.ptr(lat), L.ptr(xlens), int(xlens.numel()), T, Lmax, L.ptr(ylens),
+                                            L.ptr(mem_of), N, L.ptr(tok_frame), L.ptr(tok_logp), L.ptr(frame_u),
+                                            L.ptr(total), L.ptr(ws), int(ws.numel()), L.current_stream_ptr()),
+                "em_transducer_seq_align")
+        return tok_frame, tok_logp, frame_u, total
+
+    @torch.no_grad()
     def forward(self, enc_out: torch.Tensor, dec_out: torch.Tensor) -> torch.Tensor:
         raise NotImplementedError("JointNetwork.forward on broadcast (B, T, U) lattices is training only; decoding goes "
                                   "through enc_proj_device / em_transducer_joint_logp")

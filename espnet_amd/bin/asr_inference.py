@@ -317,6 +317,103 @@ class Speech2Text:
                                 total=float(row[T + 3 * Lm])))
         return results
 
+    # ------------------------------------------------------------------ transducer forced alignment: token timestamps
+    @torch.no_grad()
+    def transducer_align(self, speech: Union[torch.Tensor, np.ndarray], text=None):
+        """Token timestamps of one utterance under a transducer model: `batch_transducer_align` for a batch of one."""
+        if isinstance(speech, np.ndarray):
+            speech = torch.tensor(speech)
+        speech = speech.unsqueeze(0).to(torch.float32)
+        return self.batch_transducer_align(speech, [speech.size(1)], None if text is None else [text])[0]
+
+    def _greedy_walk_device(self, st):
+        """The greedy walk's (tokens (B, T) int32, ylens (B,) int32) of an encoded batch, left on the device."""
+        from espnet_amd.asr.transducer.beam_search_transducer import MAX_WALK_ROWS, BeamSearchTransducer
+
+        walker = self.beam_search_transducer or getattr(self, "_greedy_walker", None)
+        if walker is None:  # (an object built with ctc_greedy=True has no search of its own)
+            m = self.asr_model
+            walker = self._greedy_walker = BeamSearchTransducer(decoder=m.decoder, joint_network=m.joint_network, beam_size=1)
+        B = int(st.enc_act.shape[0])
+        parts = [walker.greedy_device(st.enc_act[b0 : b0 + MAX_WALK_ROWS].contiguous(), st.olens_dev[b0 : b0 + MAX_WALK_ROWS])
+                 for b0 in range(0, B, MAX_WALK_ROWS)]
+        if len(parts) == 1:
+            return parts[0][0], parts[0][1]
+        return torch.cat([p[0] for p in parts]), torch.cat([p[1] for p in parts])
+
+    @torch.no_grad()
+    def batch_transducer_align(self, speech: torch.Tensor, speech_lengths: Sequence[int], texts=None):
+        """Transducer forced alignment (`ESPnetASRModel.transducer_align`: the best path through the RNN-T lattice) of one
+        transcript per utterance - the token timestamps of a model without CTC head, where `batch_align` has nothing to
+        align with.  speech (B, N) zero padded, lengths host ints, texts[b] a string (tokenised with this object's
+        tokenizer) or a list of token ids, an empty transcript allowed.  texts=None aligns every utterance's own
+        GREEDY-WALK hypothesis (`BeamSearchTransducer.greedy_device`), whatever `beam_size` this object was built with - it
+        is `batch_decode`'s hypothesis only for beam_size <= 1 - so one call gives hypothesis and timings; the walk's
+        tokens stay on the device.
+
+        Returns per utterance a dict: `tokens` = [(token, token_id, start_s, end_s, logp)] with start_s = frame x
+        `seconds_per_frame` and end_s = (frame + 1) x `seconds_per_frame` of the encoder frame at which the token is
+        emitted and logp its log-probability at that lattice node; `token_int` (the ids); `frame_u` (the (T_b,) int64
+        number of tokens emitted when the path leaves each encoder frame); `total` (log-probability of the path).  An
+        utterance without a path - no encoder frame - has total = -inf, and its tokens carry start_s = end_s = -1.0 and
+        logp = 0.0: there is no time to report.  Several tokens may share a frame.  The receptive-field offset of the subsampling
+        convolutions is not modelled.  One D2H copy per batch (texts=None beyond `align_no_sync_frames` encoder frames:
+        one more word, the longest hypothesis' length, is read first)."""
+        m = self.asr_model
+        if not getattr(m, "use_transducer_decoder", False):
+            raise RuntimeError("batch_transducer_align: the model has no joint network (decoder: transducer); the CTC head's "
+                               "forced alignment is batch_align")
+        B = int(speech.shape[0])
+        ids = None
+        if texts is not None:
+            if len(texts) != B:
+                raise ValueError(f"{len(texts)} transcripts for {B} utterances")
+            ids = [self._target_ids(t) for t in texts]
+            V = getattr(m, "vocab_size", None)
+            if V is not None and any(v < 0 or v >= V for y in ids for v in y):
+                raise ValueError(f"token ids must lie in [0, {V})")
+        speech = speech.to(self.device, torch.float32, non_blocking=True)
+        st = m.encode_device(speech, [int(n) for n in speech_lengths], isolate=True)
+        if ids is None:
+            from espnet_amd import lib as L
+
+            tokens, tlens = self._greedy_walk_device(st)
+            if tokens.shape[1] > min(self.align_no_sync_frames, int(L.load().em_transducer_seq_nll_max_tokens())):
+                # the row stride is the lattice's Lmax: the prediction network runs Lmax + 1 steps and the recursion has a
+                # thread per column up to its cap - one small sync for the longest hypothesis
+                tokens = tokens[:, : int(tlens.max())].contiguous()
+            outs = m._transducer_align_rows(st.enc_act, st.olens_dev, tokens, tlens, checked=True)
+        else:
+            tokens = tlens = None
+            ys = torch.zeros(B, max((len(y) for y in ids), default=0), dtype=torch.long)
+            for b, y in enumerate(ids):
+                ys[b, : len(y)] = torch.tensor(y, dtype=torch.long)
+            outs = m.transducer_align(st.enc_act, torch.tensor(st.olens), ys, torch.tensor([len(y) for y in ids]))
+        tok_frame, tok_logp, frame_u, total = outs
+        T, Lm = int(frame_u.shape[1]), int(tok_frame.shape[1])
+        # the one D2H copy: everything as f32 columns of one matrix (frame counts and ids are far below 2**24)
+        cols = [frame_u, tok_frame, tok_logp, total[:, None]]
+        if tokens is not None:
+            cols += [tlens[:, None], tokens]
+        off_tok = T + 2 * Lm + 2  # column of the first hypothesis token (behind `total` and the token count)
+        host = torch.cat([c.to(torch.float32) for c in cols], dim=1).cpu().numpy()
+        spf = self.seconds_per_frame
+        results = []
+        for b in range(B):
+            row = host[b]
+            if ids is None:
+                n = int(row[off_tok - 1])
+                y = row[off_tok : off_tok + n].astype(np.int64).tolist()
+            else:
+                y = ids[b]
+            names = self.converter.ids2tokens(y)
+            fr, lp = row[T : T + Lm], row[T + Lm : T + 2 * Lm]
+            toks = [(names[i], int(y[i]), float(fr[i]) * spf, (float(fr[i]) + 1.0) * spf, float(lp[i])) if fr[i] >= 0 else
+                    (names[i], int(y[i]), -1.0, -1.0, 0.0) for i in range(len(y))]  # (frame -1: no path)
+            results.append(dict(tokens=toks, token_int=[int(v) for v in y],
+                                frame_u=torch.from_numpy(row[: st.olens[b]].astype(np.int64)), total=float(row[T + 2 * Lm])))
+        return results
+
     # ------------------------------------------------------------------ attention-decoder likelihood of given transcripts
     nll_rows_per_call = 100  # candidates per enqueue (ESPnetASRModel.batchify_nll's default slice)
 

@@ -410,6 +410,8 @@ _SIGNATURES = {
     "em_transducer_lattice_logp_workspace_bytes": (_sz, [C.c_int, C.POINTER(EmTransducerWeights), _i32, _i32, _i32]),
     "em_transducer_seq_nll": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _i32, _vp, _vp]),
     "em_transducer_seq_nll_max_tokens": (_i32, []),
+    "em_transducer_seq_align": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "em_transducer_seq_align_workspace_bytes": (_sz, [_i32, _i32, _i32]),
     "em_ctc_greedy": (C.c_int, [C.c_int, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _i32,
                                 _vp, _vp, _vp, _vp, _vp]),
 }

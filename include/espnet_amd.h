@@ -28,7 +28,8 @@
  *       em_dec_seq_nll, em_lm_seq_nll, em_lm_head_nll: nll whole (exactly 0.0 where nothing is scored);
  *       em_ctc_forced_align: every output whole (labels -1, spans -1, scores 0 behind the lengths);
  *       em_transducer_greedy: ylens and score whole, tokens[b][< ylens[b]], the traces [b][< olens[b]];
- *       em_transducer_lattice_logp: the nodes t < xlens[mem_of[n]], u <= ylens[n] (the label of u == ylens[n]: -inf).
+ *       em_transducer_lattice_logp: the nodes t < xlens[mem_of[n]], u <= ylens[n] (the label of u == ylens[n]: -inf);
+ *       em_transducer_seq_align: every output whole (frames -1, log-probabilities 0 behind the lengths).
  *   - EmSearchBuffers: the caller writes xlens / maxlens / minlens per search and ZEROES ONCE, at allocation, mem_vT,
  *     rnn_hs, rnn_cs and rnn_hin (and again mem_vT whenever Tpad changes under it: the streaming search).  The library
  *     leaves their zero regions zero - the columns T .. Tpad of mem_vT, the channels nhid .. d of every recurrent state
@@ -1310,6 +1311,37 @@ size_t em_transducer_lattice_logp_workspace_bytes(int dtype, const EmTransducerW
 int em_transducer_seq_nll(const float* lat, const int32_t* xlens, int32_t Bm, int32_t T, int32_t Lmax, const int32_t* ylens,
                           const int32_t* mem_of, int32_t N, float* nll, void* stream);
 int32_t em_transducer_seq_nll_max_tokens(void);
+
+/* ---- transducer forced alignment (csrc/transducer_align.hip): WHEN each token of a given transcript is emitted - the
+ *      best (max-product, Viterbi) path through the lattice of em_transducer_lattice_logp and its back-trace, the twin of
+ *      em_transducer_seq_nll as em_ctc_forced_align is of em_ctc_seq_nll.  All pointers on the device; one launch for all
+ *      candidates, enqueue only.
+ *   em_transducer_seq_align.  lat, xlens, Bm, T, Lmax, ylens, mem_of, N as em_transducer_seq_nll takes them, with the same
+ *      clamping of m, T_b and U.  With b = lat[..][0], e = lat[..][1] of candidate n:
+ *        v[0][0]  = 0
+ *        v[t][u]  = max(v[t-1][u] + b[t-1][u], v[t][u-1] + e[t][u-1])   (a missing neighbour is -inf)
+ *        total[n] = v[T_b-1][U] + b[T_b-1][U]
+ *      All f32; every v is ONE f32 add on top of its predecessor, so a path's value is its terms added in path order.
+ *      Tie rule: the label move (from (t, u-1)) is taken only if it is STRICTLY greater than the blank move (from
+ *      (t-1, u)); equal values keep the blank move.  The path is the back-trace from (T_b-1, U) to (0, 0).
+ *   Outputs:
+ *      tok_frame [N][Lmax] i32  the frame t at which token u is emitted (the path goes (t, u) -> (t, u+1)), non-decreasing
+ *                               in u; -1 for u >= U;
+ *      tok_logp  [N][Lmax] f32  e[t][u] at that node; 0 for u >= U;
+ *      frame_u   [N][T]    i32  the number of tokens emitted when the path leaves frame t; -1 for t >= T_b;
+ *      total     [N]       f32.
+ *      T_b == 0, or a path value of -inf (possible only with a caller's own lattice): total = -inf, tok_frame and frame_u
+ *      read -1, tok_logp reads 0; never NaN.  Every element of every output row is written, padding included (tok_frame
+ *      and tok_logp may be NULL when Lmax == 0).  Only the nodes t < T_b, u <= U are read; a row's outputs depend on its
+ *      own lattice only: bit for bit the same whatever N, Lmax, mem_of and the companions are.
+ *   Lmax <= em_transducer_seq_nll_max_tokens() (1 023) and N * T * (Lmax+1) <= 2^28; other shapes: EM_ERR_UNSUPPORTED, and
+ *      em_transducer_seq_align_workspace_bytes returns 0 for them.  ws: that many bytes of device memory, the back-pointer
+ *      store (one bit per node, [N][Lmax+1][ceil(T / 32)] 32-bit words); a smaller one: EM_ERR_WORKSPACE.  Its contents on
+ *      entry are ignored ("Scratch memory" above): the back-trace reads only words that this call's recursion wrote.    */
+int em_transducer_seq_align(const float* lat, const int32_t* xlens, int32_t Bm, int32_t T, int32_t Lmax,
+                            const int32_t* ylens, const int32_t* mem_of, int32_t N, int32_t* tok_frame, float* tok_logp,
+                            int32_t* frame_u, float* total, void* ws, size_t ws_bytes, void* stream);
+size_t em_transducer_seq_align_workspace_bytes(int32_t N, int32_t T, int32_t Lmax);
 
 /* ---- §8(f) rank 3: block-synchronous streaming search, BatchBeamSearchOnline
  *      (espnet2/legacy/nets/batch_beam_search_online.py:155-534).  The host mirrors the reference's
