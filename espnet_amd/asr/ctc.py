@@ -197,6 +197,101 @@ class CTC(PackedModule):
         host = [x.cpu() if torch.is_tensor(x) else x for x in (hlens, ys_pad, ylens)]
         return self.forced_align_device(act, host[0], host[1], host[2], int(blank_idx))[0].to(torch.int64)
 
+    # ------------------------------------------------------------------ segmentation (csrc/ctc_segment.hip)
+    @staticmethod
+    def check_segmentable(olens, gt, clens, vocab, T=None):
+        """The host-side checks of a segmentation, before anything is launched: lengths inside their rows, C_b >= 2,
+        C_b - 1 <= T_b, every id of the columns 1 .. C_b - 1 in [0, vocab) (the blank is allowed: separators).  `gt`: one
+        list of columns per recording.  Raises ValueError."""
+        for b, (T_b, row, C_b) in enumerate(zip(olens, gt, clens)):
+            T_b, C_b = int(T_b), int(C_b)
+            if C_b > len(row) or T_b < 0 or (T is not None and T_b > T):
+                raise ValueError(f"recording {b}: a length lies outside its row")
+            if C_b < 2:
+                raise ValueError(f"recording {b}: {C_b} ground-truth columns (the start symbol and at least one more are needed)")
+            if C_b - 1 > T_b:
+                raise ValueError(f"recording {b}: {T_b} encoder frames cannot carry {C_b - 1} ground-truth columns")
+            if any(int(v) < 0 or int(v) >= vocab for v in row[1:C_b]):
+                raise ValueError(f"recording {b}: token ids must lie in [0, {vocab})")
+
+    @staticmethod
+    def _segment_inputs(olens, gt, clens, vocab, T, dev):
+        """(olens_d, gt_d, clens_d, Cmax): HOST data is checked (`check_segmentable`) and copied over, int32 DEVICE
+        tensors are taken as they are, a mixture is refused."""
+        given = (olens, gt, clens)
+        on_dev = [torch.is_tensor(x) and x.is_cuda for x in given]
+        if all(on_dev):
+            if any(x.dtype != torch.int32 for x in given) or gt.dim() != 2 or gt.shape[1] < 2:
+                raise ValueError("device-side olens / gt / clens must be int32, gt (B, Cmax) with Cmax >= 2")
+            if int(olens.numel()) != int(gt.shape[0]) or int(clens.numel()) != int(gt.shape[0]):
+                raise ValueError(f"olens and clens must have {int(gt.shape[0])} entries")
+            return olens.contiguous(), gt.contiguous(), clens.contiguous(), int(gt.shape[1])
+        if any(on_dev):
+            raise ValueError("olens, gt and clens must be all host data or all device tensors")
+        ol, rows, cl = [x.tolist() if torch.is_tensor(x) else list(x) for x in given]
+        if not (len(ol) == len(rows) == len(cl)) or not rows:
+            raise ValueError("olens, gt and clens must have one entry per recording")
+        rows = [list(r) for r in rows]
+        CTC.check_segmentable(ol, rows, cl, vocab, T)
+        Cmax = max(cl)
+        g = torch.zeros(len(rows), Cmax, dtype=torch.int32)
+        for b, (r, n) in enumerate(zip(rows, cl)):
+            g[b, 1:n] = torch.tensor([int(v) for v in r[1:n]], dtype=torch.int32)
+        olens_d, clens_d, gt_d = (torch.as_tensor(v, dtype=torch.int32).to(dev, non_blocking=True) for v in (ol, cl, g))
+        return olens_d, gt_d, clens_d, Cmax
+
+    def segment_device(self, enc_act: torch.Tensor, olens, gt, clens, blank: int, window: int,
+                       preamble_free: bool = True, from_last_frame: bool = False):
+        """CTC segmentation of the recordings enc_act (B,T,d) (compute dtype, on the device) against their ground-truth
+        columns, by `em_ctc_log_probs_t` -> `em_ctc_segment` (include/espnet_amd.h states the band, the recursion and
+        the tie rule).  Returns (first_frame (B,Cmax) i32, frame_col (B,T) i32, frame_lp (B,T) f32, t_end (B,) i32,
+        total (B,) f32, status (B,) i32) as device tensors, no host sync.
+
+        olens / clens: per-recording lengths, gt (B, Cmax) columns (column 0 is the start symbol, never read).  Given as
+        HOST data they are checked first (`check_segmentable`: ValueError before any launch) and copied over; given as
+        int32 DEVICE tensors they are taken as they are."""
+        L.require_gpu(enc_act, "enc_act")
+        B, T, d = enc_act.shape
+        dev, V = enc_act.device, self.odim
+        olens_d, gt_d, clens_d, Cmax = self._segment_inputs(olens, gt, clens, V, T, dev)
+        if int(gt_d.shape[0]) != B:
+            raise ValueError(f"gt must have {B} rows")
+        return self.segment_log_probs_t(self.log_probs_t_device(enc_act), B * T, olens_d, gt_d, Cmax, clens_d, B, T, blank,
+                                        window, preamble_free=preamble_free, from_last_frame=from_last_frame)
+
+    def log_probs_t_device(self, enc_act: torch.Tensor) -> torch.Tensor:
+        """enc_act (B,T,d) in the compute dtype -> the transposed log-posteriors lpT (V, B*T) f32 the trellis kernels
+        read (`em_ctc_log_probs_t`: frame-contiguous rows); only enqueues work."""
+        B, T, d = enc_act.shape
+        p = self.packed(enc_act.device)
+        lpT = torch.empty(self.odim, B * T, dtype=torch.float32, device=enc_act.device)
+        L.check(L.load().em_ctc_log_probs_t(self.em_dtype, L.ptr(enc_act), B, T, d, L.ptr(p.weight), L.ptr(p.bias),
+                                            self.odim, L.ptr(lpT), L.current_stream_ptr()), "em_ctc_log_probs_t")
+        return lpT
+
+    @staticmethod
+    def segment_log_probs_t(lpT, ldT, olens_d, gt_d, Cmax, clens_d, B, T, blank, window, preamble_free=True,
+                            from_last_frame=False, ws_bytes=None):
+        """`em_ctc_segment` on given transposed log-posteriors lpT [V][ldT] (device tensors throughout)."""
+        lib, dev = L.load(), lpT.device
+        window = int(window)
+        if window < 1 or window > int(lib.em_ctc_segment_max_window()):
+            raise ValueError(f"window must lie in [1, {int(lib.em_ctc_segment_max_window())}], not {window}")
+        flags = (L.EM_SEG_PREAMBLE_FREE if preamble_free else 0) | (L.EM_SEG_FROM_LAST_FRAME if from_last_frame else 0)
+        if ws_bytes is None:
+            ws_bytes = int(lib.em_ctc_segment_workspace_bytes(B, T, Cmax, window))
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
+        first_frame = torch.empty(B, Cmax, dtype=torch.int32, device=dev)
+        frame_col = torch.empty(B, T, dtype=torch.int32, device=dev)
+        frame_lp = torch.empty(B, T, dtype=torch.float32, device=dev)
+        t_end = torch.empty(B, dtype=torch.int32, device=dev)
+        total = torch.empty(B, dtype=torch.float32, device=dev)
+        status = torch.empty(B, dtype=torch.int32, device=dev)
+        L.check(lib.em_ctc_segment(L.ptr(lpT), ldT, L.ptr(olens_d), L.ptr(gt_d), Cmax, L.ptr(clens_d), B, T, blank, window,
+                                   flags, L.ptr(first_frame), L.ptr(frame_col), L.ptr(frame_lp), L.ptr(t_end), L.ptr(total),
+                                   L.ptr(status), L.ptr(ws), ws_bytes, L.current_stream_ptr()), "em_ctc_segment")
+        return first_frame, frame_col, frame_lp, t_end, total, status
+
     # ------------------------------------------------------------------ likelihood of given transcripts (csrc/ctc_nll.hip)
     def nll_device(self, enc_act: torch.Tensor, olens, targets, ylens, blank: int, mem_of=None) -> torch.Tensor:
         """-log p_ctc(targets[n] | utterance mem_of[n]) for N candidate transcripts, (N,) f32 on the device, by

@@ -19,6 +19,8 @@ EM_F32, EM_BF16 = 0, 1
  EM_EPI_STORE_F32, _EM_EPI_UNUSED_7, _EM_EPI_UNUSED_8, EM_EPI_ARGMAX_PART, EM_EPI_GELU, EM_EPI_QK_HEADS,
  EM_EPI_VT_HEADS) = range(13)
 EM_A_PLAIN, EM_A_CONV2 = 0, 1
+EM_SEG_PREAMBLE_FREE, EM_SEG_FROM_LAST_FRAME = 1, 2  # em_ctc_segment: flags
+EM_SEG_NO_ROUTE, EM_SEG_CLIPPED = 1, 2  # ... status bits
 
 EM_DW_SWISH, EM_DW_LINEAR, EM_DW_GATE, EM_DW_SELFRES = range(4)
 EM_ENC_ISOLATE_UTTS = 1  # em_conformer_encode flags (include/espnet_amd.h)
@@ -394,6 +396,10 @@ _SIGNATURES = {
                                       _sz, _vp]),
     "em_ctc_forced_align_workspace_bytes": (_sz, [_i32, _i32, _i32]),
     "em_ctc_forced_align_max_tokens": (_i32, []),
+    "em_ctc_segment": (C.c_int, [_vp, _i32, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp,
+                                 _vp, _vp, _sz, _vp]),
+    "em_ctc_segment_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32]),
+    "em_ctc_segment_max_window": (_i32, []),
     "em_ctc_seq_nll": (C.c_int, [_vp, _i32, _vp, _i32, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _vp, _vp]),
     "em_ngram_score": (C.c_int, [C.POINTER(EmNgramModel), _i32, _vp, _vp, _vp, _vp, _i32, _vp, _vp]),
     "em_arpa_count": (C.c_int, [C.c_char_p, _vp, _vp, _vp]),

@@ -27,6 +27,7 @@
  *       em_cb_encode_blocks[_batch], em_cbt_encode_blocks[_batch]: the blocks in place and next_ctx whole;
  *       em_dec_seq_nll, em_lm_seq_nll, em_lm_head_nll: nll whole (exactly 0.0 where nothing is scored);
  *       em_ctc_forced_align: every output whole (labels -1, spans -1, scores 0 behind the lengths);
+ *       em_ctc_segment: every output whole (columns -1, frames -1, scores 0 off the path and behind the lengths);
  *       em_transducer_greedy: ylens and score whole, tokens[b][< ylens[b]], the traces [b][< olens[b]];
  *       em_transducer_lattice_logp: the nodes t < xlens[mem_of[n]], u <= ylens[n] (the label of u == ylens[n]: -inf);
  *       em_transducer_seq_align: every output whole (frames -1, log-probabilities 0 behind the lengths).
@@ -1193,6 +1194,53 @@ int em_ctc_forced_align(const float* lpT, int32_t ldT, const int32_t* xlens, con
                         void* stream);
 size_t em_ctc_forced_align_workspace_bytes(int32_t B, int32_t T, int32_t Lmax);
 int32_t em_ctc_forced_align_max_tokens(void);
+
+/* ---- CTC segmentation (csrc/ctc_segment.hip): where the utterances of a long text lie in a long recording - the trellis
+ *      of the ctc_segmentation package as espnet2/bin/asr_align.py (class CTCSegmentation) drives it, for a ragged batch
+ *      of recordings in one launch.  The package was not at hand when this was written: THIS text is the contract; it
+ *      deviates knowingly in the band's shape (the package bands over time per column), in the tie rule, and the host
+ *      layer in the inclusive last window of the confidence.
+ *      lpT [V][ldT] f32 = em_ctc_log_probs_t's output (ldT >= B*T; recording b's frames are the columns b*T .. b*T +
+ *      xlens[b] - 1, the layout em_ctc_forced_align takes), gt [B][Cmax] the ground-truth COLUMNS, xlens / clens [B], all
+ *      on the device.
+ *   Per recording, T_b = xlens[b], C_b = clens[b] >= 2, lp[f][v] = lpT[v][b*T + f]:
+ *      column 0 is the start symbol (gt[b][0] is never read); columns 1 .. C_b - 1 hold ids in [0, V) (the caller checks
+ *      that), the blank id among them: utterance separators are blank columns.  There are no separate blank states: C
+ *      columns, not 2L + 1.
+ *      Band: 1 <= W <= em_ctc_segment_max_window() (8 192), W_b = min(W, C_b); row t computes the columns
+ *      lo(t) <= c < lo(t) + W_b only, all others are -inf,
+ *        lo(t) = min(max(floor(t * C_b / T_b) - floor(W_b / 2), 0), C_b - W_b)      (64-bit product):
+ *      centred on the diagonal, slack at both ends.
+ *      k[t][c], t = 0 .. T_b, plain f32 adds and compares: k[0][0] = 0, k[0][c > 0] = -inf; row t >= 1 reads frame
+ *      f = t - 1;
+ *        c = 0:  k[t][0] = 0 under EM_SEG_PREAMBLE_FREE, else k[t-1][0] + lp[f][blank];
+ *        c >= 1, e = lp[f][gt[c]]:  stay = k[t-1][c] + max(lp[f][blank], e),  switch = k[t-1][c-1] + e,
+ *                k[t][c] = switch and the move bit is 1 if and only if switch > stay (strictly), else k[t][c] = stay.
+ *      End: t_end = T_b under EM_SEG_FROM_LAST_FRAME, else the LOWEST t in [1, T_b] that maximises k[t][C_b - 1];
+ *      total = k[t_end][C_b - 1].
+ *      Back-trace from (t_end, C_b - 1) while t > 0 and c > 0, f = t - 1: frame_col[f] = c; move bit set: frame_lp[f] =
+ *      lp[f][gt[c]], first_frame[c] = f, c -= 1; else frame_lp[f] = max(lp[f][blank], lp[f][gt[c]]); then t -= 1.
+ *      first_frame[0] = 0.
+ *   Outputs: first_frame [B][Cmax] (-1 for c >= C_b); frame_col, frame_lp [B][T]: -1 / 0 for the frames the path does not
+ *      visit (the preamble, the frames at or after t_end, the frames at or beyond T_b); t_end, total, status [B].
+ *      status bit 0 (EM_SEG_NO_ROUTE): total = -inf (for example C_b - 1 > T_b; also T_b == 0 or C_b < 2) - then total =
+ *      -inf, t_end = 0, first_frame = -1, frame_col = -1, frame_lp = 0 throughout.
+ *      status bit 1 (EM_SEG_CLIPPED): a cell (t, c) of the path sits on a band edge that is not a table edge, c == lo(t)
+ *      with lo(t) > 0, or c == lo(t) + W_b - 1 with lo(t) + W_b < C_b: a wider W may give another path.
+ *   Exact ties are systematic (a blank separator column and the blank stay of the token in front of it give bit-equal
+ *   sums): the strict > and the lowest t are part of the contract.
+ *   W above the cap: EM_ERR_UNSUPPORTED.  ws: em_ctc_segment_workspace_bytes(B, T, Cmax, W) bytes of device memory (0
+ *   when the back-pointers fit LDS: ws may then be NULL); a smaller one: EM_ERR_WORKSPACE.  Enqueue only.             */
+#define EM_SEG_PREAMBLE_FREE 1
+#define EM_SEG_FROM_LAST_FRAME 2
+#define EM_SEG_NO_ROUTE 1
+#define EM_SEG_CLIPPED 2
+int em_ctc_segment(const float* lpT, int32_t ldT, const int32_t* xlens, const int32_t* gt, int32_t Cmax,
+                   const int32_t* clens, int32_t B, int32_t T, int32_t blank, int32_t W, int32_t flags,
+                   int32_t* first_frame, int32_t* frame_col, float* frame_lp, int32_t* t_end, float* total,
+                   int32_t* status, void* ws, size_t ws_bytes, void* stream);
+size_t em_ctc_segment_workspace_bytes(int32_t B, int32_t T, int32_t Cmax, int32_t W);
+int32_t em_ctc_segment_max_window(void);
 
 /* ---- CTC likelihood of given transcripts (csrc/ctc_nll.hip): the forward (sum-product) trellis, the per-utterance value
  *      of CTC.forward with reduce=False under the builtin ctc_loss (espnet2/asr/ctc.py; torch.nn.functional.ctc_loss,
