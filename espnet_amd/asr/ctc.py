@@ -156,16 +156,9 @@ class CTC(PackedModule):
         int32 DEVICE tensors they are taken as they are - for ids the device produced itself (the greedy CTC tokens),
         which are valid by construction."""
         L.require_gpu(enc_act, "enc_act")
-        B, T, d = enc_act.shape
-        dev, V = enc_act.device, self.odim
+        B, T, _ = enc_act.shape
         olens_d, tg_d, ylens_d, _, _, Lmax = self._trellis_inputs(enc_act, olens, targets, ylens, blank, None, align=True)
-        lib, st = L.load(), L.current_stream_ptr()
-        ws_bytes = int(lib.em_ctc_forced_align_workspace_bytes(B, T, Lmax))
-        p = self.packed(dev)
-        lpT = torch.empty(V, B * T, dtype=torch.float32, device=dev)
-        L.check(lib.em_ctc_log_probs_t(self.em_dtype, L.ptr(enc_act), B, T, d, L.ptr(p.weight), L.ptr(p.bias), V,
-                                       L.ptr(lpT), st), "em_ctc_log_probs_t")
-        return self.align_log_probs_t(lpT, B * T, olens_d, tg_d, Lmax, ylens_d, B, T, blank, ws_bytes=ws_bytes)
+        return self.align_log_probs_t(self.log_probs_t_device(enc_act), B * T, olens_d, tg_d, Lmax, ylens_d, B, T, blank)
 
     @staticmethod
     def align_log_probs_t(lpT, ldT, olens_d, tg_d, Lmax, ylens_d, B, T, blank, ws_bytes=None):
@@ -304,18 +297,13 @@ class CTC(PackedModule):
         DEVICE tensors are taken as they are.  A transcript its utterance has too few frames for is no error here: its
         value is +inf, as the reference's ctc_loss has it."""
         L.require_gpu(enc_act, "enc_act")
-        Bm, T, d = enc_act.shape
-        dev, V = enc_act.device, self.odim
+        Bm, T, _ = enc_act.shape
         olens_d, tg_d, ylens_d, mo_d, N, Lmax = self._trellis_inputs(enc_act, olens, targets, ylens, blank, mem_of, align=False)
         if N == 0:
-            return torch.empty(0, dtype=torch.float32, device=dev)
+            return torch.empty(0, dtype=torch.float32, device=enc_act.device)
         if mo_d is None and N != Bm:
             raise ValueError(f"{N} transcripts for {Bm} utterances need mem_of")
-        p = self.packed(dev)
-        lpT = torch.empty(V, Bm * T, dtype=torch.float32, device=dev)
-        L.check(L.load().em_ctc_log_probs_t(self.em_dtype, L.ptr(enc_act), Bm, T, d, L.ptr(p.weight), L.ptr(p.bias), V,
-                                            L.ptr(lpT), L.current_stream_ptr()), "em_ctc_log_probs_t")
-        return self.nll_log_probs_t(lpT, Bm * T, olens_d, Bm, T, tg_d, Lmax, ylens_d, mo_d, N, blank)
+        return self.nll_log_probs_t(self.log_probs_t_device(enc_act), Bm * T, olens_d, Bm, T, tg_d, Lmax, ylens_d, mo_d, N, blank)
 
     @staticmethod
     def nll_log_probs_t(lpT, ldT, olens_d, Bm, T, tg_d, Lmax, ylens_d, mem_of_d, N, blank) -> torch.Tensor:

@@ -252,13 +252,53 @@ class Speech2Text:
                 raise ValueError(f"token id {v} ({bad[v]}) cannot be aligned")
         return ids
 
+    def _batch_of_one(self, batch, speech, text):
+        """`batch`, one of the batch aligners, for one utterance."""
+        speech = (torch.tensor(speech) if isinstance(speech, np.ndarray) else speech).unsqueeze(0).to(torch.float32)
+        return batch(speech, [speech.size(1)], None if text is None else [text])[0]
+
+    def _token_times(self, speech, speech_lengths, texts, check_ids, hypothesis, min_width, run, row_result):
+        """The shared driver of the batch aligners behind their model-kind refusal: texts -> ids (check_ids(ids): what the
+        aligner refuses beyond `_target_ids`), the encode, then run(st, ids, tokens, tlens) -> the aligner's output columns,
+        (B, w) device tensors.  texts=None: ids is None and hypothesis(st) gives the own hypothesis as device (tokens (B, T),
+        tlens (B,), no_sync); token rows wider than no_sync are cut to the longest hypothesis, at least min_width.  One D2H
+        copy brings the columns and, behind them, `tlens | tokens`; row_result(cols, y, names, T_b, spf) formats
+        utterance b from its row of every column, its ids and their token names, its encoder frames and
+        `seconds_per_frame`."""
+        B = int(speech.shape[0])
+        ids = tokens = tlens = None
+        if texts is not None:
+            if len(texts) != B:
+                raise ValueError(f"{len(texts)} transcripts for {B} utterances")
+            ids = [self._target_ids(t) for t in texts]
+            check_ids(ids)
+        speech = speech.to(self.device, torch.float32, non_blocking=True)
+        st = self.asr_model.encode_device(speech, [int(n) for n in speech_lengths], isolate=True)
+        if ids is None:
+            tokens, tlens, no_sync = hypothesis(st)
+            if tokens.shape[1] > no_sync:
+                # the row stride is the kernels' Lmax - the waves per utterance and the back-pointer workspace of the CTC
+                # trellis, the steps of the prediction network and the threads of the lattice recursion up to its cap:
+                # one small sync for the longest hypothesis
+                tokens = tokens[:, : max(int(tlens.max()), min_width)].contiguous()
+        cols = list(run(st, ids, tokens, tlens))
+        n_out = len(cols)
+        if tokens is not None:
+            cols += [tlens[:, None], tokens]
+        # the one D2H copy: everything as f32 columns of one matrix (frame counts and ids are far below 2**24)
+        host = torch.cat([c.to(torch.float32) for c in cols], dim=1).cpu().numpy()
+        parts = np.split(host, np.cumsum([int(c.shape[1]) for c in cols])[:-1], axis=1)
+        spf = self.seconds_per_frame
+        results = []
+        for b in range(B):
+            y = ids[b] if ids is not None else parts[-1][b, : int(parts[-2][b, 0])].astype(np.int64).tolist()
+            results.append(row_result([c[b] for c in parts[:n_out]], y, self.converter.ids2tokens(y), st.olens[b], spf))
+        return results
+
     @torch.no_grad()
     def align(self, speech: Union[torch.Tensor, np.ndarray], text=None):
         """Token timestamps of one utterance: `batch_align` for a batch of one."""
-        if isinstance(speech, np.ndarray):
-            speech = torch.tensor(speech)
-        speech = speech.unsqueeze(0).to(torch.float32)
-        return self.batch_align(speech, [speech.size(1)], None if text is None else [text])[0]
+        return self._batch_of_one(self.batch_align, speech, text)
 
     @torch.no_grad()
     def batch_align(self, speech: torch.Tensor, speech_lengths: Sequence[int], texts=None):
@@ -275,56 +315,30 @@ class Speech2Text:
         m = self.asr_model
         if m.ctc is None:
             raise ValueError("forced alignment needs a CTC head (the model has ctc_weight == 0)")
-        B = int(speech.shape[0])
-        ids = None
-        if texts is not None:
-            if len(texts) != B:
-                raise ValueError(f"{len(texts)} transcripts for {B} utterances")
-            ids = [self._target_ids(t) for t in texts]
-        speech = speech.to(self.device, torch.float32, non_blocking=True)
-        st = m.encode_device(speech, [int(n) for n in speech_lengths], isolate=True)
-        if ids is None:
-            _, tokens, tlens = m.greedy_ctc_device(st)
-            if tokens.shape[1] > self.align_no_sync_frames:
-                # the row stride is the kernel's Lmax, and beyond one wave's 255 tokens it sets the waves per utterance
-                # and the back-pointer workspace: one small sync for the longest hypothesis
-                tokens = tokens[:, : max(int(tlens.max()), 1)].contiguous()
-            outs = m.ctc.forced_align_device(st.enc_act, st.olens_dev, tokens, tlens, m.blank_id)
-        else:
-            tokens = tlens = None
-            outs = m.ctc.forced_align_device(st.enc_act, st.olens, ids, [len(y) for y in ids], m.blank_id)
-        align, _, tok_start, tok_end, tok_lp, total = outs
-        T, Lm = int(align.shape[1]), int(tok_start.shape[1])
-        # the one D2H copy: everything as f32 columns of one matrix (frame counts and ids are far below 2**24)
-        cols = [align, tok_start, tok_end, tok_lp, total[:, None]]
-        if tokens is not None:
-            cols += [tlens[:, None], tokens]
-        off_tok = T + 3 * Lm + 2  # column of the first hypothesis token (behind `total` and the token count)
-        host = torch.cat([c.to(torch.float32) for c in cols], dim=1).cpu().numpy()
-        spf = self.seconds_per_frame
-        results = []
-        for b in range(B):
-            row = host[b]
+
+        def hypothesis(st):
+            return (*m.greedy_ctc_device(st)[1:], self.align_no_sync_frames)
+
+        def run(st, ids, tokens, tlens):
             if ids is None:
-                n = int(row[off_tok - 1])
-                y = row[off_tok : off_tok + n].astype(np.int64).tolist()
+                outs = m.ctc.forced_align_device(st.enc_act, st.olens_dev, tokens, tlens, m.blank_id)
             else:
-                y = ids[b]
-            names = self.converter.ids2tokens(y)
-            s, e, lp = row[T : T + Lm], row[T + Lm : T + 2 * Lm], row[T + 2 * Lm : T + 3 * Lm]
+                outs = m.ctc.forced_align_device(st.enc_act, st.olens, ids, [len(y) for y in ids], m.blank_id)
+            align, _, tok_start, tok_end, tok_lp, total = outs
+            return align, tok_start, tok_end, tok_lp, total[:, None]
+
+        def row_result(cols, y, names, Tb, spf):
+            align, s, e, lp, total = cols
             toks = [(names[i], int(y[i]), float(s[i]) * spf, float(e[i]) * spf, float(lp[i])) for i in range(len(y))]
-            results.append(dict(tokens=toks, frame_labels=torch.from_numpy(row[: st.olens[b]].astype(np.int64)),
-                                total=float(row[T + 3 * Lm])))
-        return results
+            return dict(tokens=toks, frame_labels=torch.from_numpy(align[:Tb].astype(np.int64)), total=float(total[0]))
+
+        return self._token_times(speech, speech_lengths, texts, lambda ids: None, hypothesis, 1, run, row_result)
 
     # ------------------------------------------------------------------ transducer forced alignment: token timestamps
     @torch.no_grad()
     def transducer_align(self, speech: Union[torch.Tensor, np.ndarray], text=None):
         """Token timestamps of one utterance under a transducer model: `batch_transducer_align` for a batch of one."""
-        if isinstance(speech, np.ndarray):
-            speech = torch.tensor(speech)
-        speech = speech.unsqueeze(0).to(torch.float32)
-        return self.batch_transducer_align(speech, [speech.size(1)], None if text is None else [text])[0]
+        return self._batch_of_one(self.batch_transducer_align, speech, text)
 
     def _greedy_walk_device(self, st):
         """The greedy walk's (tokens (B, T) int32, ylens (B,) int32) of an encoded batch, left on the device."""
@@ -363,56 +377,36 @@ class Speech2Text:
         if not getattr(m, "use_transducer_decoder", False):
             raise RuntimeError("batch_transducer_align: the model has no joint network (decoder: transducer); the CTC head's "
                                "forced alignment is batch_align")
-        B = int(speech.shape[0])
-        ids = None
-        if texts is not None:
-            if len(texts) != B:
-                raise ValueError(f"{len(texts)} transcripts for {B} utterances")
-            ids = [self._target_ids(t) for t in texts]
+
+        def check_ids(ids):
             V = getattr(m, "vocab_size", None)
             if V is not None and any(v < 0 or v >= V for y in ids for v in y):
                 raise ValueError(f"token ids must lie in [0, {V})")
-        speech = speech.to(self.device, torch.float32, non_blocking=True)
-        st = m.encode_device(speech, [int(n) for n in speech_lengths], isolate=True)
-        if ids is None:
+
+        def hypothesis(st):
             from espnet_amd import lib as L
 
-            tokens, tlens = self._greedy_walk_device(st)
-            if tokens.shape[1] > min(self.align_no_sync_frames, int(L.load().em_transducer_seq_nll_max_tokens())):
-                # the row stride is the lattice's Lmax: the prediction network runs Lmax + 1 steps and the recursion has a
-                # thread per column up to its cap - one small sync for the longest hypothesis
-                tokens = tokens[:, : int(tlens.max())].contiguous()
-            outs = m._transducer_align_rows(st.enc_act, st.olens_dev, tokens, tlens, checked=True)
-        else:
-            tokens = tlens = None
-            ys = torch.zeros(B, max((len(y) for y in ids), default=0), dtype=torch.long)
-            for b, y in enumerate(ids):
-                ys[b, : len(y)] = torch.tensor(y, dtype=torch.long)
-            outs = m.transducer_align(st.enc_act, torch.tensor(st.olens), ys, torch.tensor([len(y) for y in ids]))
-        tok_frame, tok_logp, frame_u, total = outs
-        T, Lm = int(frame_u.shape[1]), int(tok_frame.shape[1])
-        # the one D2H copy: everything as f32 columns of one matrix (frame counts and ids are far below 2**24)
-        cols = [frame_u, tok_frame, tok_logp, total[:, None]]
-        if tokens is not None:
-            cols += [tlens[:, None], tokens]
-        off_tok = T + 2 * Lm + 2  # column of the first hypothesis token (behind `total` and the token count)
-        host = torch.cat([c.to(torch.float32) for c in cols], dim=1).cpu().numpy()
-        spf = self.seconds_per_frame
-        results = []
-        for b in range(B):
-            row = host[b]
+            return (*self._greedy_walk_device(st), min(self.align_no_sync_frames, int(L.load().em_transducer_seq_nll_max_tokens())))
+
+        def run(st, ids, tokens, tlens):
             if ids is None:
-                n = int(row[off_tok - 1])
-                y = row[off_tok : off_tok + n].astype(np.int64).tolist()
+                outs = m._transducer_align_rows(st.enc_act, st.olens_dev, tokens, tlens, checked=True)
             else:
-                y = ids[b]
-            names = self.converter.ids2tokens(y)
-            fr, lp = row[T : T + Lm], row[T + Lm : T + 2 * Lm]
+                ys = torch.zeros(len(ids), max((len(y) for y in ids), default=0), dtype=torch.long)
+                for b, y in enumerate(ids):
+                    ys[b, : len(y)] = torch.tensor(y, dtype=torch.long)
+                outs = m.transducer_align(st.enc_act, torch.tensor(st.olens), ys, torch.tensor([len(y) for y in ids]))
+            tok_frame, tok_logp, frame_u, total = outs
+            return frame_u, tok_frame, tok_logp, total[:, None]
+
+        def row_result(cols, y, names, Tb, spf):
+            frame_u, fr, lp, total = cols
             toks = [(names[i], int(y[i]), float(fr[i]) * spf, (float(fr[i]) + 1.0) * spf, float(lp[i])) if fr[i] >= 0 else
                     (names[i], int(y[i]), -1.0, -1.0, 0.0) for i in range(len(y))]  # (frame -1: no path)
-            results.append(dict(tokens=toks, token_int=[int(v) for v in y],
-                                frame_u=torch.from_numpy(row[: st.olens[b]].astype(np.int64)), total=float(row[T + 2 * Lm])))
-        return results
+            return dict(tokens=toks, token_int=[int(v) for v in y], frame_u=torch.from_numpy(frame_u[:Tb].astype(np.int64)),
+                        total=float(total[0]))
+
+        return self._token_times(speech, speech_lengths, texts, check_ids, hypothesis, 0, run, row_result)
 
     # ------------------------------------------------------------------ attention-decoder likelihood of given transcripts
     nll_rows_per_call = 100  # candidates per enqueue (ESPnetASRModel.batchify_nll's default slice)

@@ -3,10 +3,7 @@
 // (contract: include/espnet_amd.h, "transducer forced alignment").  It is the Viterbi twin of seq_nll_kernel
 // (csrc/transducer_nll.hip), as csrc/ctc_align.hip is of the CTC forward recursion.
 //
-//   seq_align_kernel   a workgroup per candidate, thread u owns column u of the lattice and the anti-diagonals d = t + u
-//                      pass in sequence: cell (d - u, u) needs its own value and thread u - 1's of diagonal d - 1, which
-//                      cross through a double-buffered LDS row with ONE barrier per diagonal; the two log-probabilities
-//                      of diagonal d + 1 are loaded before the chain of diagonal d (seq_nll_kernel's scheme).
+//   seq_align_kernel   a workgroup per candidate: csrc/rnnt_lattice.h's walk with the Viterbi cell, back-trace, outputs.
 //
 // Back-pointers are one bit per node, set when the label move (from (t, u-1)) is strictly better than the blank move
 // (from (t-1, u)).  The store is u-major, bp[n][u][t / 32]: thread u meets the frames of its column in order, one per
@@ -22,11 +19,9 @@
 #include <math.h>
 
 #include "em_common.h"
+#include "rnnt_lattice.h"
 
 namespace {
-
-constexpr int SA_MAX_L = 1023;           // one thread per lattice column u <= Lmax: 1 024 threads
-constexpr long SA_MAX_NODES = 1L << 28;  // N * T * (Lmax + 1), the bound of em_transducer_lattice_logp's lattices
 
 struct AlignArgs {
   const float* lat;
@@ -37,16 +32,30 @@ struct AlignArgs {
   uint32_t* bp;  // [N][Lmax + 1][(T + 31) / 32] back-pointer words
 };
 
+struct ViterbiCell {  // the max-product cell of rnnt_lattice::walk, with the back-pointer store described above
+  uint32_t* col;  // bp[n][u]
+  int last;       // Tb - 1
+  uint32_t word;  // the bits of the frames 32 * (t / 32) .. t
+  __device__ __forceinline__ float node(int t, float stay, float emit) {
+    const bool label = emit > stay;  // the tie rule: equal values keep the blank move
+    word |= (uint32_t)label << (t & 31);
+    if ((t & 31) == 31 || t == last) {
+      col[t >> 5] = word;
+      word = 0;
+    }
+    return label ? emit : stay;
+  }
+};
+
 __global__ __launch_bounds__(1024) void seq_align_kernel(const AlignArgs a) {
-  __shared__ float row[2][SA_MAX_L + 1];
-  __shared__ int32_t tf[SA_MAX_L + 1];  // the frame of token u, found by the back-trace
+  __shared__ float row[2][rnnt_lattice::MAX_L + 1];
+  __shared__ int32_t tf[rnnt_lattice::MAX_L + 1];  // the frame of token u, found by the back-trace
   __shared__ float s_total;
   __shared__ int s_ok;
   const int n = blockIdx.x, u = threadIdx.x, NT = blockDim.x;
   const int T = a.T, Lmax = a.Lmax;
-  const int m = a.mem_of ? min(max(a.mem_of[n], 0), a.Bm - 1) : n;
-  const int Tb = min(max(a.xlens[m], 0), T);
-  const int U = min(max(a.ylens[n], 0), Lmax);
+  const rnnt_lattice::Cand cand = rnnt_lattice::clamp(a.xlens, a.ylens, a.mem_of, a.Bm, T, Lmax, n);
+  const int Tb = cand.Tb, U = cand.U;
   int32_t* tok_frame = a.tok_frame + (size_t)n * Lmax;
   float* tok_logp = a.tok_logp + (size_t)n * Lmax;
   int32_t* frame_u = a.frame_u + (size_t)n * T;
@@ -67,37 +76,8 @@ __global__ __launch_bounds__(1024) void seq_align_kernel(const AlignArgs a) {
   const float* base = a.lat + (size_t)n * T * ld;
   const int W = (T + 31) >> 5;
   uint32_t* bpn = a.bp + (size_t)n * (Lmax + 1) * W;
-  uint32_t* col = bpn + (size_t)u * W;
-  const bool mine = u <= U;
-  // the terms that cell (t, u) adds: b[t-1][u] (t >= 1) and e[t][u-1] (u >= 1); a missing neighbour is -inf
-  auto load_b = [&](int t) { return mine && t >= 1 && t < Tb ? base[(size_t)(t - 1) * ld + 2 * u] : -INFINITY; };
-  auto load_e = [&](int t) { return mine && u >= 1 && t >= 0 && t < Tb ? base[(size_t)t * ld + 2 * (u - 1) + 1] : -INFINITY; };
-  float v = -INFINITY;  // v[d - 1 - u][u] while diagonal d runs
-  uint32_t word = 0;    // the back-pointer bits of the frames 32 * (t / 32) .. t of this column
-  float nb = load_b(0 - u), ne = load_e(0 - u);
-  const int D = Tb + U;  // diagonals 0 .. D - 1
-  for (int d = 0; d < D; ++d) {
-    const int t = d - u;
-    const float b = nb, e = ne;
-    nb = load_b(t + 1);  // diagonal d + 1, in flight during this diagonal's chain
-    ne = load_e(t + 1);
-    const float left = u >= 1 ? row[(d + 1) & 1][u - 1] : -INFINITY;  // v[t][u-1], written on diagonal d - 1
-    const bool on = mine && t >= 0 && t < Tb;
-    if (on) {
-      const float stay = v + b, emit = left + e;
-      const bool label = emit > stay;  // the tie rule: equal values keep the blank move
-      v = d == 0 ? 0.f : (label ? emit : stay);
-      word |= (uint32_t)label << (t & 31);
-      if ((t & 31) == 31 || t == Tb - 1) {
-        col[t >> 5] = word;
-        word = 0;
-      }
-    }
-    row[d & 1][u] = on ? v : -INFINITY;
-    __syncthreads();
-  }
-  // thread U holds v[Tb-1][U] after the last diagonal
-  if (u == U) s_total = v + base[(size_t)(Tb - 1) * ld + 2 * U];
+  const float v = rnnt_lattice::walk(base, Lmax, Tb, U, row, ViterbiCell{bpn + (size_t)u * W, Tb - 1, 0});
+  if (u == U) s_total = v + base[(size_t)(Tb - 1) * ld + 2 * U];  // the closing blank
   __syncthreads();  // (and the back-pointer words of every column are visible to the workgroup)
   const float tot = s_total;
   if (!(tot > -INFINITY)) {  // (workgroup-uniform) no path of finite value
@@ -144,15 +124,10 @@ __global__ __launch_bounds__(1024) void seq_align_kernel(const AlignArgs a) {
   if (u == 0) a.total[n] = tot;
 }
 
-bool align_shape_ok(int N, int T, int Lmax) {
-  if (N <= 0 || T <= 0 || Lmax < 0 || Lmax > SA_MAX_L) return false;
-  return (long)N * T * (Lmax + 1) <= SA_MAX_NODES;
-}
-
 }  // namespace
 
 extern "C" size_t em_transducer_seq_align_workspace_bytes(int32_t N, int32_t T, int32_t Lmax) {
-  if (!align_shape_ok(N, T, Lmax)) return 0;
+  if (!rnnt_lattice::shape_ok(N, T, Lmax)) return 0;
   const size_t words = (size_t)N * (Lmax + 1) * ((T + 31) / 32);
   return (words * sizeof(uint32_t) + 255) & ~(size_t)255;
 }
@@ -164,13 +139,9 @@ extern "C" int em_transducer_seq_align(const float* lat, const int32_t* xlens, i
   if (!lat || !xlens || !ylens || !frame_u || !total || N <= 0 || Bm <= 0 || T <= 0 || Lmax < 0) return EM_ERR_BAD_ARG;
   if (Lmax > 0 && (!tok_frame || !tok_logp)) return EM_ERR_BAD_ARG;
   if (!mem_of && N > Bm) return EM_ERR_BAD_ARG;
-  if (!align_shape_ok(N, T, Lmax)) return EM_ERR_UNSUPPORTED;
+  if (!rnnt_lattice::shape_ok(N, T, Lmax)) return EM_ERR_UNSUPPORTED;
   if (!ws || ws_bytes < em_transducer_seq_align_workspace_bytes(N, T, Lmax)) return EM_ERR_WORKSPACE;
-  AlignArgs a;
-  a.lat = lat; a.xlens = xlens; a.ylens = ylens; a.mem_of = mem_of;
-  a.Bm = Bm; a.T = T; a.Lmax = Lmax;
-  a.tok_frame = tok_frame; a.frame_u = frame_u; a.tok_logp = tok_logp; a.total = total;
-  a.bp = (uint32_t*)ws;
+  const AlignArgs a{lat, xlens, ylens, mem_of, Bm, T, Lmax, tok_frame, frame_u, tok_logp, total, (uint32_t*)ws};
   hipLaunchKernelGGL(seq_align_kernel, dim3(N), dim3(64 * em_cdiv(Lmax + 1, 64)), 0, (hipStream_t)stream, a);
   EM_CHECK_LAUNCH();
   return EM_OK;

@@ -16,11 +16,7 @@
 //                         exp per logit; the 16 lanes of a row group, then the eight waves merge once at the end and the
 //                         two log-probabilities of the node are stored.  No partial records in memory, no merge launch;
 //   lattice_f32_kernel    the parity path: a workgroup per node, z in LDS as f32, thread i walks the columns i, i + 256, ..;
-//   seq_nll_kernel        a workgroup per candidate, thread u owns column u of the lattice and the anti-diagonals
-//                         d = t + u pass in sequence: cell (d - u, u) needs its own value and thread u - 1's of diagonal
-//                         d - 1, which cross through a double-buffered LDS row with ONE barrier per diagonal
-//                         (csrc/ctc_align.hip's scheme); the two log-probabilities of diagonal d + 1 are loaded before
-//                         the chain of diagonal d.
+//   seq_nll_kernel        a workgroup per candidate: the walk of csrc/rnnt_lattice.h with the sum cell, the closing blank.
 // A node's values depend on its own two projection rows and the weights only: the operations on a row are the same
 // whichever tile, row slot and companions it has (an MFMA row sees its own A row only; the merges run in a fixed order
 // over columns), so they are bit for bit the same for any N, Lmax and mem_of.
@@ -29,6 +25,7 @@
 
 #include "em_common.h"
 #include "enc_host.h"
+#include "rnnt_lattice.h"
 
 namespace {
 
@@ -36,8 +33,6 @@ constexpr int LT_ROWS = 64;      // rows of a workgroup: four 16-row MFMA tiles
 constexpr int LT_WAVES = 8;      // waves of a workgroup: the 16-column tiles of the vocabulary are dealt round robin
 constexpr int LT_JP_MAX = 1024;  // bf16: 64 rows of jp + 8 bf16 stay inside the 160 KiB of LDS
 constexpr int LT_JP_MAX_F32 = 8192;
-constexpr long LT_MAX_NODES = 1L << 28;  // N * T * (Lmax + 1): node numbers stay inside 31 bits, lat inside 2 GiB
-constexpr int SN_MAX_L = 1023;           // one thread per lattice column u <= Lmax: 1 024 threads
 
 struct LatArgs {
   const float *enc_proj, *dec_proj, *out_b;
@@ -57,10 +52,7 @@ __global__ __launch_bounds__(1024) void lattice_rows_kernel(const int32_t* __res
   const int per = (N + 1023) / 1024;
   const int n0 = min(tid * per, N), n1 = min(n0 + per, N);
   int sum = 0;
-  for (int n = n0; n < n1; ++n) {
-    const int m = mem_of ? min(max(mem_of[n], 0), Bm - 1) : n;
-    sum += min(max(xlens[m], 0), T) * (min(max(ylens[n], 0), Lmax) + 1);
-  }
+  for (int n = n0; n < n1; ++n) sum += rnnt_lattice::clamp(xlens, ylens, mem_of, Bm, T, Lmax, n).nodes();
   run[tid] = sum;
   __syncthreads();
   if (tid == 0) {
@@ -76,8 +68,7 @@ __global__ __launch_bounds__(1024) void lattice_rows_kernel(const int32_t* __res
   int acc = run[tid];
   for (int n = n0; n < n1; ++n) {
     off[n] = acc;
-    const int m = mem_of ? min(max(mem_of[n], 0), Bm - 1) : n;
-    acc += min(max(xlens[m], 0), T) * (min(max(ylens[n], 0), Lmax) + 1);
+    acc += rnnt_lattice::clamp(xlens, ylens, mem_of, Bm, T, Lmax, n).nodes();
   }
 }
 
@@ -95,29 +86,30 @@ __device__ __forceinline__ Node find_node(const LatArgs& a, int g) {
     if (a.off[mid] <= g) lo = mid; else hi = mid - 1;
   }
   const int n = lo;
-  const int U = min(max(a.ylens[n], 0), a.Lmax);
+  const rnnt_lattice::Cand c = rnnt_lattice::clamp(a.xlens, a.ylens, a.mem_of, a.Bm, a.T, a.Lmax, n);
   const int local = g - a.off[n];
-  const int t = local / (U + 1), u = local - t * (U + 1);
-  const int m = a.mem_of ? min(max(a.mem_of[n], 0), a.Bm - 1) : n;
+  const int t = local / (c.U + 1), u = local - t * (c.U + 1);
   Node r;
-  r.enc_row = m * a.T + t;
+  r.enc_row = c.m * a.T + t;
   r.dec_row = u * a.N + n;
-  r.label = u < U ? a.targets[(size_t)n * a.Lmax + u] : -1;
+  r.label = u < c.U ? a.targets[(size_t)n * a.Lmax + u] : -1;
   r.lat_node = (n * a.T + t) * (a.Lmax + 1) + u;
   return r;
 }
 
 // A row's record over a set of columns: the maximum logit, the sum of exp(logit - maximum), the blank's logit and the
-// label's (-inf while their columns have not been met)
+// label's (-inf while their columns have not been met).  FAST: the bf16 path's __expf; the parity path keeps expf.
 struct Rec {
   float m, s, b, l;
 };
+template <bool FAST = true>
 __device__ __forceinline__ Rec rec_merge(Rec x, Rec y) {
   Rec r;
   r.m = fmaxf(x.m, y.m);
   r.b = fmaxf(x.b, y.b);
   r.l = fmaxf(x.l, y.l);
-  r.s = (x.m == -INFINITY ? 0.f : x.s * __expf(x.m - r.m)) + (y.m == -INFINITY ? 0.f : y.s * __expf(y.m - r.m));
+  const float ex = FAST ? __expf(x.m - r.m) : expf(x.m - r.m), ey = FAST ? __expf(y.m - r.m) : expf(y.m - r.m);
+  r.s = (x.m == -INFINITY ? 0.f : x.s * ex) + (y.m == -INFINITY ? 0.f : y.s * ey);
   return r;
 }
 __device__ __forceinline__ Rec rec_shfl_xor(Rec v, int o) {
@@ -307,15 +299,7 @@ __global__ __launch_bounds__(256) void lattice_f32_kernel(const LatArgs a) {
     r.m = mm;
   }
 #pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const Rec y = rec_shfl_xor(r, o);
-    Rec m;
-    m.m = fmaxf(r.m, y.m);
-    m.b = fmaxf(r.b, y.b);
-    m.l = fmaxf(r.l, y.l);
-    m.s = (r.m == -INFINITY ? 0.f : r.s * expf(r.m - m.m)) + (y.m == -INFINITY ? 0.f : y.s * expf(y.m - m.m));
-    r = m;
-  }
+  for (int o = 1; o < 64; o <<= 1) r = rec_merge<false>(r, rec_shfl_xor(r, o));
   if (lane == 0) {
     red[wave][0] = r.m;
     red[wave][1] = r.s;
@@ -344,38 +328,22 @@ struct SeqArgs {
   float* nll;
 };
 
+struct SumCell {  // the sum-product cell of rnnt_lattice::walk
+  __device__ __forceinline__ float node(int, float stay, float emit) { return logaddexp_(stay, emit); }
+};
+
 __global__ __launch_bounds__(1024) void seq_nll_kernel(const SeqArgs a) {
-  __shared__ float row[2][SN_MAX_L + 1];
+  __shared__ float row[2][rnnt_lattice::MAX_L + 1];
   const int n = blockIdx.x, u = threadIdx.x;
-  const int T = a.T, Lmax = a.Lmax;
-  const int m = a.mem_of ? min(max(a.mem_of[n], 0), a.Bm - 1) : n;
-  const int Tb = min(max(a.xlens[m], 0), T);
-  const int U = min(max(a.ylens[n], 0), Lmax);
-  if (Tb == 0) {  // (workgroup-uniform)
+  const rnnt_lattice::Cand c = rnnt_lattice::clamp(a.xlens, a.ylens, a.mem_of, a.Bm, a.T, a.Lmax, n);
+  if (c.Tb == 0) {  // (workgroup-uniform)
     if (u == 0) a.nll[n] = INFINITY;
     return;
   }
-  const size_t ld = (size_t)(Lmax + 1) * 2;
-  const float* base = a.lat + (size_t)n * T * ld;
-  const bool mine = u <= U;
-  // the terms that cell (t, u) adds: b[t-1][u] (t >= 1) and e[t][u-1] (u >= 1); a missing neighbour is -inf
-  auto load_b = [&](int t) { return mine && t >= 1 && t < Tb ? base[(size_t)(t - 1) * ld + 2 * u] : -INFINITY; };
-  auto load_e = [&](int t) { return mine && u >= 1 && t >= 0 && t < Tb ? base[(size_t)t * ld + 2 * (u - 1) + 1] : -INFINITY; };
-  float alpha = -INFINITY;  // alpha[d - 1 - u][u] while diagonal d runs
-  float nb = load_b(0 - u), ne = load_e(0 - u);
-  const int D = Tb + U;  // diagonals 0 .. D - 1
-  for (int d = 0; d < D; ++d) {
-    const int t = d - u;
-    const float b = nb, e = ne;
-    nb = load_b(t + 1);  // diagonal d + 1, in flight during this diagonal's chain
-    ne = load_e(t + 1);
-    const float left = u >= 1 ? row[(d + 1) & 1][u - 1] : -INFINITY;  // alpha[t][u-1], written on diagonal d - 1
-    if (mine && t >= 0 && t < Tb) alpha = d == 0 ? 0.f : logaddexp_(alpha + b, left + e);
-    row[d & 1][u] = (mine && t >= 0 && t < Tb) ? alpha : -INFINITY;
-    __syncthreads();
-  }
-  // thread U holds alpha[Tb-1][U] after the last diagonal
-  if (u == U) a.nll[n] = -(alpha + base[(size_t)(Tb - 1) * ld + 2 * U]);
+  const size_t ld = (size_t)(a.Lmax + 1) * 2;
+  const float* base = a.lat + (size_t)n * a.T * ld;
+  const float alpha = rnnt_lattice::walk(base, a.Lmax, c.Tb, c.U, row, SumCell{});
+  if (u == c.U) a.nll[n] = -(alpha + base[(size_t)(c.Tb - 1) * ld + 2 * c.U]);  // the closing blank
 }
 
 int check_weights(int dtype, const EmTransducerWeights* w) {
@@ -387,20 +355,15 @@ int check_weights(int dtype, const EmTransducerWeights* w) {
   return EM_OK;
 }
 
-bool lattice_shape_ok(int N, int T, int Lmax) {
-  if (N <= 0 || T <= 0 || Lmax < 0 || Lmax > SN_MAX_L) return false;
-  return (long)N * T * (Lmax + 1) <= LT_MAX_NODES;
-}
-
 EmLdsCap lattice_cap;
 
 }  // namespace
 
-extern "C" int32_t em_transducer_seq_nll_max_tokens(void) { return SN_MAX_L; }
+extern "C" int32_t em_transducer_seq_nll_max_tokens(void) { return rnnt_lattice::MAX_L; }
 
 extern "C" size_t em_transducer_lattice_logp_workspace_bytes(int dtype, const EmTransducerWeights* w, int32_t N, int32_t T,
                                                              int32_t Lmax) {
-  if (check_weights(dtype, w) != EM_OK || !lattice_shape_ok(N, T, Lmax)) return 0;
+  if (check_weights(dtype, w) != EM_OK || !rnnt_lattice::shape_ok(N, T, Lmax)) return 0;
   return (((size_t)N + 1) * sizeof(int32_t) + 255) & ~(size_t)255;
 }
 
@@ -412,7 +375,7 @@ extern "C" int em_transducer_lattice_logp(int dtype, const EmTransducerWeights* 
   if (!enc_proj || !xlens || !dec_proj || !ylens || !lat || N <= 0 || Bm <= 0 || T <= 0 || Lmax < 0) return EM_ERR_BAD_ARG;
   if (Lmax > 0 && !targets) return EM_ERR_BAD_ARG;
   if (!mem_of && N > Bm) return EM_ERR_BAD_ARG;
-  if (!lattice_shape_ok(N, T, Lmax) || (long)Bm * T > LT_MAX_NODES) return EM_ERR_UNSUPPORTED;
+  if (!rnnt_lattice::shape_ok(N, T, Lmax) || (long)Bm * T > rnnt_lattice::MAX_NODES) return EM_ERR_UNSUPPORTED;
   if (!ws || ws_bytes < em_transducer_lattice_logp_workspace_bytes(dtype, w, N, T, Lmax)) return EM_ERR_WORKSPACE;
   hipStream_t s = (hipStream_t)stream;
   LatArgs a;
@@ -437,11 +400,8 @@ extern "C" int em_transducer_seq_nll(const float* lat, const int32_t* xlens, int
                                      const int32_t* ylens, const int32_t* mem_of, int32_t N, float* nll, void* stream) {
   if (!lat || !xlens || !ylens || !nll || N <= 0 || Bm <= 0 || T <= 0 || Lmax < 0) return EM_ERR_BAD_ARG;
   if (!mem_of && N > Bm) return EM_ERR_BAD_ARG;
-  if (!lattice_shape_ok(N, T, Lmax)) return EM_ERR_UNSUPPORTED;
-  SeqArgs a;
-  a.lat = lat; a.xlens = xlens; a.ylens = ylens; a.mem_of = mem_of;
-  a.Bm = Bm; a.T = T; a.Lmax = Lmax;
-  a.nll = nll;
+  if (!rnnt_lattice::shape_ok(N, T, Lmax)) return EM_ERR_UNSUPPORTED;
+  const SeqArgs a{lat, xlens, ylens, mem_of, Bm, T, Lmax, nll};
   hipLaunchKernelGGL(seq_nll_kernel, dim3(N), dim3(64 * em_cdiv(Lmax + 1, 64)), 0, (hipStream_t)stream, a);
   EM_CHECK_LAUNCH();
   return EM_OK;

@@ -115,6 +115,62 @@ def test_all_equal_lattice_takes_every_tie_as_a_blank_move():
     _assert_row_equals(got, 0, R.viterbi(lat[0], Tb, U), Tb, U, "all equal")
 
 
+# ---------------------------------------------------------------------- one finite path: the two recursions agree
+# the smallest case; one frame, several tokens; the back-pointer word edge, with two waves of columns; five waves
+ONE_PATH_XLENS = [65, 33, 32, 1]
+ONE_PATH_CANDS = [(3, 0), (3, 5), (2, 4), (1, 64), (0, 300)]  # (utterance, U): (T_b, U) = (1, 0) (1, 5) (32, 4) (33, 64) (65, 300)
+ONE_PATH_T, ONE_PATH_LMAX = 68, 302  # padding frames and padding columns, NaN there
+
+
+def _one_path_lattice(g, Tb, U, T, Lmax):
+    """(T, Lmax + 1, 2) f32 with exactly one finite path from (0, 0) to (T_b - 1, U): the planted path's own moves and the
+    closing blank are multiples of 2^-6 in [-8, 0] (as `_exact_lattice` draws them), everything else inside (T_b, U) is
+    -inf, everything outside NaN.  Returns (lat, tok_frame [U], the path's sum in float64)."""
+    lat = torch.full((T, Lmax + 1, 2), float("nan"))
+    lat[:Tb, : U + 1] = -math.inf
+    tok_frame = sorted(torch.randint(0, Tb, (U,), generator=g).tolist())
+    draw = iter((-torch.randint(0, 8 * 64 + 1, (Tb + U,), generator=g).to(torch.float64) / 64.0).tolist())
+    total, u = 0.0, 0
+    for t in range(Tb):
+        while u < U and tok_frame[u] == t:
+            lat[t, u, 1] = next(draw)
+            total += float(lat[t, u, 1])
+            u += 1
+        lat[t, u, 0] = next(draw)  # the move to frame t + 1; at t == T_b - 1 the closing blank
+        total += float(lat[t, u, 0])
+    return lat, tok_frame, total
+
+
+def test_one_finite_path_sum_and_max_agree_bit_for_bit():
+    """On a lattice with ONE finite path the sum over paths and the maximum over paths are the same number: at most 65 + 300
+    terms of at most 8 in multiples of 2^-6 - below 2^12, 18 bits - so every partial sum is exact in f32, and
+    logaddexp(x, -inf) is x exactly (expf(-inf) = 0, log1pf(0) = 0).  So `total` of seq_align_device EQUALS the planted sum,
+    seq_nll_device is its negation bit for bit, and the path is the planted one.  One ragged batch over mem_of, with
+    padding frames and columns."""
+    g = torch.Generator().manual_seed(4242)
+    made = [_one_path_lattice(g, ONE_PATH_XLENS[m], U, ONE_PATH_T, ONE_PATH_LMAX) for m, U in ONE_PATH_CANDS]
+    # the restatements first, on the CPU: the planted path and sum, and the sum's negation
+    for (m, U), (lat, frames, want) in zip(ONE_PATH_CANDS, made):
+        Tb = ONE_PATH_XLENS[m]
+        ref = R.viterbi(lat, Tb, U)
+        assert ref["tok_frame"] == frames and ref["total"] == want and math.isfinite(want), (Tb, U)
+        assert R.forward_nll(lat, Tb, U) == -want, (Tb, U)
+    jn = _jn()
+    lat_dev = torch.stack([lat for lat, _, _ in made]).cuda()
+    xl, yl, mo = _i32(ONE_PATH_XLENS), _i32([u for _, u in ONE_PATH_CANDS]), _i32([m for m, _ in ONE_PATH_CANDS])
+    tok_frame, tok_logp, frame_u, total = (o.cpu() for o in jn.seq_align_device(lat_dev, xl, yl, mo))
+    nll = jn.seq_nll_device(lat_dev, xl, yl, mo).cpu()
+    for n, ((m, U), (lat, frames, want)) in enumerate(zip(ONE_PATH_CANDS, made)):
+        Tb = ONE_PATH_XLENS[m]
+        print(f"\none path {Tb} x {U}: planted {want!r}, total {float(total[n])!r}, nll {float(nll[n])!r}")
+        assert float(total[n]) == want, (Tb, U)
+        assert sf.bytes_equal(nll[n], -total[n]), (Tb, U)
+        assert tok_frame[n, :U].tolist() == frames, (Tb, U)
+        assert frame_u[n, :Tb].tolist() == [sum(1 for f in frames if f <= t) for t in range(Tb)], (Tb, U)
+        assert tok_logp[n, :U].tolist() == [float(lat[f, u, 1]) for u, f in enumerate(frames)], (Tb, U)
+        assert bool((tok_frame[n, U:] == -1).all()) and bool((tok_logp[n, U:] == 0).all()) and bool((frame_u[n, Tb:] == -1).all())
+
+
 # ---------------------------------------------------------------------- a ragged batch
 RAG_XLENS = [13, 0, 40]
 RAG_CANDS = [(0, 5), (2, 12), (1, 3), (0, 0), (2, 0), (2, 7), (0, 12), (1, 0), (2, 1)]  # (utterance, U); utterance 1: no frame

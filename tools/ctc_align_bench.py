@@ -21,23 +21,13 @@ from pathlib import Path
 import torch
 
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
+from tools.bench_common import timed_host as timed  # noqa: E402
 from espnet_amd import lib as L  # noqa: E402
 from espnet_amd.asr.ctc import CTC  # noqa: E402
 
 V, D = 5000, 256
 SHAPES = [dict(B=32, T=249, L=60, head=True), dict(B=32, T=249, L=120, head=True),
           dict(B=1, T=3000, L=700, head=False), dict(B=1, T=15000, L=3000, head=False)]
-
-
-def timed(fn, iters, warmup):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(iters):
-        fn()
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t0) * 1e3 / iters
 
 
 def targets(B, Lmax, jitter, seed):

@@ -17,7 +17,6 @@ Before anything is timed the device result is compared with that host run: paths
 frame_lp bit-equal.  Every leg is reported as measured, a losing one too."""
 import argparse
 import json
-import statistics
 import sys
 import time
 from pathlib import Path
@@ -26,13 +25,10 @@ import numpy as np
 import torch
 
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
+from tools.bench_common import summary  # noqa: E402
 
 SHAPES = {"long": dict(B=1, T=90000, C=45000, K=1500, pre=1500, post=2500, W=8192),
           "batch": dict(B=8, T=7500, C=3000, K=100, pre=100, post=200, W=8192)}
-
-
-def _summary(ms):
-    return dict(median=round(statistics.median(ms), 4), min=round(min(ms), 4), max=round(max(ms), 4))
 
 
 def timed(fn, reps, warmup):
@@ -47,7 +43,7 @@ def timed(fn, reps, warmup):
         b.record()
         b.synchronize()
         ms.append(a.elapsed_time(b))
-    return _summary(ms)
+    return summary(ms)
 
 
 def planted(seed, T, C, K, pre, post, V, blank=0, peak=12.0):

@@ -17,12 +17,12 @@ import json
 import os
 import statistics
 import sys
-import time
 from pathlib import Path
 
 import torch
 
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
+from tools.bench_common import timed_host as timed  # noqa: E402
 from espnet_amd import lib as L  # noqa: E402
 from espnet_amd.asr.encoder.contextual_block_conformer_encoder import ContextualBlockConformerEncoder  # noqa: E402
 from espnet_amd.asr.encoder.contextual_block_transformer_encoder import ContextualBlockTransformerEncoder  # noqa: E402
@@ -85,17 +85,6 @@ def make_call(enc, S, graph):
     with torch.cuda.graph(g):
         call()
     return g.replay
-
-
-def timed(fn, iters, warmup):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(iters):
-        fn()
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t0) * 1e3 / iters
 
 
 def set_env(env):

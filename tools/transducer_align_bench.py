@@ -19,7 +19,6 @@ Before anything is timed the alignment is checked against the restatement on the
 """
 import argparse
 import json
-import statistics
 import sys
 import time
 from pathlib import Path
@@ -27,10 +26,7 @@ from pathlib import Path
 import torch
 
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
-
-
-def _summary(ms):
-    return dict(median=round(statistics.median(ms), 4), min=round(min(ms), 4), max=round(max(ms), 4))
+from tools.bench_common import summary, transducer_candidates, transducer_small  # noqa: E402
 
 
 def timed_pair(fa, fb, reps, warmup, inner=1):
@@ -51,7 +47,7 @@ def timed_pair(fa, fb, reps, warmup, inner=1):
             b.record()
             b.synchronize()
             ms.append(a.elapsed_time(b) / inner)
-    return _summary(out[0]), _summary(out[1])
+    return summary(out[0]), summary(out[1])
 
 
 def main():
@@ -71,33 +67,16 @@ def main():
         raise SystemExit("transducer_align_bench: no GPU (a timing needs the device)")
 
     from espnet_amd import lib as L
-    from espnet_amd.tasks.asr import ASRTask
-    from oracle.weights import recipe_state_dict, synth_waveform, token_list
+    from oracle.weights import synth_waveform
     from tests.transducer_align_ref import viterbi
 
     V, B, N = a.vocab, a.utts, a.utts * a.per_utt
-    cfg = dict(token_list=token_list(V), frontend="default", frontend_conf=dict(n_fft=512, hop_length=160, win_length=400),
-               normalize="utterance_mvn", normalize_conf={}, encoder="conformer",
-               encoder_conf=dict(output_size=256, attention_heads=4, linear_units=1024, num_blocks=12, macaron_style=True,
-                                 cnn_module_kernel=31),
-               decoder="transducer", decoder_conf=dict(rnn_type="lstm", num_layers=1, hidden_size=512),
-               joint_net_conf=dict(joint_space_size=640), model_conf=dict(ctc_weight=0.0), compute_dtype="bfloat16")
-    model = ASRTask.build_model(cfg)
-    sd = model.state_dict()
-    new = recipe_state_dict({k: tuple(v.shape) for k, v in sd.items()}, 7)
-    new["frontend.logmel.melmat"] = sd["frontend.logmel.melmat"].clone()
-    new["decoder.embed.weight"][0] = 0.0
-    new["joint_network.lin_out.bias"][0] += 1.0
-    model.load_state_dict(new, strict=True)
-    model.cuda().eval()
+    model, _ = transducer_small(V)
     dec, jn = model.decoder, model.joint_network
     n_samples = int(a.seconds * 16000)
     speech = torch.stack([synth_waveform(b, n_samples) for b in range(B)]).cuda()
-    g = torch.Generator().manual_seed(7)
-    ylens = torch.randint(40, 81, (N,), generator=g)
-    Lmax = int(ylens.max())
-    ys = torch.randint(1, V - 1, (N, Lmax), generator=g)
-    mem_of = torch.arange(N) // a.per_utt
+    g, ylens, ys, mem_of = transducer_candidates(N, V, a.per_utt)
+    Lmax = int(ys.shape[1])
     with torch.no_grad():
         st = model.encode_device(speech, [n_samples] * B, isolate=True)
         enc_act, T = st.enc_act, int(st.enc_act.shape[1])
@@ -152,7 +131,7 @@ def main():
             t0 = time.perf_counter()
             host_route()
             host_ms.append((time.perf_counter() - t0) * 1e3)
-        res["host_route_ms"] = _summary(host_ms)
+        res["host_route_ms"] = summary(host_ms)
         res["host_route_runs"] = len(host_ms)  # (its own count, after the one run of the check above; host clock)
         res["align_over_nll"] = round(res["align_ms"]["median"] / res["nll_ms"]["median"], 3)
         res["whole_align_over_whole_nll"] = round(res["whole_align_ms"]["median"] / res["whole_nll_ms"]["median"], 3)

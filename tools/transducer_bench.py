@@ -23,6 +23,7 @@ from pathlib import Path
 import torch
 
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
+from tools.bench_common import transducer_small  # noqa: E402
 
 
 def timed(fn, reps, warmup):
@@ -52,24 +53,10 @@ def main():
     a = ap.parse_args()
 
     from espnet_amd.asr.transducer.beam_search_transducer import BeamSearchTransducer
-    from espnet_amd.tasks.asr import ASRTask
-    from oracle.weights import recipe_state_dict, synth_waveform, token_list
+    from oracle.weights import synth_waveform
 
     V, B = a.vocab, a.batch
-    cfg = dict(token_list=token_list(V), frontend="default", frontend_conf=dict(n_fft=512, hop_length=160, win_length=400),
-               normalize="utterance_mvn", normalize_conf={}, encoder="conformer",
-               encoder_conf=dict(output_size=256, attention_heads=4, linear_units=1024, num_blocks=12, macaron_style=True,
-                                 cnn_module_kernel=31),
-               decoder="transducer", decoder_conf=dict(rnn_type="lstm", num_layers=1, hidden_size=512),
-               joint_net_conf=dict(joint_space_size=640), model_conf=dict(ctc_weight=0.0), compute_dtype="bfloat16")
-    model = ASRTask.build_model(cfg)
-    sd = model.state_dict()
-    new = recipe_state_dict({k: tuple(v.shape) for k, v in sd.items()}, 7)
-    new["frontend.logmel.melmat"] = sd["frontend.logmel.melmat"].clone()
-    new["decoder.embed.weight"][0] = 0.0
-    new["joint_network.lin_out.bias"][0] += a.blank_bias
-    model.load_state_dict(new, strict=True)
-    model.cuda().eval()
+    model, new = transducer_small(V, a.blank_bias)
     dec, jn = model.decoder, model.joint_network
     bs = BeamSearchTransducer(dec, jn, beam_size=1)
     n = int(a.seconds * 16000)

@@ -21,30 +21,15 @@ the encoder on the BASELINE.md waveforms.
 """
 import argparse
 import json
-import statistics
 import sys
 from pathlib import Path
 
 import torch
 
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
+from tools.bench_common import timed, transducer_candidates, transducer_small  # noqa: E402
 
 PEAK_BF16_TFLOPS = 2500.0
-
-
-def timed(fn, reps, warmup):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        ms.append(a.elapsed_time(b))
-    return dict(median=round(statistics.median(ms), 4), min=round(min(ms), 4), max=round(max(ms), 4))
 
 
 def torch_recursion(lat, tb, U):
@@ -84,33 +69,16 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit("transducer_nll_bench: no GPU (a timing needs the device)")
 
-    from espnet_amd.tasks.asr import ASRTask
-    from oracle.weights import recipe_state_dict, synth_waveform, token_list
+    from oracle.weights import synth_waveform
 
     V, B, N = a.vocab, a.utts, a.utts * a.per_utt
-    cfg = dict(token_list=token_list(V), frontend="default", frontend_conf=dict(n_fft=512, hop_length=160, win_length=400),
-               normalize="utterance_mvn", normalize_conf={}, encoder="conformer",
-               encoder_conf=dict(output_size=256, attention_heads=4, linear_units=1024, num_blocks=12, macaron_style=True,
-                                 cnn_module_kernel=31),
-               decoder="transducer", decoder_conf=dict(rnn_type="lstm", num_layers=1, hidden_size=512),
-               joint_net_conf=dict(joint_space_size=640), model_conf=dict(ctc_weight=0.0), compute_dtype="bfloat16")
-    model = ASRTask.build_model(cfg)
-    sd = model.state_dict()
-    new = recipe_state_dict({k: tuple(v.shape) for k, v in sd.items()}, 7)
-    new["frontend.logmel.melmat"] = sd["frontend.logmel.melmat"].clone()
-    new["decoder.embed.weight"][0] = 0.0
-    new["joint_network.lin_out.bias"][0] += 1.0
-    model.load_state_dict(new, strict=True)
-    model.cuda().eval()
+    model, new = transducer_small(V)
     dec, jn = model.decoder, model.joint_network
     J = jn.joint_space_size
     n_samples = int(a.seconds * 16000)
     speech = torch.stack([synth_waveform(b, n_samples) for b in range(B)]).cuda()
-    g = torch.Generator().manual_seed(7)
-    ylens = torch.randint(40, 81, (N,), generator=g)
-    Lmax = int(ylens.max())
-    ys = torch.randint(1, V - 1, (N, Lmax), generator=g)
-    mem_of = torch.arange(N) // a.per_utt
+    _, ylens, ys, mem_of = transducer_candidates(N, V, a.per_utt)
+    Lmax = int(ys.shape[1])
     bf = torch.bfloat16
     with torch.no_grad():
         st = model.encode_device(speech, [n_samples] * B, isolate=True)
