@@ -84,6 +84,20 @@ class CTC(PackedModule):
         L.check(L.load().em_argmax_partials(L.ptr(part), B * T, G, L.ptr(ids), st), "em_argmax_partials")
         return ids if as_int32 else ids.to(torch.int64)
 
+    def frame_top_device(self, hs_pad: torch.Tensor):
+        """Per frame the arg-max id and its probability, exp(max_v log_softmax) (`em_ctc_frame_top`, csrc/maskctc.hip: the
+        logits never exist): hs_pad (B, T, d) on the GPU -> (ids (B, T) int32, prob (B, T) f32).  Only enqueues."""
+        act = self._to_act(hs_pad)
+        B, T, d = act.shape
+        p, dev, lib = self.packed(act.device), act.device, L.load()
+        ids = torch.empty(B, T, dtype=torch.int32, device=dev)
+        prob = torch.empty(B, T, dtype=torch.float32, device=dev)
+        need = lib.em_ctc_frame_top_workspace_bytes(self.em_dtype, B * T, self.odim)
+        ws = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
+        L.check(lib.em_ctc_frame_top(self.em_dtype, L.ptr(act), L.ptr(p.weight), L.ptr(p.bias), B * T, self.odim, d,
+                                     L.ptr(ids), L.ptr(prob), L.ptr(ws), need, L.current_stream_ptr()), "em_ctc_frame_top")
+        return ids, prob
+
     # ------------------------------------------------------------------ forced alignment (csrc/ctc_align.hip)
     @staticmethod
     def check_alignable(olens, targets, blank, vocab):

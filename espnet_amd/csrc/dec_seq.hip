@@ -201,15 +201,7 @@ SeqWs seq_layout(int dtype, const EmDecoderWeights* dw, size_t M) {
   return s;
 }
 
-// M rows and the widest activation row stay inside 31-bit element offsets (the GEMMs' buffer resources); B and the heads
-// are grid dimensions
-bool seq_shape_ok(const EmDecoderWeights* dw, int B, int Lp) {
-  if (B <= 0 || Lp <= 0 || B > 65535 || dw->heads <= 0 || dw->heads > 65535 || dw->d <= 0 || dw->d % dw->heads) return false;
-  const int dk = dw->d / dw->heads;
-  if ((dk != 32 && dk != 64) || dw->d > 1024) return false;  // (1024: the vocabulary head's rows in LDS)
-  const size_t wide = (size_t)(dw->ff > 3 * dw->d ? dw->ff : 3 * dw->d);
-  return (size_t)B * Lp * wide * 4 < ((size_t)1 << 31);
-}
+using em_host::dec_seq_shape_ok;
 
 }  // namespace
 
@@ -253,7 +245,7 @@ extern "C" int em_dec_seq_src_attention(int dtype, const void* qs, const void* k
 }
 
 extern "C" size_t em_dec_seq_nll_workspace_bytes(int dtype, const EmDecoderWeights* dw, int32_t B, int32_t Lp) {
-  if (!dw || (dtype != EM_BF16 && dtype != EM_F32) || !seq_shape_ok(dw, B, Lp)) return 0;
+  if (!dw || (dtype != EM_BF16 && dtype != EM_F32) || !dec_seq_shape_ok(dw, B, Lp)) return 0;
   return seq_layout(dtype, dw, (size_t)B * Lp).total;
 }
 
@@ -265,7 +257,7 @@ extern "C" int em_dec_seq_nll(int dtype, const EmDecoderWeights* dw, const void*
   if (dtype != EM_BF16 && dtype != EM_F32) return EM_ERR_BAD_ARG;
   if (B <= 0 || Bm <= 0 || Lp <= 0 || T <= 0 || Tpad < T || Tpad % 32 != 0 || (!mem_of && Bm < B)) return EM_ERR_BAD_ARG;
   if (dw->d <= 0 || dw->heads <= 0 || dw->d % dw->heads || Lp > dw->pe_len) return EM_ERR_BAD_ARG;
-  if (!seq_shape_ok(dw, B, Lp)) return EM_ERR_UNSUPPORTED;
+  if (!dec_seq_shape_ok(dw, B, Lp)) return EM_ERR_UNSUPPORTED;
   const int M = B * Lp, V = dw->vocab, d = dw->d, ff = dw->ff, h = dw->heads;
   const size_t es = dtype == EM_BF16 ? 2 : 4;
   const SeqWs o = seq_layout(dtype, dw, (size_t)M);

@@ -44,6 +44,16 @@ inline int gemm(int dtype, int epi, const void* A, const void* W, void* C, const
   return em_gemm(dtype, epi, EM_A_PLAIN, &a, stream);
 }
 
+// ---- the attention decoder over whole sentences (csrc/dec_seq.hip, csrc/maskctc.hip): M = B * Lp rows and the widest
+// activation row stay inside 31-bit element offsets (the GEMMs' buffer resources); B and the heads are grid dimensions
+inline bool dec_seq_shape_ok(const EmDecoderWeights* dw, int B, int Lp) {
+  if (B <= 0 || Lp <= 0 || B > 65535 || dw->heads <= 0 || dw->heads > 65535 || dw->d <= 0 || dw->d % dw->heads) return false;
+  const int dk = dw->d / dw->heads;
+  if ((dk != 32 && dk != 64) || dw->d > 1024) return false;  // (1024: the vocabulary head's rows in LDS)
+  const size_t wide = (size_t)(dw->ff > 3 * dw->d ? dw->ff : 3 * dw->d);
+  return (size_t)B * Lp * wide * 4 < ((size_t)1 << 31);
+}
+
 // ---- per-head operands of the batch encoders' attention: Tpad frames per (utterance, head), a multiple of 256
 inline int tpad256(int T) { return (T + 255) / 256 * 256; }
 inline size_t head_slab_bytes(int B, int d, int Tpad, size_t es) { return (size_t)B * d * Tpad * es; }

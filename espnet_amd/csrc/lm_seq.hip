@@ -58,7 +58,9 @@ __global__ __launch_bounds__(256) void lm_seq_input_norm_kernel(float* __restric
 // The running maximum is shared by the four lane groups of a query (they all scale the same accumulators), the running sum is
 // per lane and meets at the end.  A masked key (beyond the diagonal, id 0, or past Lp) takes p = 0.0 exactly; a query with no
 // visible key writes zeros.  LDS: one V tile, 4.5 KiB at DK = 64, whatever Lp is.
-template <int DK>
+// CAUSAL = false (em_dec_full_attention, the MLM decoder): no diagonal, x [B] holds the sentences' lengths and query (b, j)
+// sees the keys below x[b]; the V rows of the keys behind it enter LDS as zeros (0.0 * whatever lies there would not be 0).
+template <int DK, bool CAUSAL>
 __global__ __launch_bounds__(64) void lm_causal_attn_bf16_kernel(const bf16* __restrict__ qkv, const int32_t* __restrict__ x,
                                                                  int Lp, int d, bf16* __restrict__ ctx) {
   constexpr int NC = DK / 32, ND = DK / 16, VLD = DK + 8;
@@ -77,13 +79,15 @@ __global__ __launch_bounds__(64) void lm_causal_attn_bf16_kernel(const bf16* __r
   f32x4 acc[ND];
 #pragma unroll
   for (int t = 0; t < ND; ++t) acc[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
-  const int kend = min(q0 + 16, Lp);
+  const int kend = CAUSAL ? min(q0 + 16, Lp) : min(max(x[b], 0), Lp);
   for (int k0 = 0; k0 < kend; k0 += 32) {
     __syncthreads();  // the previous tile's V is read
     for (int i = lane; i < 32 * (DK / 8); i += 64) {
       const int kr = i / (DK / 8), cc = i % (DK / 8);
       const bf16* src = qkv + (row0 + min(k0 + kr, Lp - 1)) * ld + 2 * d + h * DK + cc * 8;
-      *(bf16x8*)(vs + kr * VLD + cc * 8) = *(const bf16x8*)src;
+      bf16x8 v = *(const bf16x8*)src;
+      if (!CAUSAL && k0 + kr >= kend) v = (bf16x8){0, 0, 0, 0, 0, 0, 0, 0};
+      *(bf16x8*)(vs + kr * VLD + cc * 8) = v;
     }
     f32x4 s[2];
 #pragma unroll
@@ -98,7 +102,7 @@ __global__ __launch_bounds__(64) void lm_causal_attn_bf16_kernel(const bf16* __r
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       const int key = k0 + (j >> 2) * 16 + lg * 4 + (j & 3);
-      const bool ok = key <= qi && key < Lp && x[row0 + min(key, Lp - 1)] != 0;
+      const bool ok = CAUSAL ? key <= qi && key < Lp && x[row0 + min(key, Lp - 1)] != 0 : key < kend;
       sc[j] = ok ? s[j >> 2][j & 3] * scale : -INFINITY;
       tmax = fmaxf(tmax, sc[j]);
     }
@@ -141,7 +145,9 @@ __global__ __launch_bounds__(64) void lm_causal_attn_bf16_kernel(const bf16* __r
 }
 
 // ---- the same attention in f32, plain (parity path): one wave per (query, head, sentence).  Pass 1 finds the row maximum,
-// pass 2 recomputes the scores 64 keys at a time and lets lane c < dk accumulate channel c of the context.
+// pass 2 recomputes the scores 64 keys at a time and lets lane c < dk accumulate channel c of the context.  CAUSAL = false:
+// the keys below the sentence's length x[b], whatever the query.
+template <bool CAUSAL>
 __global__ __launch_bounds__(64) void lm_causal_attn_f32_kernel(const float* __restrict__ qkv, const int32_t* __restrict__ x,
                                                                 int Lp, int d, int dk, float* __restrict__ ctx) {
   const int j = blockIdx.x, h = blockIdx.y, b = blockIdx.z, lane = threadIdx.x;
@@ -150,9 +156,10 @@ __global__ __launch_bounds__(64) void lm_causal_attn_f32_kernel(const float* __r
   const float* q = qkv + (row0 + j) * ld + h * dk;
   const float scale = 1.0f / sqrtf((float)dk);
   float* out = ctx + (row0 + j) * (size_t)d + h * dk;
+  const int nkey = CAUSAL ? j + 1 : min(max(x[b], 0), Lp);  // the keys 0 .. nkey - 1 can be seen
   float m = -INFINITY;
-  for (int k = lane; k <= j; k += 64) {
-    if (x[row0 + k] == 0) continue;
+  for (int k = lane; k < nkey; k += 64) {
+    if (CAUSAL && x[row0 + k] == 0) continue;
     const float* kr = qkv + (row0 + k) * ld + d + h * dk;
     float s = 0.f;
     for (int c = 0; c < dk; ++c) s += q[c] * kr[c];
@@ -164,17 +171,17 @@ __global__ __launch_bounds__(64) void lm_causal_attn_f32_kernel(const float* __r
     return;
   }
   float lsum = 0.f, acc = 0.f;
-  for (int k0 = 0; k0 <= j; k0 += 64) {
+  for (int k0 = 0; k0 < nkey; k0 += 64) {
     const int k = k0 + lane;
     float p = 0.f;
-    if (k <= j && x[row0 + k] != 0) {
+    if (k < nkey && (!CAUSAL || x[row0 + k] != 0)) {
       const float* kr = qkv + (row0 + k) * ld + d + h * dk;
       float s = 0.f;
       for (int c = 0; c < dk; ++c) s += q[c] * kr[c];
       p = expf(s * scale - m);
     }
     lsum += p;
-    const int n = min(64, j + 1 - k0);
+    const int n = min(64, nkey - k0);
     for (int kk = 0; kk < n; ++kk) {
       const float pk = __shfl(p, kk, 64);
       if (lane < dk) acc += pk * qkv[(row0 + k0 + kk) * ld + 2 * d + h * dk + lane];
@@ -422,10 +429,10 @@ bool seq_shape_ok(const EmLmWeights* lm, int B, int Lp) {
   return (size_t)B * Lp * wide * 4 < ((size_t)1 << 31);
 }
 
-}  // namespace
-
-extern "C" int em_lm_causal_attention(int dtype, const void* qkv, const int32_t* x, int32_t B, int32_t Lp, int32_t d,
-                                      int32_t heads, void* ctx, void* stream) {
+// the launch of both attentions: x is the token array of the causal form, the lengths of the full one
+template <bool CAUSAL>
+int seq_attention(int dtype, const void* qkv, const int32_t* x, int32_t B, int32_t Lp, int32_t d, int32_t heads, void* ctx,
+                  void* stream) {
   if (!qkv || !x || !ctx || B <= 0 || Lp <= 0 || d <= 0 || heads <= 0 || d % heads) return EM_ERR_BAD_ARG;
   const int dk = d / heads;
   if (dk != 32 && dk != 64) return EM_ERR_UNSUPPORTED;
@@ -434,17 +441,32 @@ extern "C" int em_lm_causal_attention(int dtype, const void* qkv, const int32_t*
   if (dtype == EM_BF16) {
     const dim3 grid(em_cdiv(Lp, 16), heads, B);
     if (dk == 64)
-      hipLaunchKernelGGL(lm_causal_attn_bf16_kernel<64>, grid, dim3(64), 0, s, (const bf16*)qkv, x, Lp, d, (bf16*)ctx);
+      hipLaunchKernelGGL((lm_causal_attn_bf16_kernel<64, CAUSAL>), grid, dim3(64), 0, s, (const bf16*)qkv, x, Lp, d,
+                         (bf16*)ctx);
     else
-      hipLaunchKernelGGL(lm_causal_attn_bf16_kernel<32>, grid, dim3(64), 0, s, (const bf16*)qkv, x, Lp, d, (bf16*)ctx);
+      hipLaunchKernelGGL((lm_causal_attn_bf16_kernel<32, CAUSAL>), grid, dim3(64), 0, s, (const bf16*)qkv, x, Lp, d,
+                         (bf16*)ctx);
   } else if (dtype == EM_F32) {
-    hipLaunchKernelGGL(lm_causal_attn_f32_kernel, dim3(Lp, heads, B), dim3(64), 0, s, (const float*)qkv, x, Lp, d, dk,
+    hipLaunchKernelGGL(lm_causal_attn_f32_kernel<CAUSAL>, dim3(Lp, heads, B), dim3(64), 0, s, (const float*)qkv, x, Lp, d, dk,
                        (float*)ctx);
   } else {
     return EM_ERR_BAD_ARG;
   }
   EM_CHECK_LAUNCH();
   return EM_OK;
+}
+
+}  // namespace
+
+extern "C" int em_lm_causal_attention(int dtype, const void* qkv, const int32_t* x, int32_t B, int32_t Lp, int32_t d,
+                                      int32_t heads, void* ctx, void* stream) {
+  return seq_attention<true>(dtype, qkv, x, B, Lp, d, heads, ctx, stream);
+}
+
+// (contract: include/espnet_amd.h, "Mask-CTC")
+extern "C" int em_dec_full_attention(int dtype, const void* qkv, const int32_t* lens, int32_t B, int32_t Lp, int32_t d,
+                                     int32_t heads, void* ctx, void* stream) {
+  return seq_attention<false>(dtype, qkv, lens, B, Lp, d, heads, ctx, stream);
 }
 
 extern "C" size_t em_lm_head_nll_workspace_bytes(int dtype, int32_t M, int32_t V) {

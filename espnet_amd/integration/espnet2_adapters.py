@@ -16,6 +16,7 @@ from espnet2.layers.abs_normalize import AbsNormalize
 from espnet2.legacy.nets.scorer_interface import BatchPartialScorerInterface, BatchScorerInterface
 from espnet2.lm.abs_model import AbsLM
 
+from espnet_amd.asr.decoder.mlm_decoder import MLMDecoder as _MLMDecoder
 from espnet_amd.asr.decoder.transformer_decoder import TransformerDecoder as _TransformerDecoder
 from espnet_amd.asr.encoder.conformer_encoder import ConformerEncoder as _ConformerEncoder
 from espnet_amd.asr.encoder.contextual_block_conformer_encoder import (
@@ -112,6 +113,11 @@ class MI355XTransformerDecoder(_TransformerDecoder, AbsDecoder, BatchScorerInter
     """espnet2/asr/decoder/transformer_decoder.py:393-468; scorer interface :191-311."""
 
 
+class MI355XMLMDecoder(_MLMDecoder, AbsDecoder):
+    """espnet2/asr/decoder/mlm_decoder.py (the Mask-CTC decoder: `forward` without the causal mask; no scorer interface
+    in the reference either)."""
+
+
 class MI355XTransformerLM(_TransformerLM, AbsLM):
     """espnet2/lm/transformer_lm.py:12-137."""
 
@@ -135,7 +141,7 @@ ADAPTERS = {
                 "mi355x_contextual_block_transformer": MI355XContextualBlockTransformerEncoder},
     "frontend": {"mi355x_default": MI355XDefaultFrontend},
     "normalize": {"mi355x_global_mvn": MI355XGlobalMVN, "mi355x_utterance_mvn": MI355XUtteranceMVN},
-    "decoder": {"mi355x_transformer": MI355XTransformerDecoder},
+    "decoder": {"mi355x_transformer": MI355XTransformerDecoder, "mi355x_mlm": MI355XMLMDecoder},
     "lm": {"mi355x_transformer": MI355XTransformerLM, "mi355x_seq_rnn": MI355XSequentialRNNLM},
 }
 

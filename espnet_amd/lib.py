@@ -383,6 +383,16 @@ _SIGNATURES = {
     "em_dec_seq_nll_workspace_bytes": (_sz, [C.c_int, C.POINTER(EmDecoderWeights), _i32, _i32]),
     "em_dec_seq_nll": (C.c_int, [C.c_int, C.POINTER(EmDecoderWeights), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32,
                                  _i32, _i32, _vp, _vp, _sz, _vp]),
+    "em_ctc_frame_top_workspace_bytes": (_sz, [C.c_int, _i32, _i32]),
+    "em_ctc_frame_top": (C.c_int, [C.c_int, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _sz, _vp]),
+    "em_lm_head_top1_workspace_bytes": (_sz, [C.c_int, _i32, _i32]),
+    "em_lm_head_top1": (C.c_int, [C.c_int, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _sz, _vp]),
+    "em_maskctc_collapse": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "em_dec_full_attention": (C.c_int, [C.c_int, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "em_maskctc_fill": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "em_maskctc_refine_workspace_bytes": (_sz, [C.c_int, C.POINTER(EmDecoderWeights), _i32, _i32]),
+    "em_maskctc_refine": (C.c_int, [C.c_int, C.POINTER(EmDecoderWeights), _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32,
+                                    _i32, _i32, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
     "em_ctc_log_probs_t": (C.c_int, [C.c_int, _vp, _i32, _i32, _i32, _vp, _vp, _i32, _vp, _vp]),
     "em_ctc_prefix_init": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _vp]),
     "em_ctc_prefix_score": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32,

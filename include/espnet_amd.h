@@ -30,7 +30,9 @@
  *       em_ctc_segment: every output whole (columns -1, frames -1, scores 0 off the path and behind the lengths);
  *       em_transducer_greedy: ylens and score whole, tokens[b][< ylens[b]], the traces [b][< olens[b]];
  *       em_transducer_lattice_logp: the nodes t < xlens[mem_of[n]], u <= ylens[n] (the label of u == ylens[n]: -inf);
- *       em_transducer_seq_align: every output whole (frames -1, log-probabilities 0 behind the lengths).
+ *       em_transducer_seq_align: every output whole (frames -1, log-probabilities 0 behind the lengths);
+ *       em_ctc_frame_top, em_lm_head_top1: both outputs [M] whole; em_maskctc_refine: y_in and the traces whole
+ *         (tests/test_gpu_maskctc.py).
  *   - EmSearchBuffers: the caller writes xlens / maxlens / minlens per search and ZEROES ONCE, at allocation, mem_vT,
  *     rnn_hs, rnn_cs and rnn_hin (and again mem_vT whenever Tpad changes under it: the streaming search).  The library
  *     leaves their zero regions zero - the columns T .. Tpad of mem_vT, the channels nhid .. d of every recurrent state
@@ -1138,6 +1140,64 @@ size_t em_dec_seq_nll_workspace_bytes(int dtype, const EmDecoderWeights* dw, int
 int em_dec_seq_nll(int dtype, const EmDecoderWeights* dw, const void* mem_kv, const void* mem_vT, const int32_t* klens,
                    const int32_t* mem_of, const int32_t* x, const int32_t* keymask, const int32_t* target, int32_t B,
                    int32_t Bm, int32_t Lp, int32_t T, int32_t Tpad, float* nll, void* ws, size_t ws_bytes, void* stream);
+
+/* ---- Mask-CTC (csrc/maskctc.hip; em_dec_full_attention: csrc/lm_seq.hip): espnet2/asr/maskctc_model.py
+ *      MaskCTCInference.forward with espnet2/asr/decoder/mlm_decoder.py MLMDecoder - greedy CTC with the frames' winning
+ *      probabilities, collapse with confidence, threshold, then K dense passes of the MLM decoder with the easiest-first
+ *      fill, for a ragged batch and without a read-back between the passes.  The decoder's tables have V + 1 rows
+ *      (dw->vocab = V + 1), mask_token = V.
+ *   em_ctc_frame_top: per row r < M of enc_act [M][d] (compute dtype) and the CTC head ctc_w [V][d], ctc_b [V]:
+ *     ids[r] = argmax_v y[r][v] (the lowest id among equals), prob[r] = softmax(y[r])[ids[r]] = 1 / sum_v exp(y - max).
+ *     The [M][V] logits are never stored: a (max, arg-max, sum-exp) record per row and 512-column slice, merged.  EM_BF16:
+ *     MFMA, d % 32 == 0, d <= 1024 (EM_ERR_UNSUPPORTED otherwise), ws of em_ctc_frame_top_workspace_bytes bytes
+ *     (EM_ERR_WORKSPACE when smaller); EM_F32: a plain kernel, d <= 16 384, no workspace (the query returns 0).
+ *   em_lm_head_top1: em_lm_head_nll's twin: y = LN(xrows; norm_g, norm_b, eps 1e-12) out_w^T + out_b over V columns,
+ *     smax[r] = max_v y[r][v], amax[r] = its lowest arg-max; same shapes, workspace rule and refusals as em_ctc_frame_top.
+ *   em_maskctc_collapse: ids / prob [B][T] as em_ctc_frame_top leaves them, olens [B] the valid frames.  The frames
+ *     t < olens[b] are cut into maximal runs of equal id; every run whose id != blank is one token with the confidence
+ *     max prob over the run.  tokens / conf / y_in [B][Lcap], y_in[j] = conf[j] < p_thres ? mask_token : tokens[j];
+ *     ylens[b] = the token count (clipped to Lcap), nmask[b] = the masked positions.  Every output is written whole:
+ *     tokens and y_in -1, conf 0.0 behind ylens[b].
+ *   em_dec_full_attention: em_lm_causal_attention's twin without the diagonal: qkv [B*Lp][3d] (q | k | v), lens [B];
+ *     query (b, j) attends the keys k < lens[b] and nothing else.  A masked key contributes an exact zero whatever its k
+ *     and v rows hold; a sentence of length 0 gives zero rows; the rows of the queries at and behind lens[b] are don't-care.
+ *     d / heads in {32, 64} (EM_ERR_UNSUPPORTED otherwise), any Lp >= 1.  EM_BF16: MFMA, f32 accumulation, online softmax
+ *     over tiles of 32 keys, one V tile in LDS (4.5 KiB whatever Lp is); EM_F32: a plain kernel.
+ *   em_maskctc_fill: one pass of the refinement's selection.  y_in [B][Lp] in place; s / a [B][Lp] the max logit and
+ *     arg-max of every position; nmask0 [B] = M_b as em_maskctc_collapse counted it.  n_iter_b = min(K, M_b),
+ *     n_b = M_b / n_iter_b.  pass < n_iter_b - 1: the n_b positions holding mask_token with the largest s (equal scores:
+ *     the lowest position first) take their a; pass == n_iter_b - 1: every position holding mask_token does; later passes
+ *     and M_b == 0: nothing.  y_trace [B][Lp] or NULL receives y_in as the pass leaves it.  Lp <= 2 048
+ *     (EM_ERR_UNSUPPORTED beyond), K >= 1 (EM_ERR_BAD_ARG otherwise: the reference's loop is unbounded there).
+ *   em_maskctc_refine: the whole refinement, enqueue only.  K times: em_dec_seq_embed_f32 of y_in (-1 reads row 0), the
+ *     pre-norm layers (em_dec_full_attention with ylens, em_dec_seq_src_attention on the caller's em_decoder_memory of B
+ *     memories with klens, the feed-forward), after_norm + em_lm_head_top1, em_maskctc_fill.  y_in / ylens / nmask0 as
+ *     em_maskctc_collapse leaves them with Lcap = Lp; y_in holds the result.  Utterance b's result depends on its own
+ *     tokens and memory only.  y_trace [K][B][Lp] or NULL: y_in after each pass; s_trace / a_trace [K][B][Lp] (both or
+ *     neither): what each pass's head returned.  dw->pe must hold Lp rows (EM_ERR_BAD_ARG otherwise).  ws:
+ *     em_maskctc_refine_workspace_bytes bytes of device memory (0 = shape not covered - d / heads outside {32, 64},
+ *     d > 1 024, Lp > 2 048, B * Lp rows outside the GEMMs' index range: em_maskctc_refine then returns
+ *     EM_ERR_UNSUPPORTED); a smaller one: EM_ERR_WORKSPACE.  Contents of ws on entry: ignored ("Scratch memory" above). */
+size_t em_ctc_frame_top_workspace_bytes(int dtype, int32_t M, int32_t V);
+int em_ctc_frame_top(int dtype, const void* enc_act, const void* ctc_w, const float* ctc_b, int32_t M, int32_t V, int32_t d,
+                     int32_t* ids, float* prob, void* ws, size_t ws_bytes, void* stream);
+size_t em_lm_head_top1_workspace_bytes(int dtype, int32_t M, int32_t V);
+int em_lm_head_top1(int dtype, const float* xrows, const float* norm_g, const float* norm_b, const void* out_w,
+                    const float* out_b, int32_t M, int32_t V, int32_t d, float* smax, int32_t* amax, void* ws,
+                    size_t ws_bytes, void* stream);
+int em_maskctc_collapse(const int32_t* ids, const float* prob, const int32_t* olens, int32_t B, int32_t T, int32_t Lcap,
+                        int32_t blank, int32_t mask_token, float p_thres, int32_t* tokens, float* conf, int32_t* y_in,
+                        int32_t* ylens, int32_t* nmask, void* stream);
+int em_dec_full_attention(int dtype, const void* qkv, const int32_t* lens, int32_t B, int32_t Lp, int32_t d, int32_t heads,
+                          void* ctx, void* stream);
+int em_maskctc_fill(int32_t* y_in, const float* s, const int32_t* a, const int32_t* nmask0, int32_t B, int32_t Lp, int32_t K,
+                    int32_t pass, int32_t mask_token, int32_t* y_trace, void* stream);
+size_t em_maskctc_refine_workspace_bytes(int dtype, const EmDecoderWeights* dw, int32_t B, int32_t Lp);
+int em_maskctc_refine(int dtype, const EmDecoderWeights* dw, const void* mem_kv, const void* mem_vT, const int32_t* klens,
+                      int32_t* y_in, const int32_t* ylens, const int32_t* nmask0, int32_t B, int32_t Lp, int32_t T,
+                      int32_t Tpad, int32_t K, int32_t mask_token, int32_t* y_trace, float* s_trace, int32_t* a_trace,
+                      void* ws, size_t ws_bytes, void* stream);
+
 /*   CTC.log_softmax(enc) (espnet2/asr/ctc.py:197-205, scorers/ctc.py:96-98) TRANSPOSED: lpT [V][B*T] f32. */
 int em_ctc_log_probs_t(int dtype, const void* enc_act, int32_t B, int32_t T, int32_t d_model,
                        const void* ctc_w, const float* ctc_b, int32_t V, float* lpT, void* stream);
