@@ -180,20 +180,34 @@ def test_frontend_logmel(lib, win_length, hop):
     assert err < 2e-4, err
 
 
-@pytest.mark.parametrize("n_mels,hop,isolate", [(80, 160, False), (80, 128, True), (40, 160, False), (23, 160, True), (80, 97, False)])
+@pytest.mark.parametrize("n_mels,hop,isolate", [(80, 160, False), (80, 128, True), (40, 160, False), (23, 160, True), (80, 97, False),
+                                                (48, 160, False), (64, 128, True), (72, 97, False)])
 def test_frontend_v2_equals_v1(lib, n_mels, hop, isolate):
     """Round 5: the frontend kernel that walks eight frames per wave (window, twiddles and the mel bands in registers,
     wave-private padded LDS tiles) must give the bits of the one-frame-per-wave kernel of rounds 1-4
     (ESPNET_AMD_FRONTEND_V1=1): same operations in the same order.  Ragged lengths (reflection at the utterance's own end
-    with `isolate`), mel banks with other band widths, an odd hop (the unaligned load path)."""
+    with `isolate`), mel banks with other band widths, an odd hop (the unaligned load path).
+
+    Which kernel the non-forced leg runs depends on the bank: the round-5 kernel takes `mel_maxlen <= 32 and
+    n_mels <= 80` only.  The 80-, 72-, 64- and 48-mel sets (widest bands 18, 20, 23, 30) reach it, which is asserted
+    through tests/frontend_ref.py::frontend_variant; the 40- and 23-mel sets (widest bands 36 and 58) run kernel1 in
+    both legs (kept as a regression of the fallback)."""
     import os
 
     from oracle.mel import slaney_mel_filterbank
     from oracle.weights import synth_waveform
+    from tests.frontend_ref import band_limits, frontend_variant
 
     melmat = torch.from_numpy(slaney_mel_filterbank(16000, 512, n_mels, 0, 8000).T.copy())
     lens = [16000, 12345, 5000, 700]
     nmax = 16000 + (1 if hop == 97 else 0)  # (an odd row pitch: every other utterance starts on an odd sample)
+    mel_maxlen = band_limits(melmat.numpy())[2]
+    natural = frontend_variant(len(lens), 1 + nmax // hop, n_mels, mel_maxlen)[0]
+    if mel_maxlen <= 32 and n_mels <= 80:
+        assert natural.startswith("v2/"), (natural, mel_maxlen)
+        assert n_mels in (80, 72, 64, 48)
+    else:
+        assert natural == "v1" and n_mels in (40, 23), (natural, mel_maxlen)
     speech = torch.zeros(len(lens), nmax)
     for i, n in enumerate(lens):
         speech[i, :n] = synth_waveform(40 + i, n)
@@ -203,6 +217,7 @@ def test_frontend_v2_equals_v1(lib, n_mels, hop, isolate):
     fe.logmel.melmat.copy_(melmat)
     fe.cuda()
     sp = dev(speech)
+    assert fe.packed(sp.device).maxlen == mel_maxlen  # (what the dispatch is given is what frontend_variant was given)
     flens = dev(torch.tensor(fe.feature_lengths(lens), dtype=torch.int32))
     wlens = dev(torch.tensor(lens, dtype=torch.int32)) if isolate else None
     outs = []
