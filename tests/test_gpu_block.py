@@ -6,7 +6,8 @@ SAME bf16-ROUNDED operands and with the same bf16 rounding points the unfused bf
 FFN hidden activation, GLU output, depthwise-conv output, q / k / v), so what is checked is the kernel, not the
 rounding.  Tolerances: 4e-3 of the output scale for the f32 residual stream (same class as
 test_ffn_fused_bf16), 2e-2 for bf16 outputs (one bf16 ulp is 0.8 %).  Then the whole encoder: fused vs the
-per-operator launch sequence on the reference goldens.
+per-operator launch sequence on the reference goldens.  The attention phase of block<ATT|C> is also observed directly
+(test_block_att_c_attention_parity): per element against the float64 reference and budget of tests/attention_ref.py.
 """
 import math
 
@@ -17,6 +18,7 @@ import torch.nn.functional as F
 from espnet_amd import lib as L
 from espnet_amd.asr.encoder.conformer_encoder import pack_k_units, pack_w1, pack_w2
 from oracle import conformer as oc
+from tests import attention_ref as ar
 
 pytestmark = pytest.mark.gpu
 BF = torch.bfloat16
@@ -375,6 +377,41 @@ def test_block_att_c(lib, B, T, klens):
     # missing operands are refused
     a.klens = None
     assert lib.em_conformer_block_fused(L.EM_BLOCK_ATT | L.EM_BLOCK_C, a, L.current_stream_ptr()) == L.EM_ERR_BAD_ARG
+
+
+@pytest.mark.parametrize("regime", ar.REGIMES)
+@pytest.mark.parametrize("T,klens,h", ar.FUSED_CASES, ids=[f"T{T}x{len(kl)}" for T, kl, _ in ar.FUSED_CASES])
+def test_block_att_c_attention_parity(lib, T, klens, h, regime):
+    """The attention phase of block<ATT|C> observed directly.  With linear_out = identity, no bias and a zero residual the x
+    the launch writes back is the attention context itself, bit for bit as the kernel rounds it to bf16 in front of linear_out
+    (the products with 1 and the sums with 0 are exact in f32), so it is held per element to the float64 reference and the
+    bf16 budget of tests/attention_ref.py (3 u A + f (1 + S) A, exactly zero where no valid key reaches a channel) on the
+    tile-edge cases of tests/test_gpu_attention_parity.py, on all rows of every utterance.  (klens[b] > T is left out; glu
+    is not asserted here: test_block_att_c holds it.)
+    Measured on an MI355X, the worst err / budget over these cases: 0.673 (T = 40, nine utterances, sharp; exactly 0 at T = 1)."""
+    assert h == H
+    B = len(klens)
+    case = ar.case_for(T, klens, H, regime)
+    ly = Layer(1100, 256)
+    ly.wout, ly.bout = torch.eye(D), torch.zeros(D)
+    Tp = tpad(T)
+    qh = torch.full((B, H, Tp, 64), float("nan"), dtype=BF)  # rows >= T: never read into a stored output
+    kh = torch.full((B, H, Tp, 64), float("nan"), dtype=BF)  # keys >= klen: masked by select, never by arithmetic
+    vt = torch.zeros(B, H, 64, Tp, dtype=BF)                 # V^T padding must be finite (0 * x)
+    qh[:, :, :T] = case.q.transpose(1, 2).to(BF)
+    kh[:, :, :T] = case.k.transpose(1, 2).to(BF)
+    vt[:, :, :, :T] = case.v.permute(0, 2, 3, 1).to(BF)
+    palld = dev(case.pall.to(BF))
+    ppk, npg = packed_pos(lib, palld, T, ar.LB)
+    xd = dev(torch.zeros(B * T, D))
+    glu = torch.zeros(B * T, D, dtype=BF, device="cuda")
+    a = block_args(B, T, 256, x=xd, glu=glu, qh=dev(qh), kh=dev(k_to_frag(kh)), vt=dev(vt_to_frag(vt)),
+                   wout=dev(pack_k_units(ly.wout).to(BF)), pw1f=dev(pack_k_units(ly.pw1[ly.perm()]).to(BF)), params=dev(ly.c_group()),
+                   pos_u=dev(case.u), pos_v=dev(case.vb), klens=dev(torch.tensor(klens, dtype=torch.int32)))
+    a.pos, a.ldp, a.kv_frag = ppk.data_ptr() + 4 * npg * 2048, npg, 1  # (the middle block of the table)
+    L.check(lib.em_conformer_block_fused(L.EM_BLOCK_ATT | L.EM_BLOCK_C, a, L.current_stream_ptr()), "block<ATT|C>")
+    r = ar.assert_in_budget(xd.reshape(B, T, D), ar.ref_rel(case, "scaled"), BF, f"block<ATT|C> attention T={T} klens={klens} {regime}")
+    print(f"PARITY block<ATT|C> T={T} B={B} {regime}: err / budget {r:.3f}")
 
 
 def test_block_att_c_repeatable_at_bench_shape(lib):
