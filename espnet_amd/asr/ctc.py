@@ -85,7 +85,7 @@ class CTC(PackedModule):
         return ids if as_int32 else ids.to(torch.int64)
 
     def frame_top_device(self, hs_pad: torch.Tensor):
-        """Per frame the arg-max id and its probability, exp(max_v log_softmax) (`em_ctc_frame_top`, csrc/maskctc.hip: the
+        """Per frame the arg-max id and its probability, exp(max_v log_softmax) (`em_ctc_frame_top`, csrc/vocab_head.hip: the
         logits never exist): hs_pad (B, T, d) on the GPU -> (ids (B, T) int32, prob (B, T) f32).  Only enqueues."""
         act = self._to_act(hs_pad)
         B, T, d = act.shape

@@ -5,8 +5,10 @@ row and output column for `<mask>`, and a self-attention WITHOUT the causal mask
 below the sentence's length.  Packing and `EmDecoderWeights` are the base class's (built with `vocab_size + 1`).
 
 `refine_device` is the decoding path: the K mask-predict passes of a ragged batch as one enqueued chain
-(`em_maskctc_refine`, csrc/maskctc.hip).  `forward` keeps the reference's signature and returns the (B, L, V + 1) scores: the
-same layers driven launch by launch from here, for parity tests and for callers that want the logits themselves.
+(`em_maskctc_refine`, csrc/maskctc.hip: K times the layer chain `em_dec_seq_nll` runs, csrc/dec_seq.hip, and the arg-max
+head of csrc/vocab_head.hip).  `forward` keeps the reference's signature and returns the (B, L, V + 1) scores: the same
+layers driven launch by launch from here - on purpose not through that chain, so that it stays the independent route the
+chain is checked against - for parity tests and for callers that want the logits themselves.
 """
 import ctypes as C
 

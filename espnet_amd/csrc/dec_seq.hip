@@ -7,7 +7,8 @@
 // The label-step path (csrc/search.hip decoder_step) feeds one position per call.  With the transcript known beforehand
 // everything but the two attentions is row-local, so the M = B * Lp rows go through the library's GEMMs at once; the
 // self-attention is csrc/lm_seq.hip's causal kernel (its token array is the key mask here) and the vocabulary head is
-// em_lm_head_nll.  What this file adds:
+// em_lm_head_nll (csrc/vocab_head.hip).  The embedding and the layers are em_host::dec_seq_rows, which the Mask-CTC refinement
+// (csrc/maskctc.hip) runs too, with the self-attention taken without the diagonal.  What this file adds:
 //   dec_seq_embed       x[r] = embed[tok[r]] * sqrt(d) + pe[r % Lp] for all rows in one launch;
 //   dec_seq_src_attn_*  source attention of Lp queries per sentence over a ragged memory of any length, a wave per 16
 //                       queries of one (sentence, head) walking the memory in tiles of 32 frames.  The label step's
@@ -20,7 +21,6 @@
 
 namespace {
 
-using em_host::Bump;
 using em_host::gemm;
 using em_host::LN_EPS;
 
@@ -184,24 +184,12 @@ __global__ __launch_bounds__(64) void dec_seq_src_attn_f32_kernel(const float* _
   if (lane < dk) out[lane] = acc / lsum;
 }
 
-struct SeqWs {
-  size_t x, xn, qkv, ctx, h, head, total;
-};
-SeqWs seq_layout(int dtype, const EmDecoderWeights* dw, size_t M) {
-  const size_t es = dtype == EM_BF16 ? 2 : 4;
-  Bump b;
-  SeqWs s;
-  s.x = b.take(M * dw->d * 4);
-  s.xn = b.take(M * dw->d * es);
-  s.qkv = b.take(M * 3 * dw->d * es);  // q | k | v of the self-attention, then the source attention's queries
-  s.ctx = b.take(M * dw->d * es);
-  s.h = b.take(M * dw->ff * es);
-  s.head = b.take(em_lm_head_nll_workspace_bytes(dtype, (int32_t)M, dw->vocab));
-  s.total = b.o;
-  return s;
-}
-
 using em_host::dec_seq_shape_ok;
+using em_host::DecSeqWs;
+
+DecSeqWs nll_layout(int dtype, const EmDecoderWeights* dw, int M) {
+  return em_host::dec_seq_layout(dtype, dw, (size_t)M, em_lm_head_nll_workspace_bytes(dtype, M, dw->vocab), false);
+}
 
 }  // namespace
 
@@ -244,9 +232,39 @@ extern "C" int em_dec_seq_src_attention(int dtype, const void* qs, const void* k
   return EM_OK;
 }
 
+// (declared in csrc/enc_host.h)
+int em_host::dec_seq_rows(int dtype, const EmDecoderWeights* dw, const void* mem_kv, const void* mem_vT, const int32_t* klens,
+                          const int32_t* mem_of, int Bm, const int32_t* tok, bool causal, const int32_t* self_x, int B, int Lp,
+                          int T, int Tpad, void* ws, const DecSeqWs& o, void* stream) {
+  const int M = B * Lp, V = dw->vocab, d = dw->d, ff = dw->ff, h = dw->heads;
+  const size_t es = dtype == EM_BF16 ? 2 : 4;
+  unsigned char* base = (unsigned char*)ws;
+  void *xn = base + o.xn, *qkv = base + o.qkv, *ctx = base + o.ctx, *hb = base + o.h;
+  void* qs = qkv;  // q | k | v are consumed before the source attention's queries are projected
+  float* xf = (float*)(base + o.x);
+  EM_TRY(em_dec_seq_embed_f32(dw->embed, dw->pe, tok, M, V, d, Lp, dw->pe_len, xf, stream));
+  for (int l = 0; l < dw->num_blocks; ++l) {
+    const EmDecoderLayer& q = dw->layers[l];
+    const unsigned char* kv = (const unsigned char*)mem_kv + (size_t)l * Bm * T * 2 * d * es;
+    const unsigned char* vT = (const unsigned char*)mem_vT + (size_t)l * Bm * d * Tpad * es;
+    EM_TRY(em_layernorm(dtype, xf, q.norm1_g, q.norm1_b, M, d, LN_EPS, xn, nullptr, stream));
+    EM_TRY(gemm(dtype, EM_EPI_STORE, xn, q.self_wqkv, qkv, q.self_bqkv, M, 3 * d, d, d, 3 * d, 1.f, stream));
+    EM_TRY((causal ? em_lm_causal_attention : em_dec_full_attention)(dtype, qkv, self_x, B, Lp, d, h, ctx, stream));
+    EM_TRY(gemm(dtype, EM_EPI_RESID_F32, ctx, q.self_wout, xf, q.self_bout, M, d, d, d, d, 1.f, stream));
+    EM_TRY(em_layernorm(dtype, xf, q.norm2_g, q.norm2_b, M, d, LN_EPS, xn, nullptr, stream));
+    EM_TRY(gemm(dtype, EM_EPI_STORE, xn, q.src_wq, qs, q.src_bq, M, d, d, d, d, 1.f, stream));
+    EM_TRY(em_dec_seq_src_attention(dtype, qs, kv, 2 * d, vT, klens, mem_of, B, Bm, Lp, d, h, T, Tpad, ctx, stream));
+    EM_TRY(gemm(dtype, EM_EPI_RESID_F32, ctx, q.src_wout, xf, q.src_bout, M, d, d, d, d, 1.f, stream));
+    EM_TRY(em_layernorm(dtype, xf, q.norm3_g, q.norm3_b, M, d, LN_EPS, xn, nullptr, stream));
+    EM_TRY(gemm(dtype, EM_EPI_RELU, xn, q.w1, hb, q.b1, M, ff, d, d, ff, 1.f, stream));
+    EM_TRY(gemm(dtype, EM_EPI_RESID_F32, hb, q.w2, xf, q.b2, M, d, ff, ff, d, 1.f, stream));
+  }
+  return EM_OK;
+}
+
 extern "C" size_t em_dec_seq_nll_workspace_bytes(int dtype, const EmDecoderWeights* dw, int32_t B, int32_t Lp) {
   if (!dw || (dtype != EM_BF16 && dtype != EM_F32) || !dec_seq_shape_ok(dw, B, Lp)) return 0;
-  return seq_layout(dtype, dw, (size_t)B * Lp).total;
+  return nll_layout(dtype, dw, B * Lp).total;
 }
 
 extern "C" int em_dec_seq_nll(int dtype, const EmDecoderWeights* dw, const void* mem_kv, const void* mem_vT,
@@ -258,31 +276,11 @@ extern "C" int em_dec_seq_nll(int dtype, const EmDecoderWeights* dw, const void*
   if (B <= 0 || Bm <= 0 || Lp <= 0 || T <= 0 || Tpad < T || Tpad % 32 != 0 || (!mem_of && Bm < B)) return EM_ERR_BAD_ARG;
   if (dw->d <= 0 || dw->heads <= 0 || dw->d % dw->heads || Lp > dw->pe_len) return EM_ERR_BAD_ARG;
   if (!dec_seq_shape_ok(dw, B, Lp)) return EM_ERR_UNSUPPORTED;
-  const int M = B * Lp, V = dw->vocab, d = dw->d, ff = dw->ff, h = dw->heads;
-  const size_t es = dtype == EM_BF16 ? 2 : 4;
-  const SeqWs o = seq_layout(dtype, dw, (size_t)M);
+  const int M = B * Lp;
+  const DecSeqWs o = nll_layout(dtype, dw, M);
   if (!ws || ws_bytes < o.total) return EM_ERR_WORKSPACE;
   unsigned char* base = (unsigned char*)ws;
-  void *xn = base + o.xn, *qkv = base + o.qkv, *ctx = base + o.ctx, *hb = base + o.h;
-  void* qs = qkv;  // q | k | v are consumed before the source attention's queries are projected
-  float* xf = (float*)(base + o.x);
-  EM_TRY(em_dec_seq_embed_f32(dw->embed, dw->pe, x, M, V, d, Lp, dw->pe_len, xf, stream));
-  for (int l = 0; l < dw->num_blocks; ++l) {
-    const EmDecoderLayer& q = dw->layers[l];
-    const unsigned char* kv = (const unsigned char*)mem_kv + (size_t)l * Bm * T * 2 * d * es;
-    const unsigned char* vT = (const unsigned char*)mem_vT + (size_t)l * Bm * d * Tpad * es;
-    EM_TRY(em_layernorm(dtype, xf, q.norm1_g, q.norm1_b, M, d, LN_EPS, xn, nullptr, stream));
-    EM_TRY(gemm(dtype, EM_EPI_STORE, xn, q.self_wqkv, qkv, q.self_bqkv, M, 3 * d, d, d, 3 * d, 1.f, stream));
-    EM_TRY(em_lm_causal_attention(dtype, qkv, keymask, B, Lp, d, h, ctx, stream));
-    EM_TRY(gemm(dtype, EM_EPI_RESID_F32, ctx, q.self_wout, xf, q.self_bout, M, d, d, d, d, 1.f, stream));
-    EM_TRY(em_layernorm(dtype, xf, q.norm2_g, q.norm2_b, M, d, LN_EPS, xn, nullptr, stream));
-    EM_TRY(gemm(dtype, EM_EPI_STORE, xn, q.src_wq, qs, q.src_bq, M, d, d, d, d, 1.f, stream));
-    EM_TRY(em_dec_seq_src_attention(dtype, qs, kv, 2 * d, vT, klens, mem_of, B, Bm, Lp, d, h, T, Tpad, ctx, stream));
-    EM_TRY(gemm(dtype, EM_EPI_RESID_F32, ctx, q.src_wout, xf, q.src_bout, M, d, d, d, d, 1.f, stream));
-    EM_TRY(em_layernorm(dtype, xf, q.norm3_g, q.norm3_b, M, d, LN_EPS, xn, nullptr, stream));
-    EM_TRY(gemm(dtype, EM_EPI_RELU, xn, q.w1, hb, q.b1, M, ff, d, d, ff, 1.f, stream));
-    EM_TRY(gemm(dtype, EM_EPI_RESID_F32, hb, q.w2, xf, q.b2, M, d, ff, ff, d, 1.f, stream));
-  }
-  return em_lm_head_nll(dtype, xf, dw->after_norm_g, dw->after_norm_b, dw->out_w, dw->out_b, target, M, V, d, nll,
-                        base + o.head, o.total - o.head, stream);
+  EM_TRY(em_host::dec_seq_rows(dtype, dw, mem_kv, mem_vT, klens, mem_of, Bm, x, true, keymask, B, Lp, T, Tpad, ws, o, stream));
+  return em_lm_head_nll(dtype, (const float*)(base + o.x), dw->after_norm_g, dw->after_norm_b, dw->out_w, dw->out_b, target,
+                        M, dw->vocab, dw->d, nll, base + o.head, o.total - o.head, stream);
 }

@@ -4,6 +4,8 @@
 //   - Bump: workspace layouts as one call per slot;
 //   - tpad256 / head_slab_bytes / project_heads / clear_head_slabs: the per-head operand format of the LDS-resident
 //     attention kernels (csrc/attention2.hip, csrc/abs_attn.hip): q, k [B][H][Tpad][64], V^T [B][H][64][Tpad], bf16;
+//   - dec_seq_shape_ok / DecSeqWs / dec_seq_rows: the attention decoder over whole sentences, for the transcript scorer
+//     (dec_seq.hip) and the Mask-CTC refinement (maskctc.hip);
 //   - rows_ffn_ok / head_operands_ok: the two rules that pick the 512-wide models' launch forms;
 //   - stream_*: what the two streaming launch sequences (streaming.hip, streaming_tf.hip) share - the FFN share rule and
 //     its set-up, the folded / launched context hand-over, the head of the per-operator scratch, LayerNorm + projection.
@@ -53,6 +55,32 @@ inline bool dec_seq_shape_ok(const EmDecoderWeights* dw, int B, int Lp) {
   const size_t wide = (size_t)(dw->ff > 3 * dw->d ? dw->ff : 3 * dw->d);
   return (size_t)B * Lp * wide * 4 < ((size_t)1 << 31);
 }
+// ... its workspace: the f32 residual rows x, then xn, qkv (q | k | v of the self-attention, then the source attention's
+// queries), ctx, h in the activation type, head_bytes for the caller's vocabulary head and, for the Mask-CTC refinement,
+// the head's two outputs s and a [M]
+struct DecSeqWs { size_t x, xn, qkv, ctx, h, head, s, a, total; };
+inline DecSeqWs dec_seq_layout(int dtype, const EmDecoderWeights* dw, size_t M, size_t head_bytes, bool refine) {
+  const size_t es = dtype == EM_BF16 ? 2 : 4;
+  Bump b;
+  DecSeqWs w;
+  w.x = b.take(M * dw->d * 4);
+  w.xn = b.take(M * dw->d * es);
+  w.qkv = b.take(M * 3 * dw->d * es);
+  w.ctx = b.take(M * dw->d * es);
+  w.h = b.take(M * dw->ff * es);
+  w.head = b.take(head_bytes);
+  w.s = w.a = b.o;
+  if (refine) w.s = b.take(M * 4), w.a = b.take(M * 4);
+  w.total = b.o;
+  return w;
+}
+// ... and its rows (csrc/dec_seq.hip): the embedding of tok [B][Lp] and the num_blocks layers over the M = B * Lp rows,
+// enqueue only; the f32 residual rows are left at ws + o.x for the caller's head.  The self-attention is causal with
+// self_x [B][Lp] as the key mask (em_lm_causal_attention) or, without the diagonal, over the first self_x[b] keys
+// (em_dec_full_attention); sentence b reads memory mem_of[b] (b itself without mem_of) of the Bm in mem_kv / mem_vT.
+int dec_seq_rows(int dtype, const EmDecoderWeights* dw, const void* mem_kv, const void* mem_vT, const int32_t* klens,
+                 const int32_t* mem_of, int Bm, const int32_t* tok, bool causal, const int32_t* self_x, int B, int Lp, int T,
+                 int Tpad, void* ws, const DecSeqWs& o, void* stream);
 
 // ---- per-head operands of the batch encoders' attention: Tpad frames per (utterance, head), a multiple of 256
 inline int tpad256(int T) { return (T + 255) / 256 * 256; }

@@ -5,10 +5,11 @@
 //
 // The search's step path (csrc/search.hip lm_step) feeds one position per call, ~6 launches per layer and position.  A
 // sentence that is known beforehand needs none of that chain: everything but the attention is row-local, so the
-// M = B * Lp rows go through the library's GEMMs at once, and two kernels here do the rest:
-//   lm_causal_attn_*  causal self-attention with the id-0 key mask, a wave per 16 queries of one (sentence, head);
-//   lm_head_nll_*     after_norm + vocabulary projection + log-sum-exp + the target's logit: the [M][V] logits never
-//                     exist, a row's running (max, sum-exp, target logit) is all that leaves a vocabulary tile.
+// M = B * Lp rows go through the library's GEMMs at once and through the vocabulary head that never materialises the logits
+// (em_lm_head_nll, csrc/vocab_head.hip).  What this file adds:
+//   lm_seq_input_norm  the input layer's LayerNorm + ReLU + position on all rows;
+//   lm_causal_attn_*   causal self-attention with the id-0 key mask, a wave per 16 queries of one (sentence, head); without
+//                      the diagonal it is the MLM decoder's self-attention (em_dec_full_attention).
 #include <math.h>
 
 #include "em_common.h"
@@ -191,219 +192,6 @@ __global__ __launch_bounds__(64) void lm_causal_attn_f32_kernel(const float* __r
   if (lane < dk) out[lane] = acc / lsum;
 }
 
-// ---- vocabulary head.  A row's record over a set of columns: the maximum logit, the sum of exp(logit - maximum) and the
-// target's logit (-inf while the target's column has not been met).
-struct Lse {
-  float m, s, t;
-};
-__device__ __forceinline__ Lse lse_merge(Lse a, Lse b) {
-  Lse r;
-  r.m = fmaxf(a.m, b.m);
-  r.t = fmaxf(a.t, b.t);
-  r.s = (a.m == -INFINITY ? 0.f : a.s * __expf(a.m - r.m)) + (b.m == -INFINITY ? 0.f : b.s * __expf(b.m - r.m));
-  return r;
-}
-__device__ __forceinline__ Lse lse_shfl_xor(Lse v, int o) {
-  return Lse{__shfl_xor(v.m, o, 64), __shfl_xor(v.s, o, 64), __shfl_xor(v.t, o, 64)};
-}
-
-constexpr int HEAD_ROWS = 64;    // rows of a workgroup: four 16-row MFMA tiles
-constexpr int HEAD_SLICE = 512;  // vocabulary columns of a workgroup: 8 tiles of 16 for each of its 4 waves
-constexpr int HEAD_DMAX = 1024;  // 64 rows of d + 8 bf16 stay inside the 160 KiB of LDS
-
-// bf16: workgroup (slice, row block) = 64 rows x 512 vocabulary columns.  The rows are normalised once (after_norm) into
-// LDS as bf16, rows padded by 16 bytes against bank conflicts; wave w then takes the column tiles w, w + 4, ... of the slice:
-// the weight fragment of a k-step comes straight from global memory and meets the four row tiles' fragments from LDS.  A lane
-// keeps the records of its 16 (row, column lr) pairs across tiles with ONE exp per logit; the 16 lanes of a row group, then the
-// four waves, merge once at the end and part[row][slice] receives the record.  Columns >= V count as -inf, rows >= M are zeros
-// and never stored.
-__global__ __launch_bounds__(256) void lm_head_nll_bf16_kernel(const float* __restrict__ x, const float* __restrict__ g,
-                                                               const float* __restrict__ be, const bf16* __restrict__ w,
-                                                               const float* __restrict__ bias, const int32_t* __restrict__ target,
-                                                               int M, int V, int d, float4* __restrict__ part) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char lm_head_smem[];
-  __shared__ float red[4][HEAD_ROWS][3];
-  bf16* xs = (bf16*)lm_head_smem;
-  const int ldx = d + 8;
-  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int lr = lane & 15, lg = lane >> 4;
-  const int r0 = blockIdx.y * HEAD_ROWS;
-  for (int i = 0; i < 16; ++i) {
-    const int rl = wave * 16 + i, r = r0 + rl;
-    bf16* dst = xs + (size_t)rl * ldx;
-    if (r < M) {
-      const float* xr = x + (size_t)r * d;
-      float s = 0.f;
-      for (int c = lane; c < d; c += 64) s += xr[c];
-      const float mean = wave_sum(s) / (float)d;
-      float q = 0.f;
-      for (int c = lane; c < d; c += 64) {
-        const float t = xr[c] - mean;
-        q += t * t;
-      }
-      const float rstd = 1.0f / sqrtf(wave_sum(q) / (float)d + LN_EPS);
-      for (int c = lane; c < d; c += 64) dst[c] = (bf16)((xr[c] - mean) * rstd * g[c] + be[c]);
-    } else {
-      for (int c = lane; c < d; c += 64) dst[c] = (bf16)0.f;
-    }
-  }
-  __syncthreads();
-  Lse rec[4][4];
-  int tg[4][4];
-#pragma unroll
-  for (int rt = 0; rt < 4; ++rt)
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int r = r0 + rt * 16 + lg * 4 + q;
-      rec[rt][q] = Lse{-INFINITY, 0.f, -INFINITY};
-      tg[rt][q] = r < M ? target[r] : -1;
-    }
-  const int vs0 = blockIdx.x * HEAD_SLICE;
-  const int nk = d / 32;
-  for (int t = wave; t < HEAD_SLICE / 16; t += 4) {
-    const int v0 = vs0 + t * 16;
-    if (v0 >= V) break;
-    const int col = v0 + lr;
-    const bf16* wrow = w + (size_t)min(col, V - 1) * d + lg * 8;
-    const bf16* arow = xs + (size_t)lr * ldx + lg * 8;
-    f32x4 acc[4];
-#pragma unroll
-    for (int rt = 0; rt < 4; ++rt) acc[rt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    for (int s = 0; s < nk; ++s) {
-      const bf16x8 bf = *(const bf16x8*)(wrow + s * 32);
-#pragma unroll
-      for (int rt = 0; rt < 4; ++rt)
-        acc[rt] = Mma<bf16>::mma(*(const bf16x8*)(arow + (size_t)rt * 16 * ldx + s * 32), bf, acc[rt]);
-    }
-    if (col < V) {
-      const float bb = bias[col];
-#pragma unroll
-      for (int rt = 0; rt < 4; ++rt)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const float val = acc[rt][q] + bb;
-          Lse& a = rec[rt][q];
-          if (col == tg[rt][q]) a.t = val;
-          const float dlt = val - a.m;  // a.m = -inf at first: dlt = +inf, e = 0, s = 1
-          const float e = __expf(-fabsf(dlt));
-          a.s = dlt > 0.f ? a.s * e + 1.f : a.s + e;
-          a.m = fmaxf(a.m, val);
-        }
-    }
-  }
-#pragma unroll
-  for (int rt = 0; rt < 4; ++rt)
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      Lse a = rec[rt][q];
-#pragma unroll
-      for (int o = 1; o < 16; o <<= 1) a = lse_merge(a, lse_shfl_xor(a, o));
-      if (lr == 0) {
-        float* dst = red[wave][rt * 16 + lg * 4 + q];
-        dst[0] = a.m;
-        dst[1] = a.s;
-        dst[2] = a.t;
-      }
-    }
-  __syncthreads();
-  if (threadIdx.x < HEAD_ROWS && r0 + (int)threadIdx.x < M) {
-    const int rl = threadIdx.x;
-    Lse a{red[0][rl][0], red[0][rl][1], red[0][rl][2]};
-#pragma unroll
-    for (int wv = 1; wv < 4; ++wv) a = lse_merge(a, Lse{red[wv][rl][0], red[wv][rl][1], red[wv][rl][2]});
-    part[(size_t)(r0 + rl) * gridDim.x + blockIdx.x] = make_float4(a.m, a.s, a.t, 0.f);
-  }
-}
-
-// nll[r] = logsumexp - target logit from the row's per-slice records; target < 0: 0.0
-__global__ void lm_head_merge_kernel(const float4* __restrict__ part, const int32_t* __restrict__ target, int M, int nsl,
-                                     float* __restrict__ nll) {
-  const int r = blockIdx.x * blockDim.x + threadIdx.x;
-  if (r >= M) return;
-  if (target[r] < 0) {
-    nll[r] = 0.f;
-    return;
-  }
-  Lse a{-INFINITY, 0.f, -INFINITY};
-  for (int i = 0; i < nsl; ++i) {
-    const float4 p = part[(size_t)r * nsl + i];
-    a = lse_merge(a, Lse{p.x, p.y, p.z});
-  }
-  nll[r] = (a.m + logf(a.s)) - a.t;
-}
-
-// f32 (parity path): a workgroup per row.  The normalised row sits in LDS, thread t walks the columns t, t + 256, ...
-__global__ __launch_bounds__(256) void lm_head_nll_f32_kernel(const float* __restrict__ x, const float* __restrict__ g,
-                                                              const float* __restrict__ be, const float* __restrict__ w,
-                                                              const float* __restrict__ bias, const int32_t* __restrict__ target,
-                                                              int V, int d, float* __restrict__ nll) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char lm_head_smem[];
-  __shared__ float red[4][3];
-  __shared__ float stat[2];
-  float* xn = (float*)lm_head_smem;
-  const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int tgt = target[r];
-  if (tgt < 0) {  // (workgroup-uniform)
-    if (tid == 0) nll[r] = 0.f;
-    return;
-  }
-  const float* xr = x + (size_t)r * d;
-  if (wave == 0) {
-    float s = 0.f;
-    for (int c = lane; c < d; c += 64) s += xr[c];
-    const float mean = wave_sum(s) / (float)d;
-    float q = 0.f;
-    for (int c = lane; c < d; c += 64) {
-      const float t = xr[c] - mean;
-      q += t * t;
-    }
-    const float rstd = 1.0f / sqrtf(wave_sum(q) / (float)d + LN_EPS);
-    if (lane == 0) {
-      stat[0] = mean;
-      stat[1] = rstd;
-    }
-  }
-  __syncthreads();
-  for (int c = tid; c < d; c += 256) xn[c] = (xr[c] - stat[0]) * stat[1] * g[c] + be[c];
-  __syncthreads();
-  Lse a{-INFINITY, 0.f, -INFINITY};
-  for (int v = tid; v < V; v += 256) {
-    const float* wr = w + (size_t)v * d;
-    float s = 0.f;
-    for (int c = 0; c < d; ++c) s += xn[c] * wr[c];
-    const float val = s + bias[v];
-    if (v == tgt) a.t = val;
-    const float mm = fmaxf(a.m, val);
-    a.s = a.s * expf(a.m - mm) + expf(val - mm);  // a.m = -inf: 0 * 0
-    a.m = mm;
-  }
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const Lse b = lse_shfl_xor(a, o);
-    Lse m;
-    m.m = fmaxf(a.m, b.m);
-    m.t = fmaxf(a.t, b.t);
-    m.s = (a.m == -INFINITY ? 0.f : a.s * expf(a.m - m.m)) + (b.m == -INFINITY ? 0.f : b.s * expf(b.m - m.m));
-    a = m;
-  }
-  if (lane == 0) {
-    red[wave][0] = a.m;
-    red[wave][1] = a.s;
-    red[wave][2] = a.t;
-  }
-  __syncthreads();
-  if (tid == 0) {
-    float mm = -INFINITY, t = -INFINITY, s = 0.f;
-    for (int i = 0; i < 4; ++i) mm = fmaxf(mm, red[i][0]), t = fmaxf(t, red[i][2]);
-    for (int i = 0; i < 4; ++i) s += red[i][0] == -INFINITY ? 0.f : red[i][1] * expf(red[i][0] - mm);
-    nll[r] = (mm + logf(s)) - t;
-  }
-}
-
-EmLdsCap head_cap;
-
-int head_slices(int V) { return em_cdiv(V, HEAD_SLICE); }
-
 struct SeqWs {
   size_t e, x, xn, qkv, ctx, h, head, total;
 };
@@ -467,38 +255,6 @@ extern "C" int em_lm_causal_attention(int dtype, const void* qkv, const int32_t*
 extern "C" int em_dec_full_attention(int dtype, const void* qkv, const int32_t* lens, int32_t B, int32_t Lp, int32_t d,
                                      int32_t heads, void* ctx, void* stream) {
   return seq_attention<false>(dtype, qkv, lens, B, Lp, d, heads, ctx, stream);
-}
-
-extern "C" size_t em_lm_head_nll_workspace_bytes(int dtype, int32_t M, int32_t V) {
-  if (dtype != EM_BF16 || M <= 0 || V <= 0) return 0;
-  return (size_t)M * head_slices(V) * sizeof(float4);
-}
-
-extern "C" int em_lm_head_nll(int dtype, const float* xrows, const float* norm_g, const float* norm_b, const void* out_w,
-                              const float* out_b, const int32_t* target, int32_t M, int32_t V, int32_t d, float* nll,
-                              void* ws, size_t ws_bytes, void* stream) {
-  if (!xrows || !norm_g || !norm_b || !out_w || !out_b || !target || !nll || M <= 0 || V <= 0 || d <= 0)
-    return EM_ERR_BAD_ARG;
-  hipStream_t s = (hipStream_t)stream;
-  if (dtype == EM_F32) {
-    if ((size_t)d * 4 > 64 * 1024) return EM_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(lm_head_nll_f32_kernel, dim3(M), dim3(256), (size_t)d * 4, s, xrows, norm_g, norm_b,
-                       (const float*)out_w, out_b, target, V, d, nll);
-    EM_CHECK_LAUNCH();
-    return EM_OK;
-  }
-  if (dtype != EM_BF16) return EM_ERR_BAD_ARG;
-  if (d % 32 || d > HEAD_DMAX) return EM_ERR_UNSUPPORTED;
-  const int nsl = head_slices(V);
-  if (em_cdiv(M, HEAD_ROWS) > 65535) return EM_ERR_UNSUPPORTED;
-  if (!ws || ws_bytes < em_lm_head_nll_workspace_bytes(dtype, M, V)) return EM_ERR_WORKSPACE;
-  const size_t lds = (size_t)HEAD_ROWS * (d + 8) * 2;
-  EM_TRY(em_raise_lds_cap((const void*)lm_head_nll_bf16_kernel, lds, &head_cap));
-  hipLaunchKernelGGL(lm_head_nll_bf16_kernel, dim3(nsl, em_cdiv(M, HEAD_ROWS)), dim3(256), lds, s, xrows, norm_g, norm_b,
-                     (const bf16*)out_w, out_b, target, M, V, d, (float4*)ws);
-  hipLaunchKernelGGL(lm_head_merge_kernel, dim3(em_cdiv(M, 256)), dim3(256), 0, s, (const float4*)ws, target, M, nsl, nll);
-  EM_CHECK_LAUNCH();
-  return EM_OK;
 }
 
 extern "C" size_t em_lm_seq_nll_workspace_bytes(int dtype, const EmLmWeights* lm, int32_t B, int32_t Lp) {

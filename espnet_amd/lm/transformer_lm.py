@@ -164,10 +164,10 @@ class TransformerLM(PackedModule, BatchScorerInterface):
 
     @torch.no_grad()
     def sequence_nll(self, x: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
-        """Per-token negative log-likelihoods of whole sentences in one enqueue (`em_lm_seq_nll`, csrc/lm_seq.hip): x
-        (B, Lp) integer input tokens with 0 behind a sentence's end, target (B, Lp) the token scored at every position,
-        negative where nothing is scored -> nll (B, Lp) f32, exactly 0.0 there.  What `forward` + cross-entropy
-        compute position by position, over all B * Lp rows at once."""
+        """Per-token negative log-likelihoods of whole sentences in one enqueue (`em_lm_seq_nll`, csrc/lm_seq.hip; its
+        head: csrc/vocab_head.hip): x (B, Lp) integer input tokens with 0 behind a sentence's end, target (B, Lp) the token
+        scored at every position, negative where nothing is scored -> nll (B, Lp) f32, exactly 0.0 there.  What `forward`
+        + cross-entropy compute position by position, over all B * Lp rows at once."""
         L.require_gpu(x, "x")
         L.require_gpu(target, "target")
         if x.dim() != 2 or x.shape != target.shape or x.numel() == 0:

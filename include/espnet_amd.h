@@ -1070,8 +1070,9 @@ int em_decoder_step(int dtype, const EmDecoderWeights* dw, const EmDecoderStepAr
  *   b->lm_logp [n][V] and the step's K/V (or ring-slot i % 3 recurrent state).  b->step must be NULL.     */
 int em_lm_step(int dtype, const EmSearchParams* p, const EmSearchBuffers* b, int32_t i, void* stream);
 
-/* ---- language model over whole sentences (csrc/lm_seq.hip): ESPnetLanguageModel.nll (espnet2/lm/espnet_model.py) for
- *      the TransformerLM, all M = B * Lp rows of a batch at once instead of one position per em_lm_step call.
+/* ---- language model over whole sentences (csrc/lm_seq.hip; em_lm_head_nll: csrc/vocab_head.hip): ESPnetLanguageModel.nll
+ *      (espnet2/lm/espnet_model.py) for the TransformerLM, all M = B * Lp rows of a batch at once instead of one position
+ *      per em_lm_step call.
  *   x      [B][Lp] i32  the input tokens [sos | text], 0 behind a sentence's end (the host writes it);
  *   target [B][Lp] i32  the token to score at every position ([text | eos]), negative where nothing is scored;
  *   nll    [B][Lp] f32  out: -log_softmax(lm(x)[b][j])[target[b][j]], exactly 0.0 where target < 0.
@@ -1085,7 +1086,7 @@ int em_lm_step(int dtype, const EmSearchParams* p, const EmSearchBuffers* b, int
  *     walked up to the diagonal, 4.5 KiB of LDS whatever Lp is; EM_F32: a plain kernel.
  *   em_lm_head_nll: nll[r] = logsumexp_v(y[r][v]) - y[r][target[r]] with y = LN(xrows; norm_g, norm_b, eps 1e-12) out_w^T
  *     + out_b, the [M][V] logits never stored: a row's running (maximum, sum of exponentials, target logit) per vocabulary
- *     tile is all that is kept.  xrows [M][d] f32, out_w [V][d] act, target[r] in [0, V) or negative (then nll[r] = 0.0); any
+ *     tile is all that is kept (the vocabulary head of csrc/vocab_head.hip with the target-logit record).  xrows [M][d] f32, out_w [V][d] act, target[r] in [0, V) or negative (then nll[r] = 0.0); any
  *     M and V.  EM_BF16: d % 32 == 0, d <= 1024 (EM_ERR_UNSUPPORTED otherwise), ws of em_lm_head_nll_workspace_bytes bytes
  *     (a smaller one: EM_ERR_WORKSPACE); EM_F32: no workspace (ws may be NULL).
  *   em_lm_seq_nll: the whole chain, enqueue only: embedding, input Linear + LayerNorm(1e-5) + ReLU (+ x sqrt(d) + pe[j]),
@@ -1141,7 +1142,8 @@ int em_dec_seq_nll(int dtype, const EmDecoderWeights* dw, const void* mem_kv, co
                    const int32_t* mem_of, const int32_t* x, const int32_t* keymask, const int32_t* target, int32_t B,
                    int32_t Bm, int32_t Lp, int32_t T, int32_t Tpad, float* nll, void* ws, size_t ws_bytes, void* stream);
 
-/* ---- Mask-CTC (csrc/maskctc.hip; em_dec_full_attention: csrc/lm_seq.hip): espnet2/asr/maskctc_model.py
+/* ---- Mask-CTC (csrc/maskctc.hip; em_dec_full_attention: csrc/lm_seq.hip; em_ctc_frame_top, em_lm_head_top1:
+ *      csrc/vocab_head.hip; the decoder pass: csrc/dec_seq.hip's chain): espnet2/asr/maskctc_model.py
  *      MaskCTCInference.forward with espnet2/asr/decoder/mlm_decoder.py MLMDecoder - greedy CTC with the frames' winning
  *      probabilities, collapse with confidence, threshold, then K dense passes of the MLM decoder with the easiest-first
  *      fill, for a ragged batch and without a read-back between the passes.  The decoder's tables have V + 1 rows
@@ -1151,7 +1153,7 @@ int em_dec_seq_nll(int dtype, const EmDecoderWeights* dw, const void* mem_kv, co
  *     The [M][V] logits are never stored: a (max, arg-max, sum-exp) record per row and 512-column slice, merged.  EM_BF16:
  *     MFMA, d % 32 == 0, d <= 1024 (EM_ERR_UNSUPPORTED otherwise), ws of em_ctc_frame_top_workspace_bytes bytes
  *     (EM_ERR_WORKSPACE when smaller); EM_F32: a plain kernel, d <= 16 384, no workspace (the query returns 0).
- *   em_lm_head_top1: em_lm_head_nll's twin: y = LN(xrows; norm_g, norm_b, eps 1e-12) out_w^T + out_b over V columns,
+ *   em_lm_head_top1: em_lm_head_nll's kernels with the arg-max record (as em_ctc_frame_top, behind the LayerNorm): y = LN(xrows; norm_g, norm_b, eps 1e-12) out_w^T + out_b over V columns,
  *     smax[r] = max_v y[r][v], amax[r] = its lowest arg-max; same shapes, workspace rule and refusals as em_ctc_frame_top.
  *   em_maskctc_collapse: ids / prob [B][T] as em_ctc_frame_top leaves them, olens [B] the valid frames.  The frames
  *     t < olens[b] are cut into maximal runs of equal id; every run whose id != blank is one token with the confidence

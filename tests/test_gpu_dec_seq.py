@@ -1,4 +1,4 @@
-"""Whole-transcript scoring with the attention decoder on the device (csrc/dec_seq.hip): the source-attention kernel alone,
+"""Whole-transcript scoring with the attention decoder on the device (csrc/dec_seq.hip, the head: csrc/vocab_head.hip): the source-attention kernel alone,
 the chain `em_dec_seq_nll` through TransformerDecoder.sequence_nll / ESPnetASRModel.nll / batchify_nll /
 Speech2Text.batch_nll, against the float64 restatement (tests/dec_seq_ref.py) on the weights and memories as the device
 holds them.

@@ -1,4 +1,4 @@
-"""Whole-sentence scoring with the language model on the device (csrc/lm_seq.hip): the two new kernels alone, the chain
+"""Whole-sentence scoring with the language model on the device (csrc/lm_seq.hip, the head: csrc/vocab_head.hip): the two kernels alone, the chain
 `em_lm_seq_nll` through TransformerLM.sequence_nll / ESPnetLanguageModel.nll / batchify_nll, the recurrent LM's route and
 the perplexity tool, against the float64 restatement (tests/lm_seq_ref.py) on the weights as the device holds them.
 

@@ -1,4 +1,5 @@
-"""Mask-CTC decoding on the device (csrc/maskctc.hip, em_dec_full_attention in csrc/lm_seq.hip): the primitives, the
+"""Mask-CTC decoding on the device (csrc/maskctc.hip, em_dec_full_attention in csrc/lm_seq.hip, both heads in
+csrc/vocab_head.hip, the decoder pass csrc/dec_seq.hip's chain): the primitives, the
 integer logic of collapse and fill, the refinement chain pass by pass, independence of the batch and of the workspace,
 and MaskCTCModel / Speech2Text / the command line, against the float64 restatement (tests/maskctc_ref.py) on the weights
 and inputs as the device holds them.

@@ -5,7 +5,8 @@ bf16: 64 ragged transcripts of 40-80 tokens against 64 encoder memories of T = 2
 
 Reports, in one process on one GPU (medians with min and max of `--reps` runs after `--warmup`, each run timed with device
 events around the whole call and a synchronisation after it):
-  * seq_nll_ms    ESPnetASRModel.nll: memory projection + all B * Lp rows in one enqueue (em_dec_seq_nll, csrc/dec_seq.hip);
+  * seq_nll_ms    ESPnetASRModel.nll: memory projection + all B * Lp rows in one enqueue (em_dec_seq_nll, csrc/dec_seq.hip;
+                  head: csrc/vocab_head.hip);
   * step_route_ms TransformerDecoder.forward position by position through the label step's kernels, then log-softmax, a
                   gather and the sum (the only whole-sequence route before em_dec_seq_nll);
   * torch_ms      an eager-torch restatement on the same GPU and the same bf16 weights (batched matmuls, masked softmax).

@@ -5,7 +5,8 @@
 
 Reports, in one process on one GPU (medians with min and max of `--reps` runs after `--warmup`, each run timed with device
 events around the whole call and a synchronisation after it):
-  * seq_nll_ms    ESPnetLanguageModel.nll: all B * Lp rows in one enqueue (em_lm_seq_nll, csrc/lm_seq.hip);
+  * seq_nll_ms    ESPnetLanguageModel.nll: all B * Lp rows in one enqueue (em_lm_seq_nll, csrc/lm_seq.hip;
+                  head: csrc/vocab_head.hip);
   * step_route_ms TransformerLM.forward position by position through the search's step kernels, then log-softmax and a
                   gather (the only whole-sequence route before em_lm_seq_nll);
   * torch_ms      an eager-torch restatement on the same GPU and the same bf16 weights (batched matmuls, masked softmax).

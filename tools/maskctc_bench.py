@@ -7,7 +7,7 @@ The memories are synthetic, built so that the greedy CTC pass yields 40-80 token
 fall below the threshold 0.99 (frame t of a token's run is alpha_t times the unit-norm CTC row of its label: alpha 20 gives
 a probability of 1 - 1e-5, alpha 9 one of about 0.6; the achieved share is reported).  Reports, in one process on one GPU
 (medians with min and max of `--reps` runs after `--warmup`, each run between device events around the enqueued region):
-  * ctc_stage_ms     em_ctc_frame_top + em_maskctc_collapse;
+  * ctc_stage_ms     em_ctc_frame_top (csrc/vocab_head.hip) + em_maskctc_collapse;
   * memory_ms        em_decoder_memory: the source attention's K | V and V^T of all blocks, once per batch;
   * refine_ms        em_maskctc_refine: the K passes and fills as one enqueued chain (memory projected beforehand);
   * whole_call_ms    MaskCTCModel.decode_maskctc_device: the three above with the one read-back of the counts;
