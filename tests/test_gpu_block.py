@@ -8,17 +8,21 @@ rounding.  Tolerances: 4e-3 of the output scale for the f32 residual stream (sam
 test_ffn_fused_bf16), 2e-2 for bf16 outputs (one bf16 ulp is 0.8 %).  Then the whole encoder: fused vs the
 per-operator launch sequence on the reference goldens.  The attention phase of block<ATT|C> is also observed directly
 (test_block_att_c_attention_parity): per element against the float64 reference and budget of tests/attention_ref.py.
+The row-local phases (LayerNorm, the two FFNs, linear_out, pointwise_conv1 + GLU, the depthwise conv + Swish,
+pointwise_conv2, the q / k / v projections) are each observed on their own as well (test_block_*_parity): per element against
+the float64 reference of tests/block_ref.py, whose budget follows the roundings and is zero behind an unambiguous one.
 """
 import math
 
 import pytest
 import torch
-import torch.nn.functional as F
 
 from espnet_amd import lib as L
 from espnet_amd.asr.encoder.conformer_encoder import pack_k_units, pack_w1, pack_w2
 from oracle import conformer as oc
 from tests import attention_ref as ar
+from tests import block_ref as br
+from tests.block_ref import Layer, group, ln, q, rnd
 
 pytestmark = pytest.mark.gpu
 BF = torch.bfloat16
@@ -47,33 +51,11 @@ def _release_kept_tensors():
     _KEEP.clear()
 
 
-def rnd(*shape, seed=0, scale=1.0):
-    g = torch.Generator().manual_seed(seed)
-    return torch.randn(*shape, generator=g) * scale
-
-
-def q(t):
-    return t.to(BF).to(torch.float32)
-
-
 def assert_close(got, ref, tol, what=""):
     got, ref = got.float().cpu(), ref.float().cpu()
     scale = max(ref.abs().max().item(), 1e-6)
     err = (got - ref).abs().max().item()
     assert err <= tol * scale, f"{what}: max err {err:.3e} vs scale {scale:.3e} (tol {tol})"
-
-
-def ln(x, g, b):
-    return F.layer_norm(x, (D,), g, b, 1e-12)
-
-
-def group(*vecs):
-    v = torch.cat([t.reshape(-1).float() for t in vecs])
-    return F.pad(v, (0, G - v.numel()))
-
-
-def pad_ff(b):
-    return F.pad(b, (0, 1024 - b.numel()))
 
 
 def tpad(T):
@@ -122,62 +104,6 @@ def test_relpos_attention2(lib, T, klens):
 
 
 # ------------------------------------------------------------------------------------------ block kernels
-class Layer:
-    """Random weights of one EncoderLayer (bf16-rounded matrices, f32 vectors) + its host packing."""
-
-    def __init__(self, seed, ff):
-        s = iter(range(seed, seed + 100))
-        self.ff = ff
-        w = lambda n, k: q(rnd(n, k, seed=next(s), scale=k ** -0.5))
-        vb = lambda n: rnd(n, seed=next(s), scale=0.1)
-        lng = lambda: (1 + 0.1 * rnd(D, seed=next(s)), 0.1 * rnd(D, seed=next(s)))
-        self.ln_mac, self.ln_mha, self.ln_conv, self.ln_ff, self.ln_final = lng(), lng(), lng(), lng(), lng()
-        self.ffm_w1, self.ffm_b1, self.ffm_w2, self.ffm_b2 = w(ff, D), vb(ff), w(D, ff), vb(D)
-        self.ff_w1, self.ff_b1, self.ff_w2, self.ff_b2 = w(ff, D), vb(ff), w(D, ff), vb(D)
-        self.wqkv, self.bqkv = w(3 * D, D), vb(3 * D)
-        self.wout, self.bout = w(D, D), vb(D)
-        self.pw1, self.pw1_b = w(2 * D, D), vb(2 * D)
-        self.dw_w, self.dw_b = rnd(31, D, seed=next(s), scale=0.25), vb(D)  # [k][d], BatchNorm already folded
-        self.pw2, self.pw2_b = w(D, D), vb(D)
-
-    # torch fp32 restatements with the bf16 rounding points of the bf16 path
-    def part_a(self, x):
-        xn = q(ln(x, *self.ln_mac))
-        x = x + 0.5 * (q(oc.swish(xn @ self.ffm_w1.t() + self.ffm_b1)) @ self.ffm_w2.t() + self.ffm_b2)
-        qkv = q(ln(x, *self.ln_mha)) @ self.wqkv.t() + self.bqkv
-        return x, qkv
-
-    def part_c(self, x, ctx):
-        x = x + ctx @ self.wout.t() + self.bout
-        y = q(ln(x, *self.ln_conv)) @ self.pw1.t() + self.pw1_b
-        return x, y[:, :D] * torch.sigmoid(y[:, D:])
-
-    def part_d(self, x, glu, B, T, tlens=None):
-        g3 = q(glu).reshape(B, T, D).clone()
-        if tlens is not None:
-            for b, n in enumerate(tlens):
-                g3[b, n:] = 0
-        conv = F.conv1d(g3.transpose(1, 2), self.dw_w.t().reshape(D, 1, 31), self.dw_b, padding=15, groups=D)
-        c = q(oc.swish(conv.transpose(1, 2).reshape(B * T, D)))
-        x = x + c @ self.pw2.t() + self.pw2_b
-        xn = q(ln(x, *self.ln_ff))
-        x = x + 0.5 * (q(oc.swish(xn @ self.ff_w1.t() + self.ff_b1)) @ self.ff_w2.t() + self.ff_b2)
-        return ln(x, *self.ln_final)
-
-    def a_groups(self):
-        return [group(*self.ln_mac, pad_ff(self.ffm_b1), self.ffm_b2), group(*self.ln_mha, self.bqkv)]
-
-    def d_groups(self):
-        return [group(self.pw2_b, *self.ln_ff), group(pad_ff(self.ff_b1), self.ff_b2, *self.ln_final)]
-
-    def perm(self):
-        return torch.cat([torch.cat([torch.arange(64 * j, 64 * j + 64), torch.arange(D + 64 * j, D + 64 * j + 64)])
-                          for j in range(4)])
-
-    def c_group(self):
-        return group(self.bout, *self.ln_conv, self.pw1_b[self.perm()])
-
-
 def block_args(B, T, ff, **ptrs):
     a = L.EmBlockArgs(B=B, T=T, Tpad=tpad(T), d=D, ff=ff, kernel=31, eps=1e-12)
     for k, v in ptrs.items():
@@ -578,3 +504,134 @@ def test_block_repeatable_under_load(lib):
         else:
             for g0, g1 in zip(first, got):
                 assert torch.equal(g0, g1), f"run {it} differs from run 0"
+
+
+# ------------------------------------------------------------------------------------------ one phase at a time, per element
+def launch_probe(lib, p, kv_frag=0):
+    """The launch of a tests/block_ref.py probe -> {output name: [B * T][256] tensor}, q / k / v unpacked."""
+    B, T, ff, Tp = p.B, p.T, p.ff, tpad(p.T)
+    bf = lambda t: dev(t.to(BF))
+    ptrs, out = dict(x=dev(p.x0.clone())), {}
+    if p.mode == "C":
+        out["glu"] = torch.zeros(B * T, D, dtype=BF, device="cuda")
+        ptrs.update(ctx=bf(p.ctx), glu=out["glu"], wout=bf(pack_k_units(p.l0.wout)), pw1f=bf(pack_k_units(p.l0.pw1[p.l0.perm()])),
+                    params=dev(p.l0.c_group()))
+        mode = L.EM_BLOCK_C
+    if p.mode == "ATTC":
+        # one valid key per utterance, v[b][0] = p.v0[b]; everything past it is masked: NaN keys (masked by select), finite junk
+        # in V^T (0 * x), random queries and position table
+        qh = torch.full((B, H, Tp, 64), float("nan"), dtype=BF)
+        kh = torch.full((B, H, Tp, 64), float("nan"), dtype=BF)
+        vt = torch.zeros(B, H, 64, Tp, dtype=BF)
+        qh[:, :, :T] = rnd(B, H, T, 64, seed=p.seed + 600).to(BF)
+        kh[:, :, :1] = rnd(B, H, 1, 64, seed=p.seed + 601).to(BF)
+        vt[:, :, :, :T] = rnd(B, H, 64, T, seed=p.seed + 602).to(BF)
+        vt[:, :, :, 0] = p.v0.reshape(B, H, 64).to(BF)
+        ppk, npg = packed_pos(lib, bf(rnd(2 * T - 1, ar.LB * D, seed=p.seed + 603)), T, ar.LB)
+        out["glu"] = torch.zeros(B * T, D, dtype=BF, device="cuda")
+        ptrs.update(glu=out["glu"], qh=dev(qh), kh=dev(k_to_frag(kh)), vt=dev(vt_to_frag(vt)), wout=bf(pack_k_units(p.l0.wout)),
+                    pw1f=bf(pack_k_units(p.l0.pw1[p.l0.perm()])), params=dev(p.l0.c_group()),
+                    pos_u=dev(rnd(H, 64, seed=p.seed + 604, scale=0.3)), pos_v=dev(rnd(H, 64, seed=p.seed + 605, scale=0.3)),
+                    klens=dev(torch.ones(B, dtype=torch.int32)))
+        mode, ff, kv_frag = L.EM_BLOCK_ATT | L.EM_BLOCK_C, 256, 1  # (the C part has no ff; the fused launch is built at 256)
+    if p.mode in ("CDF", "CDA"):  # folded: x is read only (a neighbour workgroup reads these rows as its halo)
+        ptrs.update(ctx=bf(p.ctx), wout=bf(pack_k_units(p.l0.wout)), pw1f=bf(pack_k_units(p.l0.pw1[p.l0.perm()])), params_c=dev(p.l0.c_group()))
+    elif p.mode in ("DF", "DA"):
+        ptrs.update(glu=bf(p.glu))
+    if p.mode in ("DF", "DA", "CDF", "CDA"):
+        ptrs.update(pw2=bf(pack_k_units(p.l0.pw2)), ff_w1=bf(pack_w1(p.l0.ff_w1)), ff_w2=bf(pack_w2(p.l0.ff_w2)),
+                    dw_w=dev(p.l0.dw_w), dw_b=dev(p.l0.dw_b), tlens=dev(torch.tensor(p.tlens, dtype=torch.int32)) if p.tlens else None)
+    if p.mode in ("DF", "CDF"):
+        out["enc_out"] = torch.zeros(B * T, D, dtype=torch.float32, device="cuda")
+        out["enc_act"] = torch.zeros(B * T, D, dtype=BF, device="cuda")
+        ptrs.update(enc_out=out["enc_out"], enc_act=out["enc_act"],
+                    params=dev(torch.cat(p.l0.d_groups() + [group(p.ag, p.ab), torch.zeros(G)])))
+        mode = L.EM_BLOCK_D | L.EM_BLOCK_FINAL | (L.EM_BLOCK_C if p.mode == "CDF" else 0)
+    if p.mode in ("A", "DA", "CDA"):
+        qh, kh = (torch.zeros(B, H, Tp, 64, dtype=BF, device="cuda") for _ in range(2))
+        vt = torch.zeros(B, H, 64, Tp, dtype=BF, device="cuda")
+        ptrs.update(qh=qh, kh=kh, vt=vt, ffm_w1=bf(pack_w1(p.l1.ffm_w1)), ffm_w2=bf(pack_w2(p.l1.ffm_w2)), wqkv=bf(pack_k_units(p.l1.wqkv)),
+                    params=dev(torch.cat((p.l0.d_groups() if p.mode != "A" else []) + p.l1.a_groups())))
+        mode = L.EM_BLOCK_A | (L.EM_BLOCK_D if p.mode != "A" else 0) | (L.EM_BLOCK_C if p.mode == "CDA" else 0)
+        if p.mode == "CDA":
+            ptrs["x_out"] = torch.full((B * T, D), float("nan"), device="cuda")
+    a = block_args(B, T, ff, **ptrs)
+    a.kv_frag = kv_frag
+    if p.mode == "ATTC":
+        a.pos, a.ldp = ppk.data_ptr() + 4 * npg * 2048, npg  # (the middle block of the table)
+    L.check(lib.em_conformer_block_fused(mode, a, L.current_stream_ptr()), f"block<{p.mode}> probe {p.name}")
+    if p.mode in ("CDF", "CDA"):
+        assert torch.equal(ptrs["x"].cpu(), p.x0), "the folded kernel must not write its input residual"
+    if p.mode not in ("DF", "CDF"):
+        out["x"] = ptrs["x_out" if p.mode == "CDA" else "x"]
+    if p.mode in ("A", "DA", "CDA"):
+        if kv_frag:
+            kh, vt = k_from_frag(kh.cpu()), vt_from_frag(vt.cpu())
+        assert torch.isfinite(vt.float()).all(), "V^T columns >= T must be finite"
+        out.update(q=split_heads(qh, B, T), k=split_heads(kh, B, T), v=vt[:, :, :, :T].permute(0, 3, 1, 2).reshape(B * T, D))
+    return out
+
+
+def hold_probe(lib, name, B, T, tlens, ff, kv_frag=0):
+    """Every output of the probe inside the budget, per element; the stage shared behind x takes the x the device wrote."""
+    p = br.probe_for(name, B, T, tlens, ff)
+    got = launch_probe(lib, p, kv_frag)
+    ref = p.run(br.RefOps(), mid=got.get("x"))
+    for o in ref:
+        r = br.assert_in_budget(got[o], ref[o], p, o, f"block<{p.mode}> B={B} T={T} ff={ff} tlens={tlens} kv_frag={kv_frag}")
+        print(f"PARITY block<{p.mode}> {name} {o} B={B} T={T} ff={ff} masked={tlens is not None} kv_frag={kv_frag}: err / budget {r:.3f}")
+
+
+@pytest.mark.parametrize("kv_frag", [0, 1])
+@pytest.mark.parametrize("B,T,tlens,ff", br.UNMASKED_PARAMS, ids=br.UNMASKED_IDS)
+def test_block_a_parity(lib, B, T, tlens, ff, kv_frag):
+    """block<A>, two probes in one launch.  x behind the macaron FFN: the input rows are LN-clean at norm_macaron, the hidden
+    activation's rounding is the one ambiguous level.  q / k / v: of norm_mha of the x the launch wrote, both K / V^T layouts.
+    (Worst err / budget measured on an MI355X: block_ref.GPU_WORST.)"""
+    hold_probe(lib, "a", B, T, tlens, ff, kv_frag)
+
+
+@pytest.mark.parametrize("B,T,tlens,ff", br.UNMASKED_PARAMS, ids=br.UNMASKED_IDS)
+def test_block_c_parity(lib, B, T, tlens, ff):
+    """block<C>.  x + linear_out(ctx): float32, no rounding point - the accumulate term alone, on every element.  glu: of
+    norm_conv of the x the launch wrote.  Measured on an MI355X, worst err / budget: x 0.098, glu 0.989."""
+    hold_probe(lib, "c", B, T, tlens, ff)
+
+
+@pytest.mark.parametrize("name", ["df_conv", "df_ffn"])
+@pytest.mark.parametrize("B,T,tlens,ff", br.CASE_PARAMS, ids=br.CASE_IDS)
+def test_block_d_final_parity(lib, B, T, tlens, ff, name):
+    """block<D|FINAL>, enc_out (f32) and enc_act (bf16).  df_conv: ff_w2 = 0, so the conv module is seen through two float32
+    LayerNorms, the conv output's rounding the one ambiguous level; frames at and past tlens hold junk of magnitude 3.
+    df_ffn: glu = 0 on the valid frames and dw_b = 0, so the conv output is exactly zero and the feed-forward module runs
+    on x + pw2 bias, rows LN-clean at norm_ff.
+    (Worst err / budget measured on an MI355X: block_ref.GPU_WORST.)"""
+    hold_probe(lib, name, B, T, tlens, ff)
+
+
+@pytest.mark.parametrize("name", ["da_conv", "da_ffn", "da_mac"])
+@pytest.mark.parametrize("B,T,tlens,ff", br.CASE_PARAMS, ids=br.CASE_IDS)
+def test_block_da_parity(lib, B, T, tlens, ff, name):
+    """block<D|A>.  da_conv, da_ffn: the two D probes with the macaron w2 = 0, x shows the D part; da_mac: the D part exact
+    (zero conv, ff_w2 = 0, norm_final gain 0), the macaron FFN live.  q / k / v of the x the launch wrote, every time.
+    (Worst err / budget measured on an MI355X: block_ref.GPU_WORST.)"""
+    hold_probe(lib, name, B, T, tlens, ff)
+
+
+@pytest.mark.parametrize("name", ["cda_conv", "cda_ffn", "cdf_conv", "cdf_ffn"])
+@pytest.mark.parametrize("B,T,tlens,ff", br.CASE_PARAMS, ids=br.CASE_IDS)
+def test_block_folded_parity(lib, B, T, tlens, ff, name):
+    """block<C|D|A> and block<C|D|FINAL>, ctx = 0.  conv probes: pointwise_conv1's value half is the identity and its gate
+    sigmoid(30) = 1, so the GLU rows that reach the conv tile - own rows and halo rows - are q(norm_conv(x + bout)) exactly,
+    every row LN-clean; ffn probes: pointwise_conv1 = 0, the conv output exactly zero, rows LN-clean at norm_ff.  x comes back
+    untouched, x_out (NaN before the launch) fully written.
+    (Worst err / budget measured on an MI355X: block_ref.GPU_WORST.)"""
+    hold_probe(lib, name, B, T, tlens, ff)
+
+
+@pytest.mark.parametrize("B,T,tlens,ff", br.UNMASKED_PARAMS, ids=br.UNMASKED_IDS)
+def test_block_att_c_rowlocal_parity(lib, B, T, tlens, ff):
+    """block<ATT|C>, every utterance with one valid key: the attention phase hands v[b][0] to linear_out exactly, in every
+    row, so the row-local phases of the fused launch are held as block<C>'s: x + linear_out(ctx) on the accumulate term alone,
+    glu of norm_conv of the x the launch wrote.  (Worst err / budget measured on an MI355X: block_ref.GPU_WORST.)"""
+    hold_probe(lib, "attc", B, T, tlens, ff)
