@@ -98,6 +98,31 @@ class CTC(PackedModule):
                                      L.ptr(ids), L.ptr(prob), L.ptr(ws), need, L.current_stream_ptr()), "em_ctc_frame_top")
         return ids, prob
 
+    def frame_topk_device(self, hs_pad: torch.Tensor, K: int, blank: int = 0):
+        """Per frame the K most probable tokens of `log_softmax(hs_pad)` (`em_ctc_frame_topk`, csrc/ctc_tsync.hip): hs_pad
+        (B, T, d) on the GPU -> (cand_id (B, T, K) int32, cand_lp (B, T, K) f32 descending, ties to the lower id, blank_lp
+        (B, T) f32).  What the time-synchronous search reads (espnet_amd/nets/beam_search_timesync.py).  Only enqueues."""
+        return self.topk_log_probs(self.log_softmax(hs_pad), K, blank)
+
+    @staticmethod
+    def topk_log_probs(lp: torch.Tensor, K: int, blank: int = 0):
+        """`em_ctc_frame_topk` on given log-probabilities lp (..., V) f32 on the device."""
+        L.require_gpu(lp, "lp")
+        if lp.dtype != torch.float32:
+            raise ValueError("lp must be float32")
+        lp = lp.contiguous()
+        V = int(lp.shape[-1])
+        lead = tuple(lp.shape[:-1])
+        M = lp.numel() // V if V else 0
+        if not 1 <= int(K) <= V:
+            raise ValueError(f"K must lie in [1, {V}], not {K}")
+        cand_id = torch.empty(lead + (int(K),), dtype=torch.int32, device=lp.device)
+        cand_lp = torch.empty(lead + (int(K),), dtype=torch.float32, device=lp.device)
+        blank_lp = torch.empty(lead, dtype=torch.float32, device=lp.device)
+        L.check(L.load().em_ctc_frame_topk(L.ptr(lp), M, V, int(K), int(blank), L.ptr(cand_id), L.ptr(cand_lp), L.ptr(blank_lp),
+                                           L.current_stream_ptr()), "em_ctc_frame_topk")
+        return cand_id, cand_lp, blank_lp
+
     # ------------------------------------------------------------------ forced alignment (csrc/ctc_align.hip)
     @staticmethod
     def check_alignable(olens, targets, blank, vocab):

@@ -11,6 +11,8 @@ Decoding modes
     blank/sos/eos (asr_inference.py:574-575) — bit-exact integer contract, fully on device.
   * a transducer model (decoder: transducer): BeamSearchTransducer built from `transducer_conf` and `beam_size` -
     the fused greedy walk or the default beam search, espnet_amd/asr/transducer/.
+  * time_sync=True with ctc_weight=1.0: the time-synchronous CTC prefix beam search with n-gram fusion
+    (BeamSearchTimeSync, espnet_amd/nets/beam_search_timesync.py; csrc/ctc_tsync.hip).
   * otherwise: label-synchronous joint CTC/attention beam search (BatchBeamSearch semantics,
     espnet2/legacy/nets/batch_beam_search.py) — see espnet_amd/nets/.
 The log markers "speech length: N" and "best hypo: ..." that utils/calculate_rtf.py parses are kept.
@@ -68,7 +70,7 @@ class Speech2Text:
                  dtype: str = "float32", beam_size: int = 20, ctc_weight: float = 0.5,
                  lm_weight: float = 1.0, ngram_weight: float = 0.9, penalty: float = 0.0,
                  nbest: int = 1, normalize_length: bool = False, streaming: bool = False,
-                 ctc_greedy: bool = False, **unsupported):
+                 ctc_greedy: bool = False, time_sync: bool = False, **unsupported):
         for k, v in unsupported.items():
             if v not in (None, False, {}, [], 0.99, 5, -1, ["Linear"], "qint8"):
                 raise NotImplementedError(f"Speech2Text({k}={v!r}) is outside the MI355X hot path")
@@ -76,6 +78,15 @@ class Speech2Text:
             raise NotImplementedError("streaming=True (use Speech2TextStreaming)")
         if not str(device).startswith("cuda"):
             raise RuntimeError("espnet_amd.Speech2Text runs on an MI355X only (device='cuda'); no CPU fallback")
+        if time_sync:  # asr_inference.py: BeamSearchTimeSync in place of the label-synchronous search
+            if ctc_greedy:
+                raise ValueError("time_sync=True and ctc_greedy=True are two different decoders: choose one")
+            if float(ctc_weight) != 1.0:
+                raise NotImplementedError(f"time_sync=True with ctc_weight={ctc_weight}: the attention decoder is not scored "
+                                          "time-synchronously on the MI355X path; pass ctc_weight=1.0")
+            if lm_train_config is not None:
+                raise NotImplementedError("time_sync=True with lm_train_config: a neural LM is not scored time-synchronously "
+                                          "on the MI355X path; an n-gram (ngram_file) is")
         # the reference's `dtype` is the model dtype; here it selects the MFMA mode
         dtype = resolve_dtype(dtype)
         asr_model, asr_train_args = ASRTask.build_model_from_file(
@@ -87,6 +98,10 @@ class Speech2Text:
         self.maxlenratio, self.minlenratio, self.nbest = maxlenratio, minlenratio, nbest
         self.normalize_length = normalize_length
         self.ctc_greedy = ctc_greedy
+        self.time_sync = bool(time_sync)
+        if time_sync and asr_model.use_transducer_decoder:
+            raise NotImplementedError("time_sync=True with a transducer model: the time-synchronous search is CTC's "
+                                      "(the transducer has its own searches: transducer_conf)")
         token_list = asr_model.token_list
         if token_type is None:
             token_type = getattr(asr_train_args, "token_type", None)
@@ -97,9 +112,23 @@ class Speech2Text:
         else:
             self.tokenizer = build_tokenizer(token_type=token_type, bpemodel=bpemodel)
         self.converter = TokenIDConverter(token_list=token_list)
-        self.beam_search = self.beam_search_transducer = None
+        self.beam_search = self.beam_search_transducer = self.beam_search_timesync = None
         self.lm = self.lm_model = self.ngram = None
-        if asr_model.use_transducer_decoder:  # asr_inference.py: BeamSearchTransducer in place of the joint search
+        if time_sync:
+            from espnet_amd.nets.beam_search_timesync import BeamSearchTimeSync
+            from espnet_amd.nets.scorers.ctc import CTCPrefixScorer
+
+            if ngram_file is not None:
+                from espnet_amd.nets.scorers.ngram import NgramFullScorer, NgramPartScorer
+
+                self.ngram = (NgramFullScorer if ngram_scorer == "full" else NgramPartScorer)(ngram_file, token_list)
+            scorers = dict(ctc=CTCPrefixScorer(ctc=asr_model.ctc, eos=asr_model.eos))
+            if self.ngram is not None:
+                scorers["ngram"] = self.ngram
+            self.beam_search_timesync = BeamSearchTimeSync(
+                sos=asr_model.sos, beam_size=beam_size, scorers=scorers, token_list=token_list, blank=asr_model.blank_id,
+                weights=dict(ctc=ctc_weight, ngram=ngram_weight if self.ngram is not None else 0.0, length_bonus=penalty))
+        elif asr_model.use_transducer_decoder:  # asr_inference.py: BeamSearchTransducer in place of the joint search
             if lm_train_config is not None or ngram_file is not None:
                 raise NotImplementedError("lm_train_config / ngram_file with a transducer model: language-model fusion in "
                                           "the transducer search is outside the MI355X hot path")
@@ -134,7 +163,7 @@ class Speech2Text:
                 ngram_weight=ngram_weight if self.ngram is not None else 0.0)
         m = asr_model
         pack_modules(device, [m.frontend, m.encoder, m.ctc] +
-                     ([] if ctc_greedy else [m.decoder, m.joint_network, self.lm, self.ngram]))
+                     ([] if ctc_greedy else [self.ngram] if time_sync else [m.decoder, m.joint_network, self.lm, self.ngram]))
 
     # ------------------------------------------------------------------ single utterance (reference API)
     @torch.no_grad()
@@ -155,6 +184,9 @@ class Speech2Text:
         st = self.asr_model.encode_device(speech, [int(n) for n in speech_lengths], isolate=True)
         if self.ctc_greedy:
             return self._finish_greedy(*self.decode_greedy_device(st))
+        if self.beam_search_timesync is not None:
+            hyps = self.beam_search_timesync.search_batch(st.enc_act, st.olens, nbest=self.nbest)
+            return [self._format(h[: self.nbest]) for h in hyps]
         if self.beam_search_transducer is not None:
             hyps = self.beam_search_transducer.search_batch(st.enc_act, st.olens)
             return [self._format_transducer(h[: self.nbest]) for h in hyps]
@@ -168,7 +200,8 @@ class Speech2Text:
         handle's `.result()` waits for this batch alone (an event after its D2H copy), so the caller can
         enqueue the next batch first and format this one while the GPU runs.  The beam search polls the
         device between step chunks and therefore completes inside this call."""
-        if self.beam_search_transducer is not None:  # (the walk reads back once, at its end: completes inside this call)
+        if self.beam_search_transducer is not None or self.beam_search_timesync is not None:
+            # (these walks read back once, at their end: complete inside this call)
             return _Done(self.batch_decode(speech, speech_lengths))
         if not self.ctc_greedy:
             # Round 6: several joint searches in flight (espnet_amd.nets.batch_beam_search.SearchLanes) - this batch is encoded
@@ -499,6 +532,9 @@ class Speech2Text:
         if self.ctc_greedy:
             raise RuntimeError("batch_rescore: this object decodes greedy CTC (ctc_greedy=True) and has no joint search whose "
                                "score it could give")
+        if self.__dict__.get("beam_search_timesync") is not None:
+            raise RuntimeError("batch_rescore: this object decodes with the time-synchronous CTC search (time_sync=True) and "
+                               "has no joint search whose score it could give")
         if self.beam_search is None:
             raise RuntimeError("batch_rescore: this is a transducer model; the joint CTC/attention score needs the joint "
                                "search's scorers (the transducer's own likelihood: batch_transducer_nll)")

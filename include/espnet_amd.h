@@ -33,6 +33,8 @@
  *       em_transducer_seq_align: every output whole (frames -1, log-probabilities 0 behind the lengths);
  *       em_ctc_frame_top, em_lm_head_top1: both outputs [M] whole; em_maskctc_refine: y_in and the traces whole
  *         (tests/test_gpu_maskctc.py).
+ *       em_ctc_frame_topk: cand_id, cand_lp [M][K] and blank_lp [M] whole; em_ctc_tsync_search: every output whole
+ *         (tokens -1 behind lens; lens 0 and scores 0 behind count) (tests/test_gpu_ctc_tsync.py).
  *   - EmSearchBuffers: the caller writes xlens / maxlens / minlens per search and ZEROES ONCE, at allocation, mem_vT,
  *     rnn_hs, rnn_cs and rnn_hin (and again mem_vT whenever Tpad changes under it: the streaming search).  The library
  *     leaves their zero regions zero - the columns T .. Tpad of mem_vT, the channels nhid .. d of every recurrent state
@@ -1328,6 +1330,55 @@ int32_t em_ctc_segment_max_window(void);
 int em_ctc_seq_nll(const float* lpT, int32_t ldT, const int32_t* xlens, int32_t Bm, int32_t T, const int32_t* targets,
                    int32_t Lmax, const int32_t* ylens, const int32_t* mem_of, int32_t N, int32_t blank, float* nll,
                    void* stream);
+
+/* ---- time-synchronous CTC prefix beam search with n-gram fusion (csrc/ctc_tsync.hip): BeamSearchTimeSync of
+ *      espnet/nets/beam_search_timesync.py (Speech2Text(time_sync=True)) for ctc_weight = 1, with the n-gram scorer of
+ *      em_ngram_score as an extension.  Two launches, nothing read back in between; all pointers on the device.
+ *   em_ctc_frame_topk: lp [M][V] f32 log-probability rows -> per row the K largest (id, value) pairs in descending value,
+ *      ties to the lower id: cand_id / cand_lp [M][K]; blank_lp [M] = lp[row][blank].  1 <= K <= V (any V); rows are
+ *      independent, one launch covers them all.  Valid rows are finite; a row holding NaN has undefined candidates (ids
+ *      stay inside [0, V)) and the call still ends.  No workspace.
+ *   em_ctc_tsync_search: cand_id / cand_lp [B][T][K], blank_lp [B][T] as em_ctc_frame_topk leaves them for lp [B][T][V]
+ *      (T the row stride), xlens [B] the valid frames (clamped to [0, T]).  Per utterance, with W the beam, sos = eos, the
+ *      weights w_ctc, w_ngram, penalty, NG(l) = the f32 sum of the n-gram's log10 scores of l's tokens, each after its
+ *      predecessors (0 without ngram), logaddexp shifted by its larger term (-inf, -inf -> -inf), everything f32:
+ *        hyps = [(sos,)];  dp = {(sos,): (p_nb = -inf, p_b = 0)}
+ *        for t < xlens[b], cands = the K candidates of frame t, next = {} (a missing key reads (-inf, -inf)):
+ *          for l in hyps, prev = logaddexp(dp[l]), for c in cands:
+ *            c == blank:  next[l].p_b = logaddexp(next[l].p_b, lp[blank] + prev)
+ *            otherwise:   l2 = l + (c,), (nb, b) = next[l2]
+ *                         c == l[-1]: nb = logaddexp(nb, lp[c] + dp[l].p_b);
+ *                                     next[l].p_nb = logaddexp(next[l].p_nb, lp[c] + dp[l].p_nb)
+ *                         else:       nb = logaddexp(nb, lp[c] + prev)
+ *                         l2 not in hyps and l2 in dp (scored last frame, then pruned):
+ *                                     b = logaddexp(b, lp[blank] + logaddexp(dp[l2])); nb = logaddexp(nb, lp[c] + dp[l2].p_nb)
+ *                         next[l2] = (nb, b)
+ *          every key written in next is a member of the frame;
+ *          score(l) = w_ctc * logaddexp(next[l]) + w_ngram * NG(l) + penalty * (len(l) - 1)
+ *          hyps = the W members of largest score > -inf (the beam may hold fewer);  dp = next (all members)
+ *        final(l) = score(l) + w_ngram * ngram(eos | l); the n-best are hyps by descending final.
+ *      Prefixes are identified by their token sequence (a 64-bit hash finds a candidate entry, the sequences are then
+ *      compared).  Two deliberate differences from the reference class: exactly K candidates per frame (it admits every
+ *      token tied with the K-th), and a prefix whose repeat or merged mass was written is a member even when the blank is
+ *      not among the K candidates (there it is dropped).
+ *      Outputs, every element written: tokens [B][nbest][T] i32 (the prefix without <sos>; -1 behind lens), lens [B][nbest],
+ *      count [B] = the hypotheses found (<= min(W, nbest)); score, score_ctc (logaddexp of the last frame), score_ngram
+ *      (NG plus the <eos> term), score_len (len - 1) [B][nbest] f32, unweighted columns; rows >= count: lens 0, scores 0.
+ *      xlens[b] == 0: the empty hypothesis, every score 0.  A row depends on its own utterance only, bit for bit.
+ *      ngram: host struct of device arrays as em_ngram_score takes it, or NULL (w_ngram is then ignored).
+ *      W <= W_max, K <= K_max of em_ctc_tsync_limits (32, 64): EM_ERR_UNSUPPORTED above.  Any T: ws of
+ *      em_ctc_tsync_search_workspace_bytes(B, T, K, W) bytes (0 for refused shapes; a smaller one: EM_ERR_WORKSPACE) holds
+ *      the prefix nodes (T W + 1 per utterance) and the frame's slot records; its contents on entry are ignored ("Scratch
+ *      memory" above).  One workgroup per utterance, every loop bounded at launch.                                        */
+int em_ctc_frame_topk(const float* lp, int32_t M, int32_t V, int32_t K, int32_t blank, int32_t* cand_id, float* cand_lp,
+                      float* blank_lp, void* stream);
+int em_ctc_tsync_search(const int32_t* cand_id, const float* cand_lp, const float* blank_lp, const int32_t* xlens, int32_t B,
+                        int32_t T, int32_t K, int32_t W, int32_t nbest, int32_t sos, int32_t blank, float w_ctc,
+                        float w_ngram, float penalty, const struct EmNgramModel* ngram, int32_t* tokens, int32_t* lens,
+                        int32_t* count, float* score, float* score_ctc, float* score_ngram, float* score_len, void* ws,
+                        size_t ws_bytes, void* stream);
+size_t em_ctc_tsync_search_workspace_bytes(int32_t B, int32_t T, int32_t K, int32_t W);
+void em_ctc_tsync_limits(int32_t* W_max, int32_t* K_max);
 
 /* ---- transducer (RNN-T) decoding (csrc/transducer.hip): the prediction network as a decoder, the joint network and the
  *      greedy search.  Reference: espnet2/asr/decoder/transducer_decoder.py (TransducerDecoder), espnet2/asr_transducer/
