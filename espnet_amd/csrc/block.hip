@@ -47,6 +47,13 @@
 // ingests 64 B/clk, i.e. 512 cycles per unit against 256 cycles of MFMA: the kernels are built around keeping
 // that stream busy (requests three units ahead, unconditional so that hipcc can count its waits, barriers only
 // where waves exchange data).
+//
+// The feed-forward loops ARE at that limit.  Conformer-small (ff = 1024, nch = 16), block<D|A>, fine stamps 20 -> 21
+// (profiles/r05b_block_stamps_fine.txt, r12a_block_stamps.txt): 7 loop iterations plus the last pair's W2 half = 480 MFMAs
+// per wave (7 x 64 + 32) and 7.5 x 128 KiB of weights in 17.4 K cycles: 44 - 47 % MFMA utilisation, 56.5 B/clk per CU.
+// (Rounds 5 - 12 read "88 - 94 %, 110 B/clk" off the same stamps by counting the 15 iterations of ff = 2048.)  A 32-row
+// workgroup that streams an FFN's 1 MiB through one CU cannot make the loop shorter; what round 13 shortens is the
+// hand-over around it (ffn() below).
 #include <stdio.h>
 #include <stdlib.h>
 
@@ -71,10 +78,20 @@ constexpr int TOUCH_OFF = RED_OFF + 2048;                    // 1 KiB: where the
 constexpr int TILE_OFF = TOUCH_OFF + 1024;                   // 32 KiB: the depthwise conv's 62-row input tile; during an FFN the parked residual
 constexpr int ABUF_OFF = TILE_OFF + 32768;                   // 16 KiB: LN(x) as four [32][64] k-tiles
 constexpr int WK_OFF = ABUF_OFF + 16384;                     // 32 KiB: depthwise conv weights [31][256] f32 (tap-major) + bias [256]
-constexpr int XCH_OFF = WK_OFF + 32768;                      // 48 KiB more: with ABUF and WK the 96 KiB of the FFN's cross-wave reduction
-constexpr int XSLOT = 8192;                                  // one (destination wave, source wave) slot: [4 fragments][2 halves][64 lanes] f32x4
-constexpr int SMEM_BYTES = XCH_OFF + 49152;                  // 159 KiB
+constexpr int XCH_OFF = WK_OFF + 32768;                      // the FFN's hand-over slots (16 KiB, HX_*); the attention phase's rel-shift scratch (42 KiB), the folded C part (40 KiB)
+#ifndef EM_BLOCK_VAR
+#define EM_BLOCK_VAR 0  // developer A/B builds (tools/build_block_variants.sh)
+#endif
+// Round 13: the FFN's waves exchange the HIDDEN tile once per chunk pair (8 KiB of bf16 per pair and workgroup, under the
+// loop's waits for weight lines) instead of their K-split partial sums behind the loop (96 KiB of f32 written, 96 KiB read
+// and a barrier on the exit path of every module).  -DEM_BLOCK_VAR=0x80000 builds the round-3 exit path again (A/B).
+constexpr bool FFN_HANDOVER = (EM_BLOCK_VAR & 0x80000) == 0;
+constexpr int HX_OFF = XCH_OFF;                              // [2 buffers][4 source waves][2 frame halves][64 lanes] 16 B: the pair's hidden tile, lane-major
+constexpr int HX_BUF = 8192, HX_SLICE = 2048;
+constexpr int XSLOT = 8192;                                  // (0x80000 builds) one (destination wave, source wave) slot of the reduction: [4 fragments][2 halves][64 lanes] f32x4, 96 KiB from ABUF on
+constexpr int SMEM_BYTES = XCH_OFF + (FFN_HANDOVER ? 45056 : 49152);  // 155 KiB (0x80000 builds: 159 KiB)
 static_assert(ABUF_OFF % 1024 == 0 && TILE_OFF % 1024 == 0 && SMEM_BYTES <= 160 * 1024, "LDS layout");
+static_assert(HX_OFF + 2 * HX_BUF <= SMEM_BYTES && XCH_OFF + 4 * (2 * 16 * 84) * 4 <= SMEM_BYTES, "hand-over slots, attention scratch");
 constexpr int KW_MAX = 31, TROWS_MAX = BM + KW_MAX - 1;  // depthwise conv: kernel width is a template argument (31: the
                                                           // Conformer recipes, 15: the streaming recipe), 62-row input tile at most
 // Row pitch of the conv tile: 512 + 16 bytes.  The conv reads a row's 256 channels contiguously (any pitch will do);
@@ -104,9 +121,6 @@ constexpr int BAR_UNIT = 1, BAR_PARAMS = 2, BAR_TILE = 4, BAR_LAST = 8;  // what
 #define EM_BLOCK_DBG 0  // developer builds: 1 = no MFMA / epilogue work (what does the streaming cost alone?)
 #endif
 
-#ifndef EM_BLOCK_VAR
-#define EM_BLOCK_VAR 0  // developer A/B builds (tools/build_block_variants.sh)
-#endif
 #ifndef EM_BLOCK_FINE
 #define EM_BLOCK_FINE 0  // 1: EM_BLOCK_STAMPS records every wave of workgroup (3, 5) at sub-stage granularity
 #endif
@@ -634,10 +648,29 @@ __global__ __launch_bounds__(NT, 1) void block_kernel(const EmBlockArgs a_in, lo
   // The weight stream is unchanged in bytes: per pair and wave 2 x 8 KiB of W1 (ring[0], ring[1]) and 2 x 8 KiB of
   // W2 (ring[2], ring[3]); a ring slot is refilled as soon as its 16 MFMAs are issued, i.e. requested one whole
   // iteration (64 MFMAs) ahead of its use.  The host pads odd chunk counts with a zero chunk (nch is even here).
+  // Round 13 (FFN_HANDOVER): the loop is not MFMA-bound, as round 3 believed, but waits for weight lines for 0.7 - 1 K of
+  // every 2.3 K-cycle iteration, and the K-split's meeting BEHIND the loop - 96 KiB of f32 written, a barrier, 96 KiB read,
+  // the residual un-parked: 2.2 - 4.7 K cycles per module, 24 modules per step - hides under nothing.  So the exchange
+  // moves to the hidden tile: per pair every wave stores its B fragments (2 x 16 B per lane, 8 KiB per workgroup) into a
+  // double-buffered slot and reads all four slices back at its own lane index (lane-major both ways: no transposition,
+  // no bank conflict), and W2 is dealt to the waves by OUTPUT columns: wave v owns the fragments f = 4 f4 + v, its
+  // columns of the residual layout, and takes the line pair[p][s][f] of pack_w2's unchanged layout for every source slice
+  // s.  Same bytes, same 32 MFMAs per pair and wave, same ring slots; one accumulator set PER SOURCE SLICE (128 registers,
+  // as acc2 before) added in slice order behind the loop, so every bit is the round-3 form's.  Fine stamps of block<D|A>
+  // (profiles/r13a_block_stamps_fine.txt), 15 -> 22 of the slowest wave: 24.2 - 24.8 K -> 22.2 - 22.4 K cycles (the D part's
+  // module), 23.5 - 24.0 K -> 21.2 K (the macaron module); the step 0.876 - 0.882 -> 0.861 - 0.867 ms (profiles/r13a_bench_pair.txt).
   auto read_w2 = [&](const void* w2, int p, int half, WF& w) __attribute__((always_inline)) {
-    GU8 su = (GU8)w2 + (size_t)p * (2 * UNIT) + nf * 16384 + half * 8192 + lane * 16;
+    if constexpr (FFN_HANDOVER) {
+      // the same 1 KiB lines pair[p][source slice s][fragment f], dealt by OUTPUT columns: this wave's fragments f = 4 f4 + nf
+      // of the source slices 2 half, 2 half + 1 (q = 4 (s & 1) + f4)
+      GU8 su = (GU8)w2 + (size_t)p * (2 * UNIT) + half * 32768 + nf * 1024 + lane * 16;
 #pragma unroll
-    for (int q = 0; q < 8; ++q) w.v[q] = *(GFRAG)(su + q * 1024);
+      for (int q = 0; q < 8; ++q) w.v[q] = *(GFRAG)(su + (q >> 2) * 16384 + (q & 3) * 4096);
+    } else {
+      GU8 su = (GU8)w2 + (size_t)p * (2 * UNIT) + nf * 16384 + half * 8192 + lane * 16;
+#pragma unroll
+      for (int q = 0; q < 8; ++q) w.v[q] = *(GFRAG)(su + q * 1024);
+    }
   };
   auto ffn_pre = [&](const void* w1, const void* w2) __attribute__((always_inline)) {
     read_unit(w1, 0, ring[0]);
@@ -672,13 +705,18 @@ __global__ __launch_bounds__(NT, 1) void block_kernel(const EmBlockArgs a_in, lo
     f32x4 acc2[16][2];
 #pragma unroll
     for (int f = 0; f < 16; ++f) acc2[f][0] = acc2[f][1] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    // the residual is not needed until the end: its 32 registers are parked in LDS (the conv tile's space, lane-major:
-    // conflict-free, private to the lane, no barrier)
+    // Round-3 form: the residual is not needed until the end, its 32 registers are parked in LDS (the conv tile's space,
+    // lane-major: conflict-free, private to the lane, no barrier).  Hand-over form: the registers are there (the worst
+    // instantiation takes 446 of 512, no scratch) and x stays in them - parked it measured 0.873 - 0.874 ms per batch against
+    // 0.868 - 0.870 (profiles/r13a_handover_ab.txt); `xpark` is still where a caller with `repark` finds x afterwards.
     float4* const xpark = (float4*)(smem + TILE_OFF) + tid;
+    constexpr bool PARK = !FFN_HANDOVER;
+    if constexpr (PARK) {
 #pragma unroll
-    for (int mi = 0; mi < 2; ++mi)
+      for (int mi = 0; mi < 2; ++mi)
 #pragma unroll
-      for (int f = 0; f < 4; ++f) xpark[(mi * 4 + f) * NT] = xr[mi][f];
+        for (int f = 0; f < 4; ++f) xpark[(mi * 4 + f) * NT] = xr[mi][f];
+    }
     // bias + Swish + bf16 of the two chunks' 16 hidden columns of this wave -> the B fragments of the pair
     auto swish_pack = [&](const f32x4 h[2][2], int p, bf16x8 hb[2]) __attribute__((always_inline)) {
       float4 b0, b1;
@@ -699,22 +737,84 @@ __global__ __launch_bounds__(NT, 1) void block_kernel(const EmBlockArgs a_in, lo
                           (bf16)act_(h[1][mi][0] + b1.x), (bf16)act_(h[1][mi][1] + b1.y),
                           (bf16)act_(h[1][mi][2] + b1.z), (bf16)act_(h[1][mi][3] + b1.w)};
     };
-    // 16 MFMAs of a W2 sub-unit: output fragments 8 half .. 8 half + 7, both frame halves
-    auto mma_w2 = [&](const WF& w, int half, const bf16x8 hb[2]) __attribute__((always_inline)) {
+    // 16 MFMAs of a W2 sub-unit.  Round 3 form: output fragments 8 half .. 8 half + 7 of this wave's own hidden slice.
+    // Hand-over form: this wave's four output fragments against the source slices 2 half, 2 half + 1; one accumulator set
+    // per source slice, acc2[4 s + f4], so that every set sees the operands, in the order, of slice s's partial sum in the
+    // round-3 form and the closing sum below is reduce_as's: the same bits.
+    auto mma_w2 = [&](const WF& w, int half, const bf16x8 (*hv)[2]) __attribute__((always_inline)) {
       if constexpr (dbg & 1) return;
 #pragma unroll
       for (int q = 0; q < 8; ++q) {
-        acc2[half * 8 + q][0] = MM::mma(w.v[q], hb[0], acc2[half * 8 + q][0]);
-        acc2[half * 8 + q][1] = MM::mma(w.v[q], hb[1], acc2[half * 8 + q][1]);
+        const bf16x8* const b = FFN_HANDOVER ? hv[2 * half + (q >> 2)] : hv[0];
+        acc2[half * 8 + q][0] = MM::mma(w.v[q], b[0], acc2[half * 8 + q][0]);
+        acc2[half * 8 + q][1] = MM::mma(w.v[q], b[1], acc2[half * 8 + q][1]);
       }
     };
+    // the hand-over: a wave's B fragments of the pair go lane-major into its slice of buffer `buf`; every wave reads all
+    // four slices at its own lane index (its own included: a register pick by wave number would need the loop four times)
+    unsigned char* const hx = smem + HX_OFF + lane * 16;
+    auto hx_put = [&](int buf, const bf16x8 hb[2]) __attribute__((always_inline)) {
+#pragma unroll
+      for (int mi = 0; mi < 2; ++mi) *(bf16x8*)(hx + buf * HX_BUF + nf * HX_SLICE + mi * 1024) = hb[mi];
+    };
+    auto hx_get = [&](int buf, bf16x8 hv[4][2]) __attribute__((always_inline)) {
+#pragma unroll
+      for (int s = 0; s < 4; ++s)
+#pragma unroll
+        for (int mi = 0; mi < 2; ++mi) hv[s][mi] = *(const bf16x8*)(hx + buf * HX_BUF + s * HX_SLICE + mi * 1024);
+    };
     f32x4 h[2][2];
-    bf16x8 hb[2];
+    bf16x8 hb[1][2];
     mma_k(ring[0], false, h[0]);
     read_w1(2, ring[0]);
     mma_k(ring[1], false, h[1]);
     read_w1(3, ring[1]);
-    swish_pack(h, 0, hb);
+    swish_pack(h, 0, hb[0]);
+    if constexpr (FFN_HANDOVER) {
+      // Iteration p: the W1 MFMAs of pair p + 1, the MEETING (barrier, then the four slices of pair p's tile from buffer
+      // p & 1), the W2 MFMAs of pair p with Swish and the store of pair p + 1's own slice into buffer (p + 1) & 1 among them.
+      // One barrier per pair is enough with two buffers: buffer (p + 1) & 1 was last read behind the meeting of iteration
+      // p - 1, and a wave passes the meeting of iteration p - the one in front of this store - only when every wave has
+      // arrived there with those reads retired (bar() waits for the wave's own LDS operations: the hardware barrier alone
+      // does not, see gemm.hip); the meeting of iteration p + 1 then publishes the store.  The first tile is written before
+      // any barrier of the module: nothing else touches XCH between the barriers of the LayerNorm in front and the end of
+      // the module, and the last tile's reads are consumed before the barriers of the LayerNorm behind.
+      // Where the meeting sits was measured (profiles/r13a_handover_ab.txt, ms per batch of the default bench line, the
+      // parent 0.880 - 0.884 in that call): behind BOTH W1 units, as here, 0.873 - 0.874 - a wave arrives at the barrier 32
+      // MFMAs and their waits for weight lines after its store, so nobody waits for a store, and only the first reads' LDS
+      // latency is exposed; at the END of the iteration, the reads under the next pair's W1 MFMAs, 0.883 - 0.885 (the store
+      // comes last, behind the Swish tail: every wave waits there with an empty matrix pipe, 20 -> 21 grew by what 21 -> 22
+      // lost); between the two W1 units 0.896 - 0.899.  The two scheduling fences keep hipcc from moving instructions
+      // across the meeting: without them the line is 0.880 - 0.883 against 0.859 - 0.863 with them (measured; which
+      // instructions it moves was not looked at).
+      bf16x8 hv[4][2];
+      auto meet = [&](int buf) __attribute__((always_inline)) {
+        __builtin_amdgcn_sched_barrier(0);
+        bar(0);
+        hx_get(buf, hv);
+        __builtin_amdgcn_sched_barrier(0);
+      };
+      hx_put(0, hb[0]);
+      rstamp(20);
+      // (requests UNCONDITIONAL, as below)
+#pragma unroll 1
+      for (int p = 0; p + 1 < np; ++p) {
+        mma_k(ring[0], false, h[0]);                             // chunk 2p + 2
+        read_w1(2 * p + 4, ring[0]);
+        mma_k(ring[1], false, h[1]);                             // chunk 2p + 3
+        read_w1(2 * p + 5, ring[1]);
+        meet(p & 1);
+        mma_w2(ring[2], 0, hv);                                  // pair p, source slices 0, 1
+        read_w2(w2, p + 1, 0, ring[2]);
+        swish_pack(h, p + 1, hb[0]);
+        hx_put((p + 1) & 1, hb[0]);
+        mma_w2(ring[3], 1, hv);                                  // source slices 2, 3
+        read_w2(w2, p + 1, 1, ring[3]);
+      }
+      meet((np - 1) & 1);
+      mma_w2(ring[2], 0, hv);                                    // the last pair
+      mma_w2(ring[3], 1, hv);
+    } else {  // (-DEM_BLOCK_VAR=0x80000: the round-3 loop, kept for A/B; its lines stand as they did)
     // every wave holds its activation fragments and has read the conv weights: ABUF / WK may receive partial sums
     // from a wave that finishes early (the only barrier of the FFN besides the reduction's)
     bar(0);
@@ -732,16 +832,42 @@ __global__ __launch_bounds__(NT, 1) void block_kernel(const EmBlockArgs a_in, lo
       read_w2(w2, p + 1, 0, ring[2]);
       mma_w2(ring[3], 1, hb);
       read_w2(w2, p + 1, 1, ring[3]);
-      swish_pack(h, p + 1, hb);
+      swish_pack(h, p + 1, hb[0]);
     }
     mma_w2(ring[2], 0, hb);                                    // the last pair
     mma_w2(ring[3], 1, hb);
+    }
     after();
     rstamp(21);
+    float4 psum[2][4];  // (split FFN, streaming instantiations: this share's partial sum)
+    if constexpr (FFN_HANDOVER) {
+      // ---- this wave holds, per source slice, what that slice's wave used to hand it: added in slice order 0, 1, 2, 3
+      // (reduce_as's order), in registers, no barrier
+#pragma unroll
+      for (int f4 = 0; f4 < 4; ++f4) {
+        const float4 b4 = *(const float4*)(pb + b2o + 64 * f4 + ncol);
+#pragma unroll
+        for (int mi = 0; mi < 2; ++mi) {
+          f32x4 sum = acc2[f4][mi];
+#pragma unroll
+          for (int src = 1; src < 4; ++src) sum = sum + acc2[4 * src + f4][mi];
+          if constexpr (RELU) {
+            if (nsplit > 1) {  // (split FFN: the partial sum of THIS workgroup's share; finished below, behind the meeting point)
+              psum[mi][f4] = make_float4(sum[0], sum[1], sum[2], sum[3]);
+              continue;
+            }
+          }
+          xr[mi][f4].x += scale * (sum[0] + b4.x);
+          xr[mi][f4].y += scale * (sum[1] + b4.y);
+          xr[mi][f4].z += scale * (sum[2] + b4.z);
+          xr[mi][f4].w += scale * (sum[3] + b4.w);
+          if (repark) xpark[(mi * 4 + f4) * NT] = xr[mi][f4];  // the caller stores x from here at the very end of the kernel
+        }
+      }
+    } else {  // (-DEM_BLOCK_VAR=0x80000: the round-3 exit path)
     // ---- the four partial sums meet: wave w keeps the output fragments f = 4 f4 + w (its columns of the residual
     // layout) and hands the other twelve to their owners through 8 KiB slots (destination, source); summed in wave
     // order 0, 1, 2, 3 whatever the arrival order: deterministic
-    float4 psum[2][4];  // (split FFN, streaming instantiations: this share's partial sum)
     auto reduce_as = [&](auto nfc) __attribute__((always_inline)) {
       constexpr int NF = decltype(nfc)::value;
 #pragma unroll
@@ -789,6 +915,7 @@ __global__ __launch_bounds__(NT, 1) void block_kernel(const EmBlockArgs a_in, lo
       case 1: reduce_as(std::integral_constant<int, 1>{}); break;
       case 2: reduce_as(std::integral_constant<int, 2>{}); break;
       default: reduce_as(std::integral_constant<int, 3>{}); break;
+    }
     }
     if constexpr (RELU) {
       if (nsplit > 1) {
@@ -884,7 +1011,7 @@ __global__ __launch_bounds__(NT, 1) void block_kernel(const EmBlockArgs a_in, lo
 #pragma unroll
             for (int f4 = 0; f4 < 4; ++f4) {
               const float4 b4 = *(const float4*)(pb + b2o + 64 * f4 + ncol);
-              xr[mi][f4] = xpark[(mi * 4 + f4) * NT];
+              if constexpr (PARK) xr[mi][f4] = xpark[(mi * 4 + f4) * NT];
               xr[mi][f4].x += scale * (tot[f4].x + b4.x);
               xr[mi][f4].y += scale * (tot[f4].y + b4.y);
               xr[mi][f4].z += scale * (tot[f4].z + b4.z);

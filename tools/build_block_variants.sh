@@ -7,6 +7,8 @@
 #                                                           round 12, where the row stores go: 0x10000 x of the A part at
 #                                                           the end of the kernel again, 0x20000 x of the C part at the end
 #                                                           again, 0x40000 the GLU stores counted too, e.g. v0x30000)
+#                                                           round 13: 0x80000 the FFN's K-split and its partial-sum exchange
+#                                                           behind the loop again instead of the per-pair hand-over)
 #   espnet_amd/lib/dbg/lib_fine.so   -DEM_BLOCK_FINE=1     (EM_BLOCK_STAMPS=1 prints sub-stage stamps of all four waves)
 # Used for profiles/r02l, r02m, r02o, r02q and the round-3 A/B calls (tools/gpu_calls.sh).  dbg builds give wrong results by
 # design: timing only.   usage: bash tools/build_block_variants.sh nt 4 v1 v16 fine
