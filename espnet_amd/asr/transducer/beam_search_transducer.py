@@ -6,8 +6,13 @@ Mirrors espnet2/asr/transducer/beam_search_transducer.py (constructor keywords, 
   * beam_size <= 1 - greedy_search: at most one label per frame, so a ragged batch moves in lock-step and the whole walk
     is `em_transducer_greedy` (csrc/transducer.hip): a stream-ordered chain of launches per frame, nothing read back
     until it has ended.  `search_batch` is the batched entry, `__call__` the batch of one.
-  * beam_size > 1, search_type="default" - default_beam_search, driven from the host over the two device primitives
-    (`em_transducer_dec_step`, `em_transducer_joint_logp`), one launch pair and one read-back per expansion.
+  * beam_size > 1, search_type="default" - `beam_device`: `em_transducer_beam_search` (csrc/transducer_beam.hip) walks a
+    batch of up to 64 utterances in lock-step, one expansion per live utterance and step, the steps enqueued in chunks
+    with one small status read-back per chunk.  `default_beam_search` - driven from the host over the two device
+    primitives (`em_transducer_dec_step`, `em_transducer_joint_logp`), one launch pair and one read-back per expansion -
+    is the route of an utterance the walk stopped on (a capacity of `beam_limits()`, MAX_EXPANSIONS_PER_FRAME) and of
+    beams above the walk's limit; both routes see the same log-probability bits and sum scores in double, so they
+    return the same lists.
   * tsd / alsd / nsc / maes, a language model and multi-blank models raise NotImplementedError.
 """
 import ctypes as C
@@ -24,6 +29,14 @@ MAX_WALK_ROWS = 64  # em_transducer_greedy: utterances per call
 # whose every context prefers some label to blank never leaves a frame.  Trained models leave one after a few
 # expansions per beam entry; each expansion here is a pair of launches and a read-back, so the loop must end.
 MAX_EXPANSIONS_PER_FRAME = 1000
+
+
+def beam_limits():
+    """`em_transducer_beam_limits`: the device walk's capacities per utterance - the largest beam, open entries, kept
+    entries, expansions of one frame, labels of one hypothesis (the leading blank included)."""
+    v = [C.c_int32(0) for _ in range(5)]
+    L.load().em_transducer_beam_limits(*(C.byref(x) for x in v))
+    return dict(zip(("beam", "open", "kept", "expansions", "labels"), (int(x.value) for x in v)))
 
 
 @dataclass
@@ -62,6 +75,8 @@ class BeamSearchTransducer:
         self.token_list = token_list
         self.keep_trace = False  # tests: the greedy walk's per-frame trace in `last_trace`
         self.last_trace = None
+        self.last_beam = None  # beam_device: status rows, steps enqueued / needed
+        self.last_routes = None  # search_batch, beam_size > 1: "device" or "host" per utterance
 
     # ------------------------------------------------------------------ greedy: the fused walk
     @torch.no_grad()
@@ -90,13 +105,122 @@ class BeamSearchTransducer:
                                          L.current_stream_ptr()), "em_transducer_greedy")
         return (tokens, ylens, score) + ((tr,) if trace else ())
 
+    # ------------------------------------------------------------------ default beam search: the device walk
+    @torch.no_grad()
+    def beam_device(self, enc_act: torch.Tensor, olens, max_steps: Optional[int] = None, trace: bool = False):
+        """`em_transducer_beam_search` (csrc/transducer_beam.hip) for enc_act (B, T, D) on the device, olens host ints,
+        B <= 64 and beam_size <= the library's limit (NotImplementedError beyond).  The steps - one expansion per live
+        utterance each - are enqueued in chunks, the first of max(olens) x beam (what a search needs at least); after a
+        chunk the (B, 4) status array is read, until every utterance has ended or stopped, then the results in one
+        gathered copy.  Returns a list over the utterances: the n-best hypotheses (`sort_nbest`; `dec_state` is None on
+        this route: the states stay on the device), or None for an utterance the walk stopped on - a capacity of
+        `beam_limits()` or MAX_EXPANSIONS_PER_FRAME - or that has no frame; `search_batch` decodes those with
+        `default_beam_search`.  `last_beam` holds the status rows, the steps enqueued and the steps needed.
+        Tests: `max_steps` ends the walk after that many steps; `trace` enqueues step by step and keeps each step's
+        (log-prob rows (B, V), trace rows (B, 4 + Lmax)) in `last_beam["steps"]`."""
+        dec, jn = self.decoder, self.joint_network
+        L.require_gpu(enc_act, "enc_act")
+        B, T, _ = enc_act.shape
+        olens = [min(int(v), int(T)) for v in olens]
+        lim = beam_limits()
+        beam = min(self.beam_size, self.vocab_size)
+        if B > MAX_WALK_ROWS:
+            raise NotImplementedError(f"beam_device: {B} utterances, one call walks at most {MAX_WALK_ROWS}")
+        if self.beam_size > lim["beam"]:
+            raise NotImplementedError(f"beam_device: beam_size={self.beam_size}, the device walk holds beams up to "
+                                      f"{lim['beam']} ({lim['open']} open and {lim['kept']} kept entries, "
+                                      f"{lim['expansions']} expansions of one frame, {lim['labels']} labels of a hypothesis)")
+        dev = enc_act.device
+        w, keep = dec.weights(dev)
+        # lin_enc per utterance, on exactly the rows default_beam_search hands it: the same GEMM call, so the same bits
+        enc_proj = torch.zeros(B, T, w.jp, dtype=torch.float32, device=dev)
+        for b in range(B):
+            if olens[b] > 0:
+                enc_proj[b, : olens[b]] = jn.enc_proj_device(enc_act[b, : olens[b]])
+        lib = L.load()
+        need = int(lib.em_transducer_beam_workspace_bytes(dec.em_dtype, C.byref(w), B, T, self.beam_size))
+        if need == 0:
+            raise NotImplementedError(f"em_transducer_beam_search: B={B}, T={T}, beam={self.beam_size} are outside one call")
+        Tmax = max(olens + [1])
+        Lmax = min(lim["labels"], 2 * Tmax + 16)
+        ncap = lim["kept"]
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        ol = torch.tensor(olens, dtype=torch.int32).to(dev)
+        status = torch.zeros(B, 4, dtype=torch.int32, device=dev)
+        out_tok = torch.empty(B, ncap, Lmax, dtype=torch.int32, device=dev)
+        out_len = torch.zeros(B, ncap, dtype=torch.int32, device=dev)
+        out_score = torch.zeros(B, ncap, dtype=torch.float64, device=dev)
+        out_cnt = torch.zeros(B, dtype=torch.int32, device=dev)
+        step_logp = torch.zeros(B, self.vocab_size, dtype=torch.float32, device=dev) if trace else None
+        step_tr = torch.zeros(B, 4 + Lmax, dtype=torch.int32, device=dev) if trace else None
+        max_exp = int(MAX_EXPANSIONS_PER_FRAME)  # (read at call time: a test lowers it)
+
+        def enqueue(first, steps):
+            L.check(lib.em_transducer_beam_search(dec.em_dtype, C.byref(w), L.ptr(enc_proj), L.ptr(ol), B, T, self.beam_size,
+                                                  max_exp, Lmax, ncap, int(first), int(steps), L.ptr(status), L.ptr(out_tok),
+                                                  L.ptr(out_len), L.ptr(out_score), L.ptr(out_cnt), L.ptr(step_logp),
+                                                  L.ptr(step_tr), L.ptr(ws), need, L.current_stream_ptr()),
+                    "em_transducer_beam_search")
+
+        enqueued, first, steps_kept = 0, True, []
+        chunk = Tmax * beam
+        while True:
+            if max_steps is not None:
+                chunk = min(chunk, max_steps - enqueued)
+            if trace:
+                for _ in range(chunk):
+                    step_tr.zero_()
+                    enqueue(first, 1)
+                    first = False
+                    steps_kept.append((step_logp.clone(), step_tr.clone()))
+            else:
+                enqueue(first, chunk)
+                first = False
+            enqueued += chunk
+            st = status.cpu()  # the read-back of this chunk
+            if int((st[:, 0] == 0).sum()) == 0 or (max_steps is not None and enqueued >= max_steps):
+                break
+            chunk = max(Tmax * beam // 4, beam)
+        cnt = out_cnt.cpu()
+        done = [b for b in range(B) if int(st[b, 0]) == 1 and int(cnt[b]) > 0]
+        out: List[Optional[List[Hypothesis]]] = [None] * B
+        if done:
+            rows = torch.tensor([b * ncap + i for b in done for i in range(int(cnt[b]))], dtype=torch.int64).to(dev)
+            scores = out_score.view(-1)[rows].cpu().tolist()
+            lens = out_len.view(-1)[rows].cpu().tolist()
+            toks = out_tok.view(B * ncap, Lmax)[rows].cpu()
+            k = 0
+            for b in done:
+                hyps = []
+                for _ in range(int(cnt[b])):
+                    hyps.append(Hypothesis(score=float(scores[k]), yseq=toks[k, : lens[k]].tolist()))
+                    k += 1
+                # the reference's final list: the qualifying kept entries by ascending score (a stable sort)
+                out[b] = self.sort_nbest(sorted(hyps, key=lambda x: x.score))
+        self.last_beam = dict(status=st, enqueued=enqueued, needed=int(st[:, 2].max()) if B else 0,
+                              steps=[(a.cpu(), t.cpu()) for a, t in steps_kept] if trace else None)
+        return out
+
     @torch.no_grad()
     def search_batch(self, enc_act: torch.Tensor, olens, **unused) -> List[List[Hypothesis]]:
-        """The n-best list of every utterance of a batch: enc_act (B, T, D) on the device, olens host ints."""
+        """The n-best list of every utterance of a batch: enc_act (B, T, D) on the device, olens host ints.  With
+        beam_size > 1 the batch goes through `beam_device` in slices of up to 64 utterances; an utterance the device
+        walk stopped on is decoded by `default_beam_search` (`last_routes`: "device" or "host" per utterance)."""
         B = int(enc_act.shape[0])
         olens = [int(v) for v in olens]
         if self.beam_size > 1:
-            return [self.default_beam_search(enc_act[b, : olens[b]], utt=b) for b in range(B)]
+            if self.beam_size > beam_limits()["beam"]:
+                self.last_routes = ["host"] * B
+                return [self.default_beam_search(enc_act[b, : olens[b]], utt=b) for b in range(B)]
+            out, routes = [], []
+            for b0 in range(0, B, MAX_WALK_ROWS):
+                b1 = min(B, b0 + MAX_WALK_ROWS)
+                res = self.beam_device(enc_act[b0:b1], olens[b0:b1])
+                for b, r in enumerate(res, b0):
+                    routes.append("host" if r is None else "device")
+                    out.append(self.default_beam_search(enc_act[b, : olens[b]], utt=b) if r is None else r)
+            self.last_routes = routes
+            return out
         out, traces = [], []
         for b0 in range(0, B, MAX_WALK_ROWS):
             b1 = min(B, b0 + MAX_WALK_ROWS)
@@ -155,6 +279,4 @@ class BeamSearchTransducer:
         """enc_out (T, D) on the device -> the n-best hypotheses."""
         L.require_gpu(enc_out, "enc_out")
         act = enc_out.to(self.joint_network.act_dtype)
-        if self.beam_size > 1:
-            return self.default_beam_search(act)
         return self.search_batch(act.unsqueeze(0), [int(enc_out.shape[0])])[0]

@@ -426,6 +426,10 @@ _SIGNATURES = {
     "em_transducer_greedy": (C.c_int, [C.c_int, C.POINTER(EmTransducerWeights), _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp,
                                        _vp, _vp, _vp, _sz, _vp]),
     "em_transducer_greedy_workspace_bytes": (_sz, [C.c_int, C.POINTER(EmTransducerWeights), _i32, _i32]),
+    "em_transducer_beam_search": (C.c_int, [C.c_int, C.POINTER(EmTransducerWeights), _vp, _vp, _i32, _i32, _i32, _i32, _i32,
+                                            _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "em_transducer_beam_workspace_bytes": (_sz, [C.c_int, C.POINTER(EmTransducerWeights), _i32, _i32, _i32]),
+    "em_transducer_beam_limits": (None, [_vp, _vp, _vp, _vp, _vp]),
     "em_transducer_lattice_logp": (C.c_int, [C.c_int, C.POINTER(EmTransducerWeights), _vp, _vp, _i32, _i32, _vp, _vp, _i32,
                                              _vp, _vp, _i32, _vp, _vp, _sz, _vp]),
     "em_transducer_lattice_logp_workspace_bytes": (_sz, [C.c_int, C.POINTER(EmTransducerWeights), _i32, _i32, _i32]),

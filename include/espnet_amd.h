@@ -29,6 +29,8 @@
  *       em_ctc_forced_align: every output whole (labels -1, spans -1, scores 0 behind the lengths);
  *       em_ctc_segment: every output whole (columns -1, frames -1, scores 0 off the path and behind the lengths);
  *       em_transducer_greedy: ylens and score whole, tokens[b][< ylens[b]], the traces [b][< olens[b]];
+ *       em_transducer_beam_search: status and out_count whole; of an ended utterance out_scores, out_lens [b][< out_count[b]]
+ *         and out_tokens [b][i][< out_lens[b][i]] (tests/test_gpu_transducer_beam.py);
  *       em_transducer_lattice_logp: the nodes t < xlens[mem_of[n]], u <= ylens[n] (the label of u == ylens[n]: -inf);
  *       em_transducer_seq_align: every output whole (frames -1, log-probabilities 0 behind the lengths);
  *       em_ctc_frame_top, em_lm_head_top1: both outputs [M] whole; em_maskctc_refine: y_in and the traces whole
@@ -1430,6 +1432,42 @@ int em_transducer_greedy(int dtype, const EmTransducerWeights* w, const float* e
                          int32_t T, int32_t* tokens, int32_t* ylens, float* score, int32_t* frame_tok, float* frame_top,
                          float* frame_margin, void* ws, size_t ws_bytes, void* stream);
 size_t em_transducer_greedy_workspace_bytes(int dtype, const EmTransducerWeights* w, int32_t B, int32_t T);
+
+/* ---- transducer beam search (csrc/transducer_beam.hip): BeamSearchTransducer.default_beam_search for a ragged batch in
+ *      lock-step, with no host read-back inside a call.  One STEP is one expansion - the pop of the best open hypothesis,
+ *      the first inserted of equal scores - for every utterance that has not ended: the prediction network and the joint
+ *      network run with rows = utterances (a row's log-probabilities are, bit for bit, those of em_transducer_dec_step +
+ *      em_transducer_joint_logp called for that row alone), the blank extension (log-probability [0]) joins the kept set,
+ *      the min(beam, vocab - 1) best labels of [1:] (lowest id first among equal ones) join the open set, and the frame is
+ *      left when at least min(beam, vocab) kept entries lie strictly above the best open score: those are the next
+ *      frame's open set, in kept order.  Scores are sums in double.  A call enqueues `steps` steps (first != 0: after
+ *      setting the search up; first == 0 continues the search the workspace holds, with the same other arguments); steps
+ *      behind the end of the last utterance return at once.  The caller reads `status` between calls.
+ *   enc_proj [B][T][jp] f32, olens [B] (an utterance with olens[b] <= 0 ends at once with out_count 0).
+ *   status [B][4] i32, whole: { state, frame, expansions so far, most expansions in one frame }; state 0 running, 1 ended,
+ *      2 stopped: `max_expansions` expansions did not leave `frame` (the caller's limit), 3 / 4 / 5 stopped at `frame` on
+ *      a capacity: expansions of one frame / labels of a hypothesis (Lmax) / final entries (nbest_cap).  A stopped
+ *      utterance costs nothing further; its outputs are not written.
+ *   Outputs of an ended utterance: out_count [B] (whole) the final kept entries, in kept order (the reference's list is
+ *      these sorted by ascending score, stably); out_scores f64, out_lens i32 [B][nbest_cap] the first out_count[b];
+ *      out_tokens [B][nbest_cap][Lmax] i32 the first out_lens of each (the leading blank included), rebuilt on the device
+ *      from the hypotheses' back-pointers.
+ *   Test hook (NULL: none): step_logp [B][vocab] f32 the log-probability rows of the call's last step, step_trace
+ *      [B][4 + Lmax] i32 = { 1, frame, carried, length, labels.. } of the hypothesis expanded there, for the utterances
+ *      that took the step only.
+ *   Capacities (em_transducer_beam_limits: largest beam, open entries, kept entries, expansions of one frame, labels of a
+ *      hypothesis) are sized for trained models, whose frames end after about `beam` expansions.  B <= 64, beam <= the
+ *      limit, Lmax <= the label limit, nbest_cap <= the kept limit and ws of at least
+ *      em_transducer_beam_workspace_bytes(dtype, w, B, T, beam) bytes (0 for refused arguments): EM_ERR_UNSUPPORTED
+ *      otherwise, before any launch.  What ws holds on entry of a first call is ignored ("Scratch memory" above).        */
+int em_transducer_beam_search(int dtype, const EmTransducerWeights* w, const float* enc_proj, const int32_t* olens, int32_t B,
+                              int32_t T, int32_t beam, int32_t max_expansions, int32_t Lmax, int32_t nbest_cap,
+                              int32_t first, int32_t steps, int32_t* status, int32_t* out_tokens, int32_t* out_lens,
+                              double* out_scores, int32_t* out_count, float* step_logp, int32_t* step_trace, void* ws,
+                              size_t ws_bytes, void* stream);
+size_t em_transducer_beam_workspace_bytes(int dtype, const EmTransducerWeights* w, int32_t B, int32_t T, int32_t beam);
+void em_transducer_beam_limits(int32_t* beam_max, int32_t* open_max, int32_t* kept_max, int32_t* expansions_max,
+                               int32_t* labels_max);
 
 /* ---- transducer likelihood of given transcripts (csrc/transducer_nll.hip): log p(y | x) of a ragged batch of N candidate
  *      transcripts, the forward value of the RNN-T loss (espnet2/asr/espnet_model.py `_calc_transducer_loss`), in two
