@@ -79,17 +79,12 @@ constexpr int TILE_OFF = TOUCH_OFF + 1024;                   // 32 KiB: the dept
 constexpr int ABUF_OFF = TILE_OFF + 32768;                   // 16 KiB: LN(x) as four [32][64] k-tiles
 constexpr int WK_OFF = ABUF_OFF + 16384;                     // 32 KiB: depthwise conv weights [31][256] f32 (tap-major) + bias [256]
 constexpr int XCH_OFF = WK_OFF + 32768;                      // the FFN's hand-over slots (16 KiB, HX_*); the attention phase's rel-shift scratch (42 KiB), the folded C part (40 KiB)
-#ifndef EM_BLOCK_VAR
-#define EM_BLOCK_VAR 0  // developer A/B builds (tools/build_block_variants.sh)
-#endif
 // Round 13: the FFN's waves exchange the HIDDEN tile once per chunk pair (8 KiB of bf16 per pair and workgroup, under the
 // loop's waits for weight lines) instead of their K-split partial sums behind the loop (96 KiB of f32 written, 96 KiB read
-// and a barrier on the exit path of every module).  -DEM_BLOCK_VAR=0x80000 builds the round-3 exit path again (A/B).
-constexpr bool FFN_HANDOVER = (EM_BLOCK_VAR & 0x80000) == 0;
+// and a barrier on the exit path of every module; profiles/r13a_bench_pair.txt, HISTORY.md section H).
 constexpr int HX_OFF = XCH_OFF;                              // [2 buffers][4 source waves][2 frame halves][64 lanes] 16 B: the pair's hidden tile, lane-major
 constexpr int HX_BUF = 8192, HX_SLICE = 2048;
-constexpr int XSLOT = 8192;                                  // (0x80000 builds) one (destination wave, source wave) slot of the reduction: [4 fragments][2 halves][64 lanes] f32x4, 96 KiB from ABUF on
-constexpr int SMEM_BYTES = XCH_OFF + (FFN_HANDOVER ? 45056 : 49152);  // 155 KiB (0x80000 builds: 159 KiB)
+constexpr int SMEM_BYTES = XCH_OFF + 45056;                  // 155 KiB
 static_assert(ABUF_OFF % 1024 == 0 && TILE_OFF % 1024 == 0 && SMEM_BYTES <= 160 * 1024, "LDS layout");
 static_assert(HX_OFF + 2 * HX_BUF <= SMEM_BYTES && XCH_OFF + 4 * (2 * 16 * 84) * 4 <= SMEM_BYTES, "hand-over slots, attention scratch");
 constexpr int KW_MAX = 31, TROWS_MAX = BM + KW_MAX - 1;  // depthwise conv: kernel width is a template argument (31: the
@@ -118,7 +113,10 @@ constexpr int BAR_UNIT = 1, BAR_PARAMS = 2, BAR_TILE = 4, BAR_LAST = 8;  // what
 // GB/s, and the LDS-DMA ring this kernel used before (DMA write + fragment read = 64 KB of LDS traffic per unit, a
 // barrier per unit, four loader waves) ~0.43 us per unit.
 #ifndef EM_BLOCK_DBG
-#define EM_BLOCK_DBG 0  // developer builds: 1 = no MFMA / epilogue work (what does the streaming cost alone?)
+// developer timing builds, wrong results by design (tools/build_block_variants.sh); bits: 1 = no MFMA / epilogue work (what
+// does the streaming cost alone?); the attention phase: 128 = no exponentials, 256 = no rel-shift
+// scratch round trip, 512 = the operand requests of tile 0 only
+#define EM_BLOCK_DBG 0
 #endif
 
 #ifndef EM_BLOCK_FINE
@@ -224,7 +222,7 @@ __global__ __launch_bounds__(NT, 1) void block_kernel(const EmBlockArgs a_in, lo
   // FFN (streaming instantiations) this workgroup's share of them
   const int nch = (((a.ff >> 6) + 1) & ~1) / nsplit;
   // developer profiling (EM_BLOCK_STAMPS / EM_BLOCK_DBG, tools/block_bench.py): stage-level cycle stamps of thread 0
-  // of workgroup (0, 0); dbg 1 = no MFMA / epilogue work, dbg 2 = no DMA
+  // of workgroup (0, 0)
   int nts = 0;
   // stamp(code): (code << 56) | cycle counter.  Codes: 1 kernel entry, 2 D prologue inputs requested, 3 inputs landed (tile
   // stored), 4 tile barrier passed, 5 conv computed, 6 conv output stored, 7 activations loaded, 10 pointwise_conv2 done,
@@ -248,11 +246,9 @@ __global__ __launch_bounds__(NT, 1) void block_kernel(const EmBlockArgs a_in, lo
     if constexpr (EM_BLOCK_FINE || RELU) stamp(code);
   };
   stamp(1);
-  int nbar = 0;  // barriers passed
   // every barrier goes through here: retire own LDS operations, synchronise
   auto bar = [&](int code) __attribute__((always_inline)) {  // `code` documents what the barrier is for
     (void)code;
-    ++nbar;
     EM_LGKM0();
     __builtin_amdgcn_s_barrier();
   };
@@ -281,27 +277,13 @@ __global__ __launch_bounds__(NT, 1) void block_kernel(const EmBlockArgs a_in, lo
   // are written through a buffer resource whose range ends with frame T - 1 of THAT utterance, unconditionally: a masked
   // lane's offset lies past the range and the memory pipeline drops its store (csrc/subsample2.hip stores the same way).
   // No clamped address: a tail row's values differ from frame T - 1's (its depthwise-conv window differs).
-  // Round 12 (profiles/r12a_switch_ab.txt, r12a_bench_pair.txt; B = 32 x 10 s, the default bench line, ms per step, builds
-  // taken round-robin in one call on one box):
-  //   x of the A part behind the macaron module, x of the C part behind linear_out (this build)  0.877 - 0.882
-  //   the parent commit (both stored at the end of the kernel, under row_ok)                     0.900 - 0.904
-  //   -DEM_BLOCK_VAR=0x30000 (both switches below)                                               0.898 - 0.905
-  //   -DEM_BLOCK_VAR=0x10000: the A part's x at the end again   0.899 - 0.903 against 0.880 - 0.882 in that call
-  //   -DEM_BLOCK_VAR=0x20000: the C part's x at the end again   0.884 - 0.886 against 0.880 - 0.882
-  //   -DEM_BLOCK_VAR=0x40000: the GLU stores counted as well    0.880 - 0.882 against 0.880 - 0.883: no gain, not built in
-  // Tried and taken out again, no faster: block<D|FINAL|CTC> with the CTC head's units 0 - 2 requested inside the
-  // feed-forward module and enc_out / enc_act stored counted behind them (kernel 50.8 against 50.7 us, step 0.880 -
-  // 0.882 with and without it: the walk's waits, joined over its loop, give the stores two units' time, and they are
-  // one launch of 25); the A part's x behind norm_mha's normalisation instead of in front of the LayerNorm (0.892 -
-  // 0.898 against 0.885 - 0.888 in that call), and half of it either side (0.891 - 0.895).
+  // Round 12: in these instantiations x of the A part is stored this way behind the macaron module and x of the C part
+  // behind linear_out, not at the end of the kernel under row_ok: 0.877 - 0.882 against 0.900 - 0.904 ms per step
+  // (profiles/r12a_switch_ab.txt, r12a_bench_pair.txt; each store's share and what else was tried: HISTORY.md section H).
   constexpr bool PLAIN = !RELU && !FOLD;
-  constexpr bool X_EARLY_A = PLAIN && HAS_A && !(EM_BLOCK_VAR & 0x10000);
-  constexpr bool X_EARLY_C = PLAIN && HAS_C && !(EM_BLOCK_VAR & 0x20000);
-  constexpr bool GLU_COUNTED = PLAIN && HAS_C && (EM_BLOCK_VAR & 0x40000) != 0;
-  typedef __attribute__((ext_vector_type(2))) unsigned su32x2;
   typedef __attribute__((ext_vector_type(4))) unsigned su32x4;
   constexpr unsigned ROW_MASKED = 0x80000000u;  // (the host refuses T * 1 KiB >= 2 GiB: past every range, and no wrap-around with the column offsets added)
-  // byte offset of (frame mi * 16 + lr, column ncol) in the utterance's [T][256] f32 rows (bf16 rows: half of it)
+  // byte offset of (frame mi * 16 + lr, column ncol) in the utterance's [T][256] f32 rows
   unsigned rowoff[2];
 #pragma unroll
   for (int mi = 0; mi < 2; ++mi) rowoff[mi] = row_ok[mi] ? (unsigned)(t0 + mi * 16 + lr) * (D * 4u) + ncol * 4u : ROW_MASKED;
@@ -311,9 +293,6 @@ __global__ __launch_bounds__(NT, 1) void block_kernel(const EmBlockArgs a_in, lo
   };
   auto put_f32x4 = [&](__amdgpu_buffer_rsrc_t rs, int mi, int f, const float4& v) __attribute__((always_inline)) {
     __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(su32x4, v), rs, rowoff[mi] + 256 * f, 0, 0);
-  };
-  auto put_bf16x4 = [&](__amdgpu_buffer_rsrc_t rs, int mi, int f, const bf16x4& v) __attribute__((always_inline)) {
-    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(su32x2, v), rs, (rowoff[mi] >> 1) + 128 * f, 0, 0);
   };
   auto store_x_counted = [&]() __attribute__((always_inline)) {
     const __amdgpu_buffer_rsrc_t rs = rows_rsrc(xdst, 4);
@@ -392,7 +371,7 @@ __global__ __launch_bounds__(NT, 1) void block_kernel(const EmBlockArgs a_in, lo
   // ingests 64 B/clk and the queue is short), during which the wave's LayerNorm arithmetic waited behind them although it
   // needs none of them: every hand-over between two GEMMs cost stream time + LayerNorm time (4 - 6 K cycles, profiles/
   // r03b_block_stamps_fine.txt) instead of the larger of the two.  sched_group_barrier pins the deal: left alone hipcc
-  // clusters the loads first.
+  // clusters the loads first (the deal against the cluster: profiles/r05b_ln_handover_ab.txt, HISTORY.md section H).
   auto no_pre = [] {};
   auto ln_stats = [&](float mean[2], float rstd[2], int code, auto&& pre1, auto n1c) __attribute__((always_inline)) {
     constexpr int N1 = decltype(n1c)::value;
@@ -400,7 +379,7 @@ __global__ __launch_bounds__(NT, 1) void block_kernel(const EmBlockArgs a_in, lo
     ++nln;
     pre1();
     ln_partials(xr, red);
-    if constexpr (N1 > 0 && !(EM_BLOCK_VAR & 32)) {
+    if constexpr (N1 > 0) {
 #pragma unroll
       for (int i = 0; i < N1; ++i) {
         __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);               // one weight request
@@ -447,7 +426,7 @@ __global__ __launch_bounds__(NT, 1) void block_kernel(const EmBlockArgs a_in, lo
         bf16x4 pk = {(bf16)y[mi][f].x, (bf16)y[mi][f].y, (bf16)y[mi][f].z, (bf16)y[mi][f].w};
         *(bf16x4*)(abuf + f * 4096 + mi * 2048 + tile_wr) = pk;
       }
-    if constexpr (N2 > 0 && !(EM_BLOCK_VAR & 32)) {
+    if constexpr (N2 > 0) {
 #pragma unroll
       for (int i = 0; i < N2; ++i) {
         __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
@@ -568,7 +547,6 @@ __global__ __launch_bounds__(NT, 1) void block_kernel(const EmBlockArgs a_in, lo
           : "memory");
     }
   };
-  auto touch_done = [&]() __attribute__((always_inline)) {};
   // Round 5, launches that do not fill the chip (a tick of a batch of streams: 64 workgroups; one stream: 2): the launcher
   // adds HELPER workgroups (rows of the grid past a.B) on the idle CUs.  A helper takes its share of the warm-up and leaves.
   // Without them the few workgroups of an XCD touch the launch's whole list themselves - 10 to 16 wave-wide requests per wave,
@@ -648,7 +626,7 @@ __global__ __launch_bounds__(NT, 1) void block_kernel(const EmBlockArgs a_in, lo
   // The weight stream is unchanged in bytes: per pair and wave 2 x 8 KiB of W1 (ring[0], ring[1]) and 2 x 8 KiB of
   // W2 (ring[2], ring[3]); a ring slot is refilled as soon as its 16 MFMAs are issued, i.e. requested one whole
   // iteration (64 MFMAs) ahead of its use.  The host pads odd chunk counts with a zero chunk (nch is even here).
-  // Round 13 (FFN_HANDOVER): the loop is not MFMA-bound, as round 3 believed, but waits for weight lines for 0.7 - 1 K of
+  // Round 13: the loop is not MFMA-bound, as round 3 believed, but waits for weight lines for 0.7 - 1 K of
   // every 2.3 K-cycle iteration, and the K-split's meeting BEHIND the loop - 96 KiB of f32 written, a barrier, 96 KiB read,
   // the residual un-parked: 2.2 - 4.7 K cycles per module, 24 modules per step - hides under nothing.  So the exchange
   // moves to the hidden tile: per pair every wave stores its B fragments (2 x 16 B per lane, 8 KiB per workgroup) into a
@@ -660,17 +638,11 @@ __global__ __launch_bounds__(NT, 1) void block_kernel(const EmBlockArgs a_in, lo
   // (profiles/r13a_block_stamps_fine.txt), 15 -> 22 of the slowest wave: 24.2 - 24.8 K -> 22.2 - 22.4 K cycles (the D part's
   // module), 23.5 - 24.0 K -> 21.2 K (the macaron module); the step 0.876 - 0.882 -> 0.861 - 0.867 ms (profiles/r13a_bench_pair.txt).
   auto read_w2 = [&](const void* w2, int p, int half, WF& w) __attribute__((always_inline)) {
-    if constexpr (FFN_HANDOVER) {
-      // the same 1 KiB lines pair[p][source slice s][fragment f], dealt by OUTPUT columns: this wave's fragments f = 4 f4 + nf
-      // of the source slices 2 half, 2 half + 1 (q = 4 (s & 1) + f4)
-      GU8 su = (GU8)w2 + (size_t)p * (2 * UNIT) + half * 32768 + nf * 1024 + lane * 16;
+    // the 1 KiB lines pair[p][source slice s][fragment f], dealt by OUTPUT columns: this wave's fragments f = 4 f4 + nf
+    // of the source slices 2 half, 2 half + 1 (q = 4 (s & 1) + f4)
+    GU8 su = (GU8)w2 + (size_t)p * (2 * UNIT) + half * 32768 + nf * 1024 + lane * 16;
 #pragma unroll
-      for (int q = 0; q < 8; ++q) w.v[q] = *(GFRAG)(su + (q >> 2) * 16384 + (q & 3) * 4096);
-    } else {
-      GU8 su = (GU8)w2 + (size_t)p * (2 * UNIT) + nf * 16384 + half * 8192 + lane * 16;
-#pragma unroll
-      for (int q = 0; q < 8; ++q) w.v[q] = *(GFRAG)(su + q * 1024);
-    }
+    for (int q = 0; q < 8; ++q) w.v[q] = *(GFRAG)(su + (q >> 2) * 16384 + (q & 3) * 4096);
   };
   auto ffn_pre = [&](const void* w1, const void* w2) __attribute__((always_inline)) {
     read_unit(w1, 0, ring[0]);
@@ -705,18 +677,11 @@ __global__ __launch_bounds__(NT, 1) void block_kernel(const EmBlockArgs a_in, lo
     f32x4 acc2[16][2];
 #pragma unroll
     for (int f = 0; f < 16; ++f) acc2[f][0] = acc2[f][1] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    // Round-3 form: the residual is not needed until the end, its 32 registers are parked in LDS (the conv tile's space,
-    // lane-major: conflict-free, private to the lane, no barrier).  Hand-over form: the registers are there (the worst
-    // instantiation takes 446 of 512, no scratch) and x stays in them - parked it measured 0.873 - 0.874 ms per batch against
-    // 0.868 - 0.870 (profiles/r13a_handover_ab.txt); `xpark` is still where a caller with `repark` finds x afterwards.
+    // The residual stays in its 32 registers through the module (the worst instantiation takes 446 of 512, no scratch):
+    // parked in LDS it measured 0.873 - 0.874 ms per batch against 0.868 - 0.870 (profiles/r13a_handover_ab.txt).  `xpark`
+    // (the conv tile's space, lane-major: conflict-free, private to the lane, no barrier) is where a caller with `repark`
+    // finds x afterwards.
     float4* const xpark = (float4*)(smem + TILE_OFF) + tid;
-    constexpr bool PARK = !FFN_HANDOVER;
-    if constexpr (PARK) {
-#pragma unroll
-      for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-        for (int f = 0; f < 4; ++f) xpark[(mi * 4 + f) * NT] = xr[mi][f];
-    }
     // bias + Swish + bf16 of the two chunks' 16 hidden columns of this wave -> the B fragments of the pair
     auto swish_pack = [&](const f32x4 h[2][2], int p, bf16x8 hb[2]) __attribute__((always_inline)) {
       float4 b0, b1;
@@ -737,15 +702,14 @@ __global__ __launch_bounds__(NT, 1) void block_kernel(const EmBlockArgs a_in, lo
                           (bf16)act_(h[1][mi][0] + b1.x), (bf16)act_(h[1][mi][1] + b1.y),
                           (bf16)act_(h[1][mi][2] + b1.z), (bf16)act_(h[1][mi][3] + b1.w)};
     };
-    // 16 MFMAs of a W2 sub-unit.  Round 3 form: output fragments 8 half .. 8 half + 7 of this wave's own hidden slice.
-    // Hand-over form: this wave's four output fragments against the source slices 2 half, 2 half + 1; one accumulator set
-    // per source slice, acc2[4 s + f4], so that every set sees the operands, in the order, of slice s's partial sum in the
-    // round-3 form and the closing sum below is reduce_as's: the same bits.
-    auto mma_w2 = [&](const WF& w, int half, const bf16x8 (*hv)[2]) __attribute__((always_inline)) {
+    // 16 MFMAs of a W2 sub-unit: this wave's four output fragments against the source slices 2 half, 2 half + 1; one
+    // accumulator set per source slice, acc2[4 s + f4], so that every set sees the operands, in the order, of slice s's
+    // partial sum in the round-3 K-split and the closing sum below adds them in its order: the same bits.
+    auto mma_w2 = [&](const WF& w, int half, const bf16x8 hv[4][2]) __attribute__((always_inline)) {
       if constexpr (dbg & 1) return;
 #pragma unroll
       for (int q = 0; q < 8; ++q) {
-        const bf16x8* const b = FFN_HANDOVER ? hv[2 * half + (q >> 2)] : hv[0];
+        const bf16x8* const b = hv[2 * half + (q >> 2)];
         acc2[half * 8 + q][0] = MM::mma(w.v[q], b[0], acc2[half * 8 + q][0]);
         acc2[half * 8 + q][1] = MM::mma(w.v[q], b[1], acc2[half * 8 + q][1]);
       }
@@ -764,60 +728,33 @@ __global__ __launch_bounds__(NT, 1) void block_kernel(const EmBlockArgs a_in, lo
         for (int mi = 0; mi < 2; ++mi) hv[s][mi] = *(const bf16x8*)(hx + buf * HX_BUF + s * HX_SLICE + mi * 1024);
     };
     f32x4 h[2][2];
-    bf16x8 hb[1][2];
+    bf16x8 hb[2];
     mma_k(ring[0], false, h[0]);
     read_w1(2, ring[0]);
     mma_k(ring[1], false, h[1]);
     read_w1(3, ring[1]);
-    swish_pack(h, 0, hb[0]);
-    if constexpr (FFN_HANDOVER) {
-      // Iteration p: the W1 MFMAs of pair p + 1, the MEETING (barrier, then the four slices of pair p's tile from buffer
-      // p & 1), the W2 MFMAs of pair p with Swish and the store of pair p + 1's own slice into buffer (p + 1) & 1 among them.
-      // One barrier per pair is enough with two buffers: buffer (p + 1) & 1 was last read behind the meeting of iteration
-      // p - 1, and a wave passes the meeting of iteration p - the one in front of this store - only when every wave has
-      // arrived there with those reads retired (bar() waits for the wave's own LDS operations: the hardware barrier alone
-      // does not, see gemm.hip); the meeting of iteration p + 1 then publishes the store.  The first tile is written before
-      // any barrier of the module: nothing else touches XCH between the barriers of the LayerNorm in front and the end of
-      // the module, and the last tile's reads are consumed before the barriers of the LayerNorm behind.
-      // Where the meeting sits was measured (profiles/r13a_handover_ab.txt, ms per batch of the default bench line, the
-      // parent 0.880 - 0.884 in that call): behind BOTH W1 units, as here, 0.873 - 0.874 - a wave arrives at the barrier 32
-      // MFMAs and their waits for weight lines after its store, so nobody waits for a store, and only the first reads' LDS
-      // latency is exposed; at the END of the iteration, the reads under the next pair's W1 MFMAs, 0.883 - 0.885 (the store
-      // comes last, behind the Swish tail: every wave waits there with an empty matrix pipe, 20 -> 21 grew by what 21 -> 22
-      // lost); between the two W1 units 0.896 - 0.899.  The two scheduling fences keep hipcc from moving instructions
-      // across the meeting: without them the line is 0.880 - 0.883 against 0.859 - 0.863 with them (measured; which
-      // instructions it moves was not looked at).
-      bf16x8 hv[4][2];
-      auto meet = [&](int buf) __attribute__((always_inline)) {
-        __builtin_amdgcn_sched_barrier(0);
-        bar(0);
-        hx_get(buf, hv);
-        __builtin_amdgcn_sched_barrier(0);
-      };
-      hx_put(0, hb[0]);
-      rstamp(20);
-      // (requests UNCONDITIONAL, as below)
-#pragma unroll 1
-      for (int p = 0; p + 1 < np; ++p) {
-        mma_k(ring[0], false, h[0]);                             // chunk 2p + 2
-        read_w1(2 * p + 4, ring[0]);
-        mma_k(ring[1], false, h[1]);                             // chunk 2p + 3
-        read_w1(2 * p + 5, ring[1]);
-        meet(p & 1);
-        mma_w2(ring[2], 0, hv);                                  // pair p, source slices 0, 1
-        read_w2(w2, p + 1, 0, ring[2]);
-        swish_pack(h, p + 1, hb[0]);
-        hx_put((p + 1) & 1, hb[0]);
-        mma_w2(ring[3], 1, hv);                                  // source slices 2, 3
-        read_w2(w2, p + 1, 1, ring[3]);
-      }
-      meet((np - 1) & 1);
-      mma_w2(ring[2], 0, hv);                                    // the last pair
-      mma_w2(ring[3], 1, hv);
-    } else {  // (-DEM_BLOCK_VAR=0x80000: the round-3 loop, kept for A/B; its lines stand as they did)
-    // every wave holds its activation fragments and has read the conv weights: ABUF / WK may receive partial sums
-    // from a wave that finishes early (the only barrier of the FFN besides the reduction's)
-    bar(0);
+    swish_pack(h, 0, hb);
+    // Iteration p: the W1 MFMAs of pair p + 1, the MEETING (barrier, then the four slices of pair p's tile from buffer
+    // p & 1), the W2 MFMAs of pair p with Swish and the store of pair p + 1's own slice into buffer (p + 1) & 1 among them.
+    // One barrier per pair is enough with two buffers: buffer (p + 1) & 1 was last read behind the meeting of iteration
+    // p - 1, and a wave passes the meeting of iteration p - the one in front of this store - only when every wave has
+    // arrived there with those reads retired (bar() waits for the wave's own LDS operations: the hardware barrier alone
+    // does not, see gemm.hip); the meeting of iteration p + 1 then publishes the store.  The first tile is written before
+    // any barrier of the module: nothing else touches XCH between the barriers of the LayerNorm in front and the end of
+    // the module, and the last tile's reads are consumed before the barriers of the LayerNorm behind.
+    // The meeting sits behind BOTH W1 units: a wave arrives at the barrier 32 MFMAs and their waits for weight lines after
+    // its store, so nobody waits for a store, and only the first reads' LDS latency is exposed (the other two places
+    // measured slower: profiles/r13a_handover_ab.txt, HISTORY.md section H).  The two scheduling fences keep hipcc from
+    // moving instructions across the meeting: without them the line is 0.880 - 0.883 against 0.859 - 0.863 with them
+    // (measured; which instructions it moves was not looked at).
+    bf16x8 hv[4][2];
+    auto meet = [&](int buf) __attribute__((always_inline)) {
+      __builtin_amdgcn_sched_barrier(0);
+      bar(0);
+      hx_get(buf, hv);
+      __builtin_amdgcn_sched_barrier(0);
+    };
+    hx_put(0, hb);
     rstamp(20);
     // The requests are UNCONDITIONAL (past the end they repeat the last unit, which nobody waits for): a load under
     // a branch makes hipcc's wait-count pass assume it may not have been issued, and every wait for an older load
@@ -828,94 +765,42 @@ __global__ __launch_bounds__(NT, 1) void block_kernel(const EmBlockArgs a_in, lo
       read_w1(2 * p + 4, ring[0]);
       mma_k(ring[1], false, h[1]);                             // chunk 2p + 3
       read_w1(2 * p + 5, ring[1]);
-      mma_w2(ring[2], 0, hb);                                  // pair p
+      meet(p & 1);
+      mma_w2(ring[2], 0, hv);                                  // pair p, source slices 0, 1
       read_w2(w2, p + 1, 0, ring[2]);
-      mma_w2(ring[3], 1, hb);
+      swish_pack(h, p + 1, hb);
+      hx_put((p + 1) & 1, hb);
+      mma_w2(ring[3], 1, hv);                                  // source slices 2, 3
       read_w2(w2, p + 1, 1, ring[3]);
-      swish_pack(h, p + 1, hb[0]);
     }
-    mma_w2(ring[2], 0, hb);                                    // the last pair
-    mma_w2(ring[3], 1, hb);
-    }
+    meet((np - 1) & 1);
+    mma_w2(ring[2], 0, hv);                                    // the last pair
+    mma_w2(ring[3], 1, hv);
     after();
     rstamp(21);
     float4 psum[2][4];  // (split FFN, streaming instantiations: this share's partial sum)
-    if constexpr (FFN_HANDOVER) {
-      // ---- this wave holds, per source slice, what that slice's wave used to hand it: added in slice order 0, 1, 2, 3
-      // (reduce_as's order), in registers, no barrier
+    // ---- this wave holds, per source slice, what that slice's wave handed it in the round-3 K-split: added in slice order
+    // 0, 1, 2, 3 (that exchange's order), in registers, no barrier
 #pragma unroll
-      for (int f4 = 0; f4 < 4; ++f4) {
-        const float4 b4 = *(const float4*)(pb + b2o + 64 * f4 + ncol);
+    for (int f4 = 0; f4 < 4; ++f4) {
+      const float4 b4 = *(const float4*)(pb + b2o + 64 * f4 + ncol);
 #pragma unroll
-        for (int mi = 0; mi < 2; ++mi) {
-          f32x4 sum = acc2[f4][mi];
+      for (int mi = 0; mi < 2; ++mi) {
+        f32x4 sum = acc2[f4][mi];
 #pragma unroll
-          for (int src = 1; src < 4; ++src) sum = sum + acc2[4 * src + f4][mi];
-          if constexpr (RELU) {
-            if (nsplit > 1) {  // (split FFN: the partial sum of THIS workgroup's share; finished below, behind the meeting point)
-              psum[mi][f4] = make_float4(sum[0], sum[1], sum[2], sum[3]);
-              continue;
-            }
+        for (int src = 1; src < 4; ++src) sum = sum + acc2[4 * src + f4][mi];
+        if constexpr (RELU) {
+          if (nsplit > 1) {  // (split FFN: the partial sum of THIS workgroup's share; finished below, behind the meeting point)
+            psum[mi][f4] = make_float4(sum[0], sum[1], sum[2], sum[3]);
+            continue;
           }
-          xr[mi][f4].x += scale * (sum[0] + b4.x);
-          xr[mi][f4].y += scale * (sum[1] + b4.y);
-          xr[mi][f4].z += scale * (sum[2] + b4.z);
-          xr[mi][f4].w += scale * (sum[3] + b4.w);
-          if (repark) xpark[(mi * 4 + f4) * NT] = xr[mi][f4];  // the caller stores x from here at the very end of the kernel
         }
+        xr[mi][f4].x += scale * (sum[0] + b4.x);
+        xr[mi][f4].y += scale * (sum[1] + b4.y);
+        xr[mi][f4].z += scale * (sum[2] + b4.z);
+        xr[mi][f4].w += scale * (sum[3] + b4.w);
+        if (repark) xpark[(mi * 4 + f4) * NT] = xr[mi][f4];  // the caller stores x from here at the very end of the kernel
       }
-    } else {  // (-DEM_BLOCK_VAR=0x80000: the round-3 exit path)
-    // ---- the four partial sums meet: wave w keeps the output fragments f = 4 f4 + w (its columns of the residual
-    // layout) and hands the other twelve to their owners through 8 KiB slots (destination, source); summed in wave
-    // order 0, 1, 2, 3 whatever the arrival order: deterministic
-    auto reduce_as = [&](auto nfc) __attribute__((always_inline)) {
-      constexpr int NF = decltype(nfc)::value;
-#pragma unroll
-      for (int dst = 0; dst < 4; ++dst) {
-        if (dst == NF) continue;
-        unsigned char* slot = smem + ABUF_OFF + (dst * 3 + (NF > dst ? NF - 1 : NF)) * XSLOT + lane * 16;
-#pragma unroll
-        for (int f4 = 0; f4 < 4; ++f4)
-#pragma unroll
-          for (int mi = 0; mi < 2; ++mi) *(f32x4*)(slot + (f4 * 2 + mi) * 1024) = acc2[4 * f4 + dst][mi];
-      }
-      bar(0);
-#pragma unroll
-      for (int f4 = 0; f4 < 4; ++f4) {
-        const float4 b4 = *(const float4*)(pb + b2o + 64 * f4 + ncol);
-#pragma unroll
-        for (int mi = 0; mi < 2; ++mi) {
-          f32x4 sum;
-          bool first = true;
-#pragma unroll
-          for (int src = 0; src < 4; ++src) {
-            f32x4 v;
-            if (src == NF) v = acc2[4 * f4 + NF][mi];
-            else v = *(const f32x4*)(smem + ABUF_OFF + (NF * 3 + (src > NF ? src - 1 : src)) * XSLOT + lane * 16 + (f4 * 2 + mi) * 1024);
-            sum = first ? v : sum + v;
-            first = false;
-          }
-          if constexpr (RELU) {
-            if (nsplit > 1) {  // (split FFN: the partial sum of THIS workgroup's share; finished below, behind the meeting point)
-              psum[mi][f4] = make_float4(sum[0], sum[1], sum[2], sum[3]);
-              continue;
-            }
-          }
-          xr[mi][f4] = xpark[(mi * 4 + f4) * NT];
-          xr[mi][f4].x += scale * (sum[0] + b4.x);
-          xr[mi][f4].y += scale * (sum[1] + b4.y);
-          xr[mi][f4].z += scale * (sum[2] + b4.z);
-          xr[mi][f4].w += scale * (sum[3] + b4.w);
-          if (repark) xpark[(mi * 4 + f4) * NT] = xr[mi][f4];  // the caller stores x from here at the very end of the kernel
-        }
-      }
-    };
-    switch (nf) {
-      case 0: reduce_as(std::integral_constant<int, 0>{}); break;
-      case 1: reduce_as(std::integral_constant<int, 1>{}); break;
-      case 2: reduce_as(std::integral_constant<int, 2>{}); break;
-      default: reduce_as(std::integral_constant<int, 3>{}); break;
-    }
     }
     if constexpr (RELU) {
       if (nsplit > 1) {
@@ -928,48 +813,23 @@ __global__ __launch_bounds__(NT, 1) void block_kernel(const EmBlockArgs a_in, lo
         const int wg = b * (int)gridDim.x + (ATT ? t0 / BM : (int)blockIdx.x);  // (ATT: the workgroups of a group of eight blocks are dealt anew, see the top)
         float4* const part = (float4*)a.ffn_part + ((size_t)wg * nsplit) * 8 * NT;
         float4* const mine = part + (size_t)blockIdx.z * 8 * NT + tid;
-        // Developer builds (profiles/r06u_stream_seam_ab*.txt): EM_BLOCK_VAR & 8192 = agent-scope (sc1) stores and no release
-        // fence, & 4096 = agent-scope loads and no acquire fence.  One stream: 661 us per call as built, 679 - 697 with either;
-        // 32 streams: 823 against 802 - 807 with the sc1 stores (the release fence writes back what the XCD's OTHER
-        // workgroups have dirtied).  The fenced form is the documented one and stays.
-        constexpr bool SEAM_ST_PLAIN = (EM_BLOCK_VAR & 8192) == 0, SEAM_LD_PLAIN = (EM_BLOCK_VAR & 4096) == 0;
-        constexpr bool SEAM_REL = SEAM_ST_PLAIN, SEAM_ACQ = SEAM_LD_PLAIN;
-        auto put = [&](float4* p, const float4& v) __attribute__((always_inline)) {
-          if constexpr (SEAM_ST_PLAIN) {
-            *p = v;
-          } else {  // agent-scope relaxed stores (sc1: written through this XCD's L2)
-            __hip_atomic_store((unsigned long long*)p, ((const unsigned long long*)&v)[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store((unsigned long long*)p + 1, ((const unsigned long long*)&v)[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          }
-        };
-        auto get = [&](const float4* p) __attribute__((always_inline)) -> float4 {
-          if constexpr (SEAM_LD_PLAIN) {
-            return *p;
-          } else {  // agent-scope relaxed loads (sc1: past whatever this XCD's L2 holds of an earlier launch's partial sums)
-            unsigned long long w[2];
-            w[0] = __hip_atomic_load((const unsigned long long*)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            w[1] = __hip_atomic_load((const unsigned long long*)p + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            float4 v;
-            __builtin_memcpy(&v, w, 16);
-            return v;
-          }
-        };
+        // Plain stores and loads with a release and an acquire fence: the documented form, and it stays.  Agent-scope (sc1)
+        // stores or loads without the fences were slower for one stream and a little faster for 32
+        // (profiles/r06u_stream_seam_ab*.txt, HISTORY.md section H).
 #pragma unroll
         for (int mi = 0; mi < 2; ++mi)
 #pragma unroll
-          for (int f4 = 0; f4 < 4; ++f4) put(mine + (mi * 4 + f4) * NT, psum[mi][f4]);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (acknowledged: at the memory side for the sc1 stores)
+          for (int f4 = 0; f4 < 4; ++f4) mine[(mi * 4 + f4) * NT] = psum[mi][f4];
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         bar(0);
         int* const flag = (int*)(red0 + 480);  // (a word of the LayerNorm exchange area nobody uses at this point)
         if (tid == 0) {
-          if constexpr (SEAM_REL) {
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-          }
+          __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
           const int t = __hip_atomic_fetch_add(a.ffn_ticket + wg, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
           if (t == nsplit - 1) {
             __hip_atomic_store(a.ffn_ticket + wg, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // every share has arrived
-            if constexpr (SEAM_ACQ) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
           }
           *flag = t;
         }
@@ -993,7 +853,7 @@ __global__ __launch_bounds__(NT, 1) void block_kernel(const EmBlockArgs a_in, lo
 #pragma unroll
               for (int sp = 0; sp < SU; ++sp)
 #pragma unroll
-                for (int f4 = 0; f4 < 4; ++f4) v[sp][f4] = get(part + ((size_t)sp * 8 + (mi * 4 + f4)) * NT + tid);
+                for (int f4 = 0; f4 < 4; ++f4) v[sp][f4] = part[((size_t)sp * 8 + (mi * 4 + f4)) * NT + tid];
 #pragma unroll
               for (int sp = 0; sp < SU; ++sp)
 #pragma unroll
@@ -1004,14 +864,13 @@ __global__ __launch_bounds__(NT, 1) void block_kernel(const EmBlockArgs a_in, lo
               for (int sp = 0; sp < nsplit; ++sp)
 #pragma unroll
                 for (int f4 = 0; f4 < 4; ++f4) {
-                  const float4 v = get(part + ((size_t)sp * 8 + (mi * 4 + f4)) * NT + tid);
+                  const float4 v = part[((size_t)sp * 8 + (mi * 4 + f4)) * NT + tid];
                   tot[f4].x += v.x; tot[f4].y += v.y; tot[f4].z += v.z; tot[f4].w += v.w;
                 }
             }
 #pragma unroll
             for (int f4 = 0; f4 < 4; ++f4) {
               const float4 b4 = *(const float4*)(pb + b2o + 64 * f4 + ncol);
-              if constexpr (PARK) xr[mi][f4] = xpark[(mi * 4 + f4) * NT];
               xr[mi][f4].x += scale * (tot[f4].x + b4.x);
               xr[mi][f4].y += scale * (tot[f4].y + b4.y);
               xr[mi][f4].z += scale * (tot[f4].z + b4.z);
@@ -1364,10 +1223,10 @@ __global__ __launch_bounds__(NT, 1) void block_kernel(const EmBlockArgs a_in, lo
           for (int n = 0; n < 4; ++n)
 #pragma unroll
             for (int mi = 0; mi < 2; ++mi) sc[mi][n] = MM::mma(kp.k[2 * n + ks], qu[mi][ks], sc[mi][n]);
-        if constexpr (!(EM_BLOCK_VAR & 512)) load_kp(jn, kp);  // (the registers are free: their MFMAs have been issued)
+        if constexpr (!(dbg & 512)) load_kp(jn, kp);  // (the registers are free: their MFMAs have been issued)
         if (jt == last) park_x();
         // rel_shift: D[c][i] -> scratch[i][c], read back at c = 15 - i + (key of the tile)
-        if constexpr (!(EM_BLOCK_VAR & 256)) {
+        if constexpr (!(dbg & 256)) {
 #pragma unroll
         for (int mi = 0; mi < 2; ++mi)
 #pragma unroll
@@ -1382,7 +1241,7 @@ __global__ __launch_bounds__(NT, 1) void block_kernel(const EmBlockArgs a_in, lo
 #pragma unroll
           for (int n = 0; n < 4; ++n)
 #pragma unroll
-            for (int r = 0; r < 4; ++r) sc[mi][n][r] += (EM_BLOCK_VAR & 256) ? dd[mi][n][r] : bdr[32 * (n >> 1) + 4 * (n & 1) + r];
+            for (int r = 0; r < 4; ++r) sc[mi][n][r] += (dbg & 256) ? dd[mi][n][r] : bdr[32 * (n >> 1) + 4 * (n & 1) + r];
           if constexpr (MASK) {
             const int kl = klen - j0 - 8 * lg;  // this lane's keys of the tile are 32 (n >> 1) + 4 (n & 1) + r < kl
 #pragma unroll
@@ -1406,11 +1265,10 @@ __global__ __launch_bounds__(NT, 1) void block_kernel(const EmBlockArgs a_in, lo
           for (int n = 0; n < 4; ++n)
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
-              // (developer timing builds, wrong results: EM_BLOCK_VAR & 128 no exponentials, & 256 no rel-shift scratch round
-              // trip, & 512 the operand requests of tile 0 only)
+              // (dbg & 128, & 256, & 512: the timing builds of EM_BLOCK_DBG, wrong results)
               const float a0 = __builtin_fmaf(sc[mi][n][2 * h], LOG2E, -mnl), a1 = __builtin_fmaf(sc[mi][n][2 * h + 1], LOG2E, -mnl);
-              const float e0 = (EM_BLOCK_VAR & 128) ? a0 : __builtin_amdgcn_exp2f(a0);
-              const float e1 = (EM_BLOCK_VAR & 128) ? a1 : __builtin_amdgcn_exp2f(a1);
+              const float e0 = (dbg & 128) ? a0 : __builtin_amdgcn_exp2f(a0);
+              const float e1 = (dbg & 128) ? a1 : __builtin_amdgcn_exp2f(a1);
               pbu[n >> 1][(n & 1) * 2 + h] = __builtin_bit_cast(unsigned, __builtin_convertvector((f32x2){e0, e1}, bf16x2));
             }
 #pragma unroll
@@ -1433,7 +1291,7 @@ __global__ __launch_bounds__(NT, 1) void block_kernel(const EmBlockArgs a_in, lo
 #pragma unroll
             for (int f = 0; f < 4; ++f) acc_o[mi][f] = MM::mma(vv.v[2 * f + jp], pb[mi][jp], acc_o[mi][f]);
           }
-        if constexpr (!(EM_BLOCK_VAR & 512)) load_v(jn, vv);
+        if constexpr (!(dbg & 512)) load_v(jn, vv);
       };
       stamp(60);
 #pragma unroll 1
@@ -1503,10 +1361,9 @@ __global__ __launch_bounds__(NT, 1) void block_kernel(const EmBlockArgs a_in, lo
     // x is final and pointwise_conv1's units 0 - 2 are in flight (requested inside linear_out): its rows leave HERE, counted
     // (store_x_counted; the reasoning is the A part's, above norm_mha) - younger than every load the pw1 stream waits for
     // before its fourth unit, draining under norm_conv instead of behind the last GLU store, where every CU of the launch
-    // stored its 32 KiB at once (until round 12; block<ATT|C> 19.2 -> 18.9 us, the step 0.885 against 0.881, see the table
-    // at store_x_counted).  The streaming instantiation keeps the closing store.
-    if constexpr (X_EARLY_C) store_x_counted();
-    const __amdgpu_buffer_rsrc_t glu_rs = rows_rsrc(a.glu, 2);
+    // stored its 32 KiB at once (until round 12; block<ATT|C> 19.2 -> 18.9 us, the step 0.885 against 0.881,
+    // profiles/r12a_switch_ab.txt).  The streaming instantiation keeps the closing store.
+    if constexpr (PLAIN) store_x_counted();
     ln_to_act(pb0, 256, 512, 0);
     fstamp(15);
     // pointwise_conv1 + GLU (convolution.py:66-69): unit 2j = value rows 64j.., unit 2j+1 = their gates
@@ -1528,17 +1385,15 @@ __global__ __launch_bounds__(NT, 1) void block_kernel(const EmBlockArgs a_in, lo
                        (bf16)((v[mi][1] + bv.y) * sigmoidf_(gt[mi][1] + bg.y)),
                        (bf16)((v[mi][2] + bv.z) * sigmoidf_(gt[mi][2] + bg.z)),
                        (bf16)((v[mi][3] + bv.w) * sigmoidf_(gt[mi][3] + bg.w))};
-          // (under row_ok every wait of the stream behind the first GLU store waits for these stores too; counted - the
-          // developer build -DEM_BLOCK_VAR=0x40000 - the step measured the same: the product keeps the branch)
-          if constexpr (GLU_COUNTED) put_bf16x4(glu_rs, mi, j, pk);
-          else if (row_ok[mi]) *(bf16x4*)((bf16*)a.glu + mrow[mi] * D + 64 * j + ncol) = pk;
+          // (under row_ok every wait of the stream behind the first GLU store waits for these stores too; stored counted,
+          // like x, the step measured the same, profiles/r12a_switch_ab.txt: the product keeps the branch)
+          if (row_ok[mi]) *(bf16x4*)((bf16*)a.glu + mrow[mi] * D + 64 * j + ncol) = pk;
         }
       }
     });
-    if constexpr (!X_EARLY_C) store_x();
+    if constexpr (!PLAIN) store_x();
     if constexpr (ATT) stamp(51);
     else fstamp(51);
-    touch_done();
     return;
   }
 
@@ -1739,117 +1594,36 @@ __global__ __launch_bounds__(NT, 1) void block_kernel(const EmBlockArgs a_in, lo
       f32x2 acc[16];
 #pragma unroll
       for (int o = 0; o < 16; ++o) acc[o] = bc2;
-      if constexpr (!(EM_BLOCK_VAR & 64)) {  // the requests in three clusters (-DEM_BLOCK_VAR=64: one per row, below - measured no faster)
-        dma_lines(a.params, PAR_OFF, std::integral_constant<int, NG * (PAR_BYTES / 1024)>{});
-        if constexpr (!FOLD) load_x();  // (folded: the own rows' residual is already in registers, updated by linear_out)
-        __builtin_amdgcn_sched_barrier(0);
-  #pragma unroll
-        for (int r = 0; r < 16 + KW - 1; ++r) {
-          // (pinned: the opaque asm ties a zero offset of the request addresses to ALL accumulators of the running
-          // convolution, so the requests can neither be hoisted above this row nor the rows before it sunk below them;
-          // a sched_barrier alone does not do it: instruction selection places arithmetic freely around it)
-          constexpr int PIN1 = KWT == 31 ? 15 : 10, PIN2 = KWT == 31 ? 30 : 20;  // (thirds of the row loop)
-          if (r == PIN1 || r == PIN2) {
-            unsigned o = 0;
-            asm volatile("" : "+s"(o), "+v"(acc[0]), "+v"(acc[1]), "+v"(acc[2]), "+v"(acc[3]), "+v"(acc[4]), "+v"(acc[5]),
-                         "+v"(acc[6]), "+v"(acc[7]), "+v"(acc[8]), "+v"(acc[9]), "+v"(acc[10]), "+v"(acc[11]), "+v"(acc[12]),
-                         "+v"(acc[13]), "+v"(acc[14]), "+v"(acc[15]));
-            const unsigned char* wp = (const unsigned char*)a.pw2 + o;
-            if (r == PIN1) {
-              read_unit(wp, 0, ring[0]);
-              read_unit(wp, 1, ring[1]);
-            } else {
-              read_unit(wp, 2, ring[2]);
-            }
-            __builtin_amdgcn_sched_barrier(0);  // ... nor sink below the rows that follow
-          }
-          const unsigned u = *(const unsigned*)(tile + (hh * 16 + r) * TPITCH + 4 * cp);
-          const f32x2 v = {__builtin_bit_cast(float, u << 16), __builtin_bit_cast(float, u & 0xffff0000u)};
-  #pragma unroll
-          for (int o = 0; o < 16; ++o)
-            if (r - o >= 0 && r - o < KW) acc[o] = __builtin_elementwise_fma(wk2[r - o], v, acc[o]);
-        }
-      } else {
-        // Round 5 experiment (built, verified, NOT faster: profiles/r05c_block_ab.txt - the conv phase drops from 9.3 K to
-        // 8.4 K cycles, but pointwise_conv2's units, now requested as late as row 38, arrive late and its four units take
-        // 5.3 K cycles instead of 1.9 K; the launch as a whole 1.026 - 1.029 against 1.021 - 1.025 ms per step):
-        // ONE request per row of the convolution instead of three clusters.  A cluster of 15 - 16 wave-wide
-        // requests (four waves: 60 KiB) stops the issuing wave for as long as the CU's memory pipeline takes to accept it
-        // - ~1 K cycles at 64 B/clk - and with one wave per SIMD nothing else issues meanwhile: the conv measured 9.3 K
-        // cycles against ~4.8 K of arithmetic + LDS waits (profiles/r05b_block_stamps_fine.txt: stamps 3 -> 5).  A row is
-        // ~72 cycles of packed FMAs; four waves asking for 1 KiB each per row stay under the 64 B/clk the pipeline drains.
-        // The order is: this wave's parameter lines (LDS-DMA), the residual rows, pointwise_conv2's first three units -
-        // the waits below count on the parameter lines being the oldest.  Every request sits between two pins: an opaque
-        // asm that redefines a zero offset in a VGPR (`vz`, part of every request's address) together with ALL
-        // accumulators - a request can neither be hoisted above the pin in front of it (its address depends on it) nor
-        // sunk below the one behind it (which overwrites the register it reads), and the pins are ordered with the rows
-        // through the accumulators.  No sched_barrier: the tile reads and the arithmetic of neighbouring rows interleave
-        // freely.
-        constexpr int NLINES = NG * (PAR_BYTES / 1024), NPW = (NLINES + 3) / 4;  // parameter lines of this wave
-        constexpr int NXL = FOLD ? 0 : 8, NREQ = NPW + NXL + 24, NROW = 16 + KW - 1, RPR = (NREQ + NROW - 1) / NROW;
-        unsigned vz = 0;
-        auto pin = [&]() __attribute__((always_inline)) {
-          asm volatile("" : "+v"(vz), "+v"(acc[0]), "+v"(acc[1]), "+v"(acc[2]), "+v"(acc[3]), "+v"(acc[4]), "+v"(acc[5]),
+      // The requests in three clusters.  One request per row instead shortens the conv phase but pointwise_conv2's units
+      // arrive late: measured no faster (profiles/r05c_block_ab.txt, HISTORY.md section H).
+      dma_lines(a.params, PAR_OFF, std::integral_constant<int, NG * (PAR_BYTES / 1024)>{});
+      if constexpr (!FOLD) load_x();  // (folded: the own rows' residual is already in registers, updated by linear_out)
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int r = 0; r < 16 + KW - 1; ++r) {
+        // (pinned: the opaque asm ties a zero offset of the request addresses to ALL accumulators of the running
+        // convolution, so the requests can neither be hoisted above this row nor the rows before it sunk below them;
+        // a sched_barrier alone does not do it: instruction selection places arithmetic freely around it)
+        constexpr int PIN1 = KWT == 31 ? 15 : 10, PIN2 = KWT == 31 ? 30 : 20;  // (thirds of the row loop)
+        if (r == PIN1 || r == PIN2) {
+          unsigned o = 0;
+          asm volatile("" : "+s"(o), "+v"(acc[0]), "+v"(acc[1]), "+v"(acc[2]), "+v"(acc[3]), "+v"(acc[4]), "+v"(acc[5]),
                        "+v"(acc[6]), "+v"(acc[7]), "+v"(acc[8]), "+v"(acc[9]), "+v"(acc[10]), "+v"(acc[11]), "+v"(acc[12]),
                        "+v"(acc[13]), "+v"(acc[14]), "+v"(acc[15]));
-        };
-        auto request = [&](auto sc) __attribute__((always_inline)) {
-          constexpr int S = decltype(sc)::value;
-          if constexpr (S < NPW) {  // parameter line wave + 4 S (past the end: the last line again)
-            int j = wave + 4 * S;
-            j = j < NLINES ? j : NLINES - 1;
-            const unsigned char* pl = em_uniform_ptr((const unsigned char*)a.params + (size_t)j * 1024);
-            const unsigned dst = __builtin_amdgcn_readfirstlane(PAR_OFF + j * 1024);
-            const unsigned vo = lane * 16 + vz;
-            unsigned keep;
-            asm volatile(
-                "s_mov_b32 %0, m0\n\t"
-                "s_mov_b32 m0, %3\n\t"
-                "s_nop 0\n\t"
-                "global_load_lds_dwordx4 %1, %2\n\t"
-                "s_mov_b32 m0, %0"
-                : "=&s"(keep)
-                : "v"(vo), "s"(pl), "s"(dst)
-                : "memory");
-          } else if constexpr (S < NPW + NXL) {
-            constexpr int i = S - NPW, mi = i >> 2, f = i & 3;
-            xr[mi][f] = *(const float4*)((const unsigned char*)(a.x + mrow[mi] * D + 64 * f + ncol) + vz);
+          const unsigned char* wp = (const unsigned char*)a.pw2 + o;
+          if (r == PIN1) {
+            read_unit(wp, 0, ring[0]);
+            read_unit(wp, 1, ring[1]);
           } else {
-            constexpr int i = S - NPW - NXL, u = i >> 3, q = i & 7;
-            GU8 su = (GU8)a.pw2 + (size_t)u * UNIT + (voff + vz);
-            ring[u].v[q] = *(GFRAG)(su + q * 1024);
+            read_unit(wp, 2, ring[2]);
           }
-        };
-        auto requests_of_row = [&](auto rc) __attribute__((always_inline)) {
-          constexpr int R = decltype(rc)::value;
-          if constexpr (R * RPR < NREQ) {
-            pin();
-            request(std::integral_constant<int, R * RPR>{});
-            if constexpr (RPR > 1 && R * RPR + 1 < NREQ) request(std::integral_constant<int, R * RPR + 1>{});
-          }
-        };
-        // (the tile words are read PF rows ahead, by hand: memory operations do not cross the pins - an asm with side
-        // effects orders them - so left to hipcc every row's LDS read sat right in front of its first use)
-        constexpr int PF = 3;
-        unsigned uw[NROW + PF];
-        auto tile_word = [&](int r) __attribute__((always_inline)) { return *(const unsigned*)(tile + (hh * 16 + r) * TPITCH + 4 * cp); };
+          __builtin_amdgcn_sched_barrier(0);  // ... nor sink below the rows that follow
+        }
+        const unsigned u = *(const unsigned*)(tile + (hh * 16 + r) * TPITCH + 4 * cp);
+        const f32x2 v = {__builtin_bit_cast(float, u << 16), __builtin_bit_cast(float, u & 0xffff0000u)};
 #pragma unroll
-        for (int r = 0; r < PF; ++r) uw[r] = tile_word(r);
-        auto rows = [&](auto self, auto rc) __attribute__((always_inline)) -> void {
-          constexpr int r = decltype(rc)::value;
-          if constexpr (r < NROW) {
-            requests_of_row(rc);
-            if constexpr (r + PF < NROW) uw[r + PF] = tile_word(r + PF);
-            const unsigned u = uw[r];
-            const f32x2 v = {__builtin_bit_cast(float, u << 16), __builtin_bit_cast(float, u & 0xffff0000u)};
-#pragma unroll
-            for (int o = 0; o < 16; ++o)
-              if (r - o >= 0 && r - o < KW) acc[o] = __builtin_elementwise_fma(wk2[r - o], v, acc[o]);
-            self(self, std::integral_constant<int, r + 1>{});
-          }
-        };
-        rows(rows, std::integral_constant<int, 0>{});
-        pin();  // (closes the last interval)
+        for (int o = 0; o < 16; ++o)
+          if (r - o >= 0 && r - o < KW) acc[o] = __builtin_elementwise_fma(wk2[r - o], v, acc[o]);
       }
       if constexpr (!FOLD) touch();  // (its chunk loop must stay OUT of the row loop: with a loop inside, hipcc does not unroll the rows and the accumulators go to scratch; folded: done in the C part)
       const int ch = 2 * cp, kt = ch >> 6, kl = ch & 63;
@@ -1915,7 +1689,6 @@ __global__ __launch_bounds__(NT, 1) void block_kernel(const EmBlockArgs a_in, lo
           }
         }
       if (!CTC) {
-        touch_done();
         return;
       }
       // ---- CTC head (asr/ctc.py:207-215 argmax over ctc_lo): the 32 rows stay in registers as activation
@@ -2013,7 +1786,6 @@ __global__ __launch_bounds__(NT, 1) void block_kernel(const EmBlockArgs a_in, lo
           if (row_ok[mi]) a.ctc_ids[mrow[mi]] = bi;
         }
       }
-      touch_done();
       return;
     }
     if constexpr (!HAS_A && !FINAL) {  // the D part alone (streaming layers: the context hand-over sits between D and A)
@@ -2029,7 +1801,6 @@ __global__ __launch_bounds__(NT, 1) void block_kernel(const EmBlockArgs a_in, lo
             for (int f = 0; f < 4; ++f) *(float4*)(dst + 64 * f + ncol) = xr[mi][f];
           }
       }
-      touch_done();
       return;
     }
   } else if (!HAS_T) {
@@ -2151,7 +1922,6 @@ __global__ __launch_bounds__(NT, 1) void block_kernel(const EmBlockArgs a_in, lo
       }
       if constexpr (!HAS_Q) {
         store_x();
-        touch_done();
         return;
       } else {
         // the hand-over (contextual_block_encoder_layer.py, the end of forward_infer): slot 0 := the previous call's context
@@ -2191,7 +1961,6 @@ __global__ __launch_bounds__(NT, 1) void block_kernel(const EmBlockArgs a_in, lo
       qkv_proj(pq, a.qh, a.kh, a.vt);
     }
     stamp(40);
-    touch_done();
     return;
   }
   if (HAS_A) {
@@ -2212,7 +1981,7 @@ __global__ __launch_bounds__(NT, 1) void block_kernel(const EmBlockArgs a_in, lo
     }
     stamp(15);
     // x += 0.5 * FFN_macaron(norm_ff_macaron(x))  (encoder_layer.py:108-121); the ring goes over to the q / k / v projections
-    ffn(pa0, 512, 1536, 0.5f, ffm_w1, ffm_w2, !X_EARLY_A, ffm_b1g, a.wqkv, [&] { read_unit(a.wqkv, 2, ring[2]); });
+    ffn(pa0, 512, 1536, 0.5f, ffm_w1, ffm_w2, !PLAIN, ffm_b1g, a.wqkv, [&] { read_unit(a.wqkv, 2, ring[2]); });
     if constexpr (RELU) {
       if (ffn_exit) return;
     }
@@ -2224,8 +1993,8 @@ __global__ __launch_bounds__(NT, 1) void block_kernel(const EmBlockArgs a_in, lo
     // final and those three units are already in flight: stores issued now are YOUNGER than every load the stream waits
     // for before its fourth unit - a LayerNorm and three units away.  Round 12 stores x here, through store_x_counted():
     // unconditional, so that the waits behind count the stores instead of waiting for them (under `if (row_ok)` the
-    // first wait of the q / k / v stream stayed vmcnt(13), with the stores counted it is 21), in straight-line code behind
-    // the reduction's switch (a store inside one of its cases is as uncounted as one under row_ok).  The 8 MB of x
+    // first wait of the q / k / v stream stayed vmcnt(13), with the stores counted it is 21), in straight-line code (a
+    // store inside a switch case is as uncounted as one under row_ok).  The 8 MB of x
     // drain under norm_mha, where a CU asks memory for nothing else, instead of in one burst with the last of q / k / v;
     // the re-park, the closing reload and the closing stores go.  Measured (profiles/r12a_*, one stream): block<D|A>
     // 42.0 -> 39.9 us, block<A> 24.6 -> 23.7 us; stamps of workgroup (0, 0): norm_mha (22 -> 15) 2 200 -> 3 750 cycles
@@ -2233,16 +2002,16 @@ __global__ __launch_bounds__(NT, 1) void block_kernel(const EmBlockArgs a_in, lo
     // 10 000 -> 8 800, and every stage in front of it shorter as well (entry -> 22: 72 100 -> 67 800) although its code
     // is the same - presumably the launch in front no longer ends in a burst that this one starts under; that part is
     // an observation, its cause was not isolated.  Behind norm_mha's
-    // normalisation, or half either side of the LayerNorm, the step was slower (table at store_x_counted).
+    // normalisation, or half either side of the LayerNorm, the step was slower (HISTORY.md section H).
     // The streaming and the folded instantiations keep the round-3 form: a few workgroups, no chip-wide burst.  The
     // q / k / v stores themselves stay inside the stream: batched behind it they cost MORE, a store-issue tail of 3 300
     // cycles that the stream otherwise hides (profiles/r03c_*).
     stamp(22);
-    if constexpr (X_EARLY_A) store_x_counted();
+    if constexpr (PLAIN) store_x_counted();
     ln_to_act(pa1, 0, 256, 0);                     // norm_mha (encoder_layer.py:123-127)
     stamp(15);
     qkv_proj(pa1, a.qh, a.kh, a.vt);
-    if constexpr (!X_EARLY_A) {
+    if constexpr (!PLAIN) {  // (x as ffn() re-parked it)
       const float4* const xp = (const float4*)(smem + TILE_OFF) + tid;
 #pragma unroll
       for (int mi = 0; mi < 2; ++mi)
@@ -2252,7 +2021,6 @@ __global__ __launch_bounds__(NT, 1) void block_kernel(const EmBlockArgs a_in, lo
     }
     stamp(40);
   }
-  touch_done();
 }
 
 template <int MODE, int KWT = 31, bool RELU = false>

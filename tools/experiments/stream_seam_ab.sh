@@ -1,3 +1,4 @@
+# RECORD, no longer runnable on this source: v4096 / v8192 / v12288 were -DEM_BLOCK_VAR builds; check out commit ad2a81c to repeat it (HISTORY.md section H).
 # split-FFN meeting point: plain stores / loads + release / acquire fences (product); lib_v8192: agent-scope (sc1) stores, no release fence;
 # lib_v4096: agent-scope loads, no acquire fence; lib_v12288: both (bash tools/build_block_variants.sh v4096 v8192 v12288)
 for rep in 1 2; do for v in product v4096 v8192 v12288; do
