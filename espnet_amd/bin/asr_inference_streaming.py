@@ -15,6 +15,11 @@ Decoding (`search=`):
     partial transcript after every chunk.
   * "offline": greedy partials, and the offline joint CTC/attention beam search over the accumulated
     encoder output at `is_final`.
+  * "tsync" (ctc_weight = 1.0): the RESUMABLE time-synchronous CTC prefix beam search (`em_ctc_tsync_extend`,
+    BeamSearchTimeSync.extend): beam search, n-gram fusion (`ngram_file`) and the length bonus for one stream, for
+    `batch_call` and for `StreamPool` alike; the n-best list so far after every chunk - what the one-shot search would
+    return if the utterance ended there.  Per tick one top-K launch, one walk launch and one D2H copy per group of streams;
+    the search's whole memory is a slot of a state slab per stream (at most `tsync_max_frames` encoder frames).
 """
 import contextlib
 import logging
@@ -53,11 +58,28 @@ class Speech2TextStreaming:
                  beam_size: int = 20, ctc_weight: float = 0.5, lm_weight: float = 1.0,
                  penalty: float = 0.0, nbest: int = 1, disable_repetition_detection: bool = False,
                  decoder_text_length_limit: int = 0, encoded_feat_length_limit: int = 0,
-                 normalize_length: bool = False, use_hipgraph: bool = True, search: Optional[str] = None):
+                 normalize_length: bool = False, use_hipgraph: bool = True, search: Optional[str] = None,
+                 ngram_file: Union[Path, str, None] = None, ngram_scorer: str = "full", ngram_weight: float = 0.9,
+                 tsync_max_frames: int = 1536):
         if search is None:
             search = "online" if beam_size > 1 else "greedy"
-        if search not in ("online", "greedy", "offline"):
+        if search not in ("online", "greedy", "offline", "tsync"):
             raise ValueError(f"search={search!r}")
+        if search == "tsync":  # (worded as Speech2Text(time_sync=True) words them)
+            if float(ctc_weight) != 1.0:
+                raise NotImplementedError(f"search='tsync' with ctc_weight={ctc_weight}: the attention decoder is not scored "
+                                          "time-synchronously on the MI355X path; pass ctc_weight=1.0")
+            if lm_train_config is not None:
+                raise NotImplementedError("search='tsync' with lm_train_config: a neural LM is not scored time-synchronously "
+                                          "on the MI355X path; an n-gram (ngram_file) is")
+            if ngram_scorer not in ("full", "part"):
+                raise ValueError(f"ngram_scorer={ngram_scorer!r}")
+            if int(tsync_max_frames) < 1:
+                raise ValueError("tsync_max_frames must be at least 1")
+        elif ngram_file is not None:
+            raise NotImplementedError(f"ngram_file with search={search!r}: the n-gram is scored by the time-synchronous "
+                                      "stream search only (search='tsync'); the block-synchronous and greedy decoders "
+                                      "do not take it")
         if decoder_text_length_limit or encoded_feat_length_limit:
             raise NotImplementedError("decoder_text_length_limit / encoded_feat_length_limit")
         if not str(device).startswith("cuda"):
@@ -75,7 +97,13 @@ class Speech2TextStreaming:
         self.device, self.dtype = device, dtype
         self.maxlenratio, self.minlenratio, self.nbest = maxlenratio, minlenratio, nbest
         self.beam_size, self.search = beam_size, search
-        self.beam_search = None
+        self.beam_search = self.beam_search_timesync = self.ngram = None
+        self.tsync_max_frames = int(tsync_max_frames)
+        # test hook: when set, every tick's candidate tables are kept per stream in `tsync_tables` (key: "call", (group,
+        # row) or the pool's stream id -> a list of (cand_id (n, K), cand_lp (n, K), blank_lp (n,)) clones)
+        self.keep_tsync_tables = False
+        self.tsync_tables = {}
+        self._tsync_state = None
         lm = None
         if lm_train_config is not None:  # :97-102
             from espnet_amd.tasks.lm import LMTask
@@ -108,8 +136,26 @@ class Speech2TextStreaming:
                 vocab_size=len(token_list), token_list=token_list,
                 pre_beam_score_key=None if ctc_weight == 1.0 else "full", normalize_length=normalize_length,
                 disable_repetition_detection=disable_repetition_detection)
+        elif search == "tsync":
+            from espnet_amd.nets.beam_search_timesync import BeamSearchTimeSync
+            from espnet_amd.nets.scorers.ctc import CTCPrefixScorer
+
+            if asr_model.ctc is None:
+                raise NotImplementedError("search='tsync' needs a model with a CTC head (ctc_weight > 0 in training)")
+            token_list = asr_model.token_list
+            if ngram_file is not None:
+                from espnet_amd.nets.scorers.ngram import NgramFullScorer, NgramPartScorer
+
+                self.ngram = (NgramFullScorer if ngram_scorer == "full" else NgramPartScorer)(ngram_file, token_list)
+            scorers = dict(ctc=CTCPrefixScorer(ctc=asr_model.ctc, eos=asr_model.eos))
+            if self.ngram is not None:
+                scorers["ngram"] = self.ngram
+            self.beam_search_timesync = BeamSearchTimeSync(
+                sos=asr_model.sos, beam_size=beam_size, scorers=scorers, token_list=token_list, blank=asr_model.blank_id,
+                weights=dict(ctc=ctc_weight, ngram=ngram_weight if self.ngram is not None else 0.0, length_bonus=penalty))
         m = asr_model
-        pack_modules(device, [m.frontend, m.encoder, m.ctc] + ([] if search == "greedy" else [m.decoder, lm]))
+        pack_modules(device, [m.frontend, m.encoder, m.ctc] +
+                     ([] if search == "greedy" else [self.ngram] if search == "tsync" else [m.decoder, lm]))
         token_type = token_type if token_type is not None else getattr(args, "token_type", None)
         bpemodel = bpemodel if bpemodel is not None else getattr(args, "bpemodel", None)
         self.tokenizer = (None if token_type is None or (token_type == "bpe" and bpemodel is None)
@@ -133,6 +179,7 @@ class Speech2TextStreaming:
         self._enc_chunks = []
         self._last_id = -1
         self._partial_ids: List[int] = []
+        self._tsync_started, self._tsync_last = False, None  # (the single stream's slot is reset by its next frames)
         if self._runner is not None:
             self._runner.reset()
         if self.search == "online" and self.beam_search is not None:
@@ -220,16 +267,55 @@ class Speech2TextStreaming:
                 nbest_hyps = self.beam_search(x=enc, maxlenratio=self.maxlenratio, minlenratio=self.minlenratio,
                                               is_final=is_final)
                 ret = self.assemble_hyps(nbest_hyps)
+            elif self.search == "tsync":
+                ret = self.assemble_hyps(self._tsync_single(enc))
             else:
                 if enc.size(0) > 0:
                     self._enc_chunks.append(enc.clone())
                     self._extend_partial(enc)
                 ret = self._results(is_final)
+        elif self.search == "tsync":  # (the call only buffered samples: the list so far)
+            ret = self.assemble_hyps(self._tsync_single(None))
         if is_final:
             self.reset()
         return ret
 
-    # ------------------------------------------------------------------ a batch of lock-step streams (greedy CTC)
+    # ------------------------------------------------------------------ the resumable time-synchronous search
+    def _tsync_extend(self, enc, n_new, slots, reset, state, keys):
+        """One top-K launch and one walk launch for the rows of one group: enc (S, T, d) or None (no new frames: emission
+        only).  Returns the TsyncTick; only enqueues."""
+        bs, m = self.beam_search_timesync, self.asr_model
+        S = len(slots)
+        if enc is None or enc.size(1) == 0:
+            K = state.shape["K"]
+            dev = state.slab.device
+            tabs = (torch.zeros(S, 1, K, dtype=torch.int32, device=dev), torch.zeros(S, 1, K, device=dev),
+                    torch.zeros(S, 1, device=dev))
+            n_new = [0] * S
+        else:
+            tabs = m.ctc.frame_topk_device(enc, state.shape["K"], bs.blank)
+        if self.keep_tsync_tables:
+            for i, key in enumerate(keys):
+                n = int(n_new[i])
+                self.tsync_tables.setdefault(key, []).append(tuple(t[i, :n].clone() for t in tabs))
+        return bs.extend_candidates(*tabs, n_new, slots, reset, state, nbest=max(1, min(self.nbest, bs.beam_size)))
+
+    def _tsync_single(self, enc):
+        """`__call__`'s step: the new encoder frames enc (T, d) (None or T = 0: none) -> the n-best list so far."""
+        bs = self.beam_search_timesync
+        n = 0 if enc is None else int(enc.size(0))
+        if n == 0 and self._tsync_last is not None:
+            return self._tsync_last
+        if self._tsync_state is None:
+            self._tsync_state = bs.stream_state(1, self.tsync_max_frames, next(self.asr_model.parameters()).device)
+            self._tsync_state.acquire()
+        tick = self._tsync_extend(None if n == 0 else enc.unsqueeze(0), [n], [0], [not self._tsync_started],
+                                  self._tsync_state, ["call"])
+        self._tsync_started = True
+        self._tsync_last = bs.collect(tick)[0]
+        return self._tsync_last
+
+    # ------------------------------------------------------------------ a batch of lock-step streams (greedy CTC / tsync)
     def apply_frontend_batch(self, speech: torch.Tensor, prev_states=None, is_final: bool = False):
         """`apply_frontend` (:205-293) for S streams that are fed equal chunks at the same times: speech (S, n) host or
         device tensor.  Returns (feats (S, t, n_mels) on the device or None, state)."""
@@ -253,7 +339,9 @@ class Speech2TextStreaming:
         speech (S, n) f32.  Returns, per stream, the token ids decoded so far (incremental G1: per-frame arg-max, repeats
         collapsed across chunk seams, blank / <sos/eos> dropped).  Stream s sees exactly what `__call__` gives it alone
         (tests/test_gpu_streaming.py::test_batch_call_equals_single_streams); one launch sequence serves all S streams
-        (ContextualBlockConformerEncoder.forward_infer_batch).  The object holds the batch's state until is_final."""
+        (ContextualBlockConformerEncoder.forward_infer_batch).  The object holds the batch's state until is_final.
+        With search="tsync": the token ids of the best hypothesis so far of the time-synchronous beam search (REPLACED each
+        tick, not appended; `batch_call_async(...)`'s `PendingTick.nbest` keeps the n-best lists with their scores)."""
         return self.batch_call_async(speech, is_final).result()
 
     @torch.no_grad()
@@ -275,12 +363,14 @@ class Speech2TextStreaming:
             bst = self._batches[group] = dict(frontend=None, encoder=None, last=[-1] * S, ids=[[] for _ in range(S)], pending=None,
                                               graph=self._tick_graphs.get((group, tuple(speech.shape))))
         m = self.asr_model
-        ids_host, event = None, None
+        ids_host, event, collect = None, None, None
+        tsync = self.search == "tsync"
         ctx = torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext()
         with ctx:
             ids = None
             tg = bst.get("graph")
-            sig = BatchTickGraph.signature(speech, bst) if (self.use_hipgraph and not is_final) else None
+            # (the time-synchronous ticks run as eager launches: their capture is a later step)
+            sig = BatchTickGraph.signature(speech, bst) if (self.use_hipgraph and not is_final and not tsync) else None
             if tg is not None and tg.graph is not None and sig is not None and sig == tg.sig:
                 ids = tg.replay(speech, bst)  # steady state: one graph launch
             else:
@@ -290,7 +380,17 @@ class Speech2TextStreaming:
                 feats, bst["frontend"] = self.apply_frontend_batch(speech_dev, bst["frontend"], is_final=is_final)
                 if feats is not None:
                     enc, y_len, bst["encoder"] = m.encoder.forward_infer_batch(feats, bst["encoder"], is_final)  # (a view: the encoder's own cat / contiguous() copies it once)
-                    if y_len > 0:
+                    if y_len > 0 and tsync:  # one state slab per group, slot = row
+                        bs = self.beam_search_timesync
+                        if bst.get("tsync") is None:
+                            bst["tsync"] = bs.stream_state(S, self.tsync_max_frames, enc.device)
+                            for _ in range(S):
+                                bst["tsync"].acquire()
+                        tick = self._tsync_extend(enc, [y_len] * S, list(range(S)), [not bst.get("tsync_started")] * S,
+                                                  bst["tsync"], [(group, s_) for s_ in range(S)])
+                        bst["tsync_started"] = True
+                        collect = bs.collect_start(tick)  # ONE device -> host read per tick for all streams
+                    elif y_len > 0:
                         ids = m.ctc.argmax(enc, as_int32=True)
                 # a second tick of the same shape in a row: the ticks from here on are this one again - capture it
                 if sig is not None and (tg is None or tg.graph is None) and BatchTickGraph.signature(speech, bst) == sig:
@@ -303,7 +403,7 @@ class Speech2TextStreaming:
                 ids_host.copy_(ids, non_blocking=True)  # ONE device -> host read per tick for all streams
                 event = torch.cuda.Event()
                 event.record()
-        tick = PendingTick(self, bst, ids_host, event, bst["pending"])
+        tick = PendingTick(self, bst, ids_host, event, bst["pending"], collect)
         bst["pending"] = tick
         if is_final:
             tg = bst.get("graph")
@@ -441,11 +541,15 @@ class PendingTick:
     """A tick of `Speech2TextStreaming.batch_call_async` whose launches are queued: `result()` waits for its token ids and
     returns, per stream, the ids decoded so far."""
 
-    def __init__(self, s2t, bst, ids_host, event, prev):
+    def __init__(self, s2t, bst, ids_host, event, prev, collect=None):
         self._s2t, self._bst, self._ids_host, self._event, self._prev = s2t, bst, ids_host, event, prev
+        self._collect = collect  # search="tsync": the queued copy of the tick's n-best lists
         self._res = None
+        self.nbest = None  # search="tsync", after result(): per stream the n-best list so far (Hypothesis: score, scores)
 
     def done(self) -> bool:
+        if self._collect is not None:
+            return self._res is not None or self._collect.done()
         return self._res is not None or self._event is None or self._event.query()
 
     def result(self) -> List[List[int]]:
@@ -460,6 +564,11 @@ class PendingTick:
                 for s_, row in enumerate(self._ids_host.tolist()):
                     bst["last"][s_] = _collapse_greedy(row, bst["last"][s_], bst["ids"][s_], drop)
                 self._ids_host = None
+            if self._collect is not None:  # the lists so far REPLACE the last tick's
+                bst["nbest"] = self._collect.result()
+                bst["ids"] = [[t for t in hyps[0].yseq[1:-1].tolist() if t != 0] if hyps else [] for hyps in bst["nbest"]]
+                self._collect = None
+            self.nbest = bst.get("nbest")
             self._res = [list(v) for v in bst["ids"]]
             if bst["pending"] is self:
                 bst["pending"] = None
@@ -477,7 +586,9 @@ class StreamPool:
     batched frontend / encoder launch sequence once (`apply_frontend_batch`, `forward_infer_batch` with one block count
     per row).  Streams fed equal chunks walk through the same short cycle of shapes whenever they joined, so a pool of
     live connections falls into a handful of groups.  Greedy CTC (incremental G1), as `batch_call`.  A stream's results
-    equal what `Speech2TextStreaming.__call__` gives it alone (tests/test_gpu_streaming.py::test_stream_pool_ragged)."""
+    equal what `Speech2TextStreaming.__call__` gives it alone (tests/test_gpu_streaming.py::test_stream_pool_ragged).
+    With search="tsync" every group of a tick is one `BeamSearchTimeSync.extend` on its rows' slots of one pool-wide state
+    slab, and `tick` returns the best hypothesis' ids so far (tests/test_gpu_ctc_tsync_stream.py)."""
 
     def __init__(self, s2t: "Speech2TextStreaming"):
         if s2t.search == "online":
@@ -485,6 +596,10 @@ class StreamPool:
         self.s2t = s2t
         self.streams = {}   # id -> dict(frontend, encoder, last, ids)
         self.groups_last_tick = 0
+        # search="tsync": ONE slab for the pool, grown by doubling; a stream holds a slot from the tick it joins to its final
+        # tick.  `nbest_last_tick`: {stream id: the n-best list so far} of the last tick's active streams.
+        self.tsync_state = None
+        self.nbest_last_tick = {}
 
     @staticmethod
     def _shape(t):
@@ -535,14 +650,21 @@ class StreamPool:
         """chunks: {stream id: (samples (n,) float tensor / array, is_final)}.  Unknown ids join the pool; a stream whose
         chunk is final leaves it after this tick.  Returns {stream id: token ids decoded so far} for the active streams."""
         s2t, m = self.s2t, self.s2t.asr_model
+        tsync = s2t.search == "tsync"
+        dev = next(m.parameters()).device
+        if tsync and self.tsync_state is None:
+            self.tsync_state = s2t.beam_search_timesync.stream_state(4, s2t.tsync_max_frames, dev)
         groups = {}
         for sid, (speech, is_final) in chunks.items():
             if isinstance(speech, np.ndarray):
                 speech = torch.from_numpy(speech)
-            st = self.streams.setdefault(sid, dict(frontend=None, encoder=None, last=-1, ids=[]))
+            st = self.streams.get(sid)
+            if st is None:
+                st = self.streams[sid] = dict(frontend=None, encoder=None, last=-1, ids=[])
+                if tsync:  # the stream joins: a slot of its own, reset by its first frames
+                    st.update(slot=self.tsync_state.acquire(), started=False, nbest=None)
             groups.setdefault(self._signature(st, speech.numel(), is_final), []).append((sid, speech))
         self.groups_last_tick = len(groups)
-        dev = next(m.parameters()).device
         drop = (m.blank_id, m.sos, m.eos)
         for sig, members in groups.items():
             is_final = sig[1]
@@ -556,7 +678,14 @@ class StreamPool:
                 if en is not None and isinstance(en["n_processed_blocks"], list) and len(set(en["n_processed_blocks"])) == 1:
                     en["n_processed_blocks"] = en["n_processed_blocks"][0]
                 enc, y_len, en_next = m.encoder.forward_infer_batch(feats.contiguous(), en, is_final)
-                if y_len > 0:
+                if y_len > 0 and tsync:  # one `extend` on the rows' slots; one device -> host read per group and tick
+                    bs = s2t.beam_search_timesync
+                    tk = s2t._tsync_extend(enc, [y_len] * len(sts), [st["slot"] for st in sts],
+                                           [not st["started"] for st in sts], self.tsync_state, [sid for sid, _ in members])
+                    for st, hyps in zip(sts, bs.collect(tk)):
+                        st["started"], st["nbest"] = True, hyps
+                        st["ids"] = [t for t in hyps[0].yseq[1:-1].tolist() if t != 0] if hyps else []
+                elif y_len > 0:
                     ids = m.ctc.argmax(enc, as_int32=True).cpu().tolist()  # one device -> host read per group and tick
             else:
                 en_next = None if sts[0]["encoder"] is None else self._stack([st["encoder"] for st in sts])
@@ -567,8 +696,12 @@ class StreamPool:
                 if ids is not None:
                     st["last"] = _collapse_greedy(ids[i], st["last"], st["ids"], drop)
         res = {sid: list(self.streams[sid]["ids"]) for sid in chunks}
+        if tsync:
+            self.nbest_last_tick = {sid: self.streams[sid]["nbest"] for sid in chunks}
         for sid, (_, is_final) in chunks.items():
             if is_final:
+                if tsync:  # the stream leaves: its slot is free for the next one
+                    self.tsync_state.release(self.streams[sid]["slot"])
                 del self.streams[sid]
         return res
 

@@ -5,8 +5,10 @@
 //                       the row's blank log-prob.  Every lane keeps the best not-yet-taken element of its own columns; a
 //                       round is one wave arg-max and a rescan of the winning lane's V / 64 columns: V + K V / 64 loads per
 //                       row, no sort, no LDS.
-//   tsync_search_kernel one workgroup per utterance walks all its frames; nothing is read back and no workgroup waits for
-//                       another.
+//   tsync_kernel        one workgroup per utterance walks all its frames; nothing is read back and no workgroup waits for
+//                       another.  ONE body, two instantiations: <false> is em_ctc_tsync_search (the whole utterance from the
+//                       empty prefix, everything between two frames in LDS and scratch), <true> is em_ctc_tsync_extend (the
+//                       frames of one call, between two calls everything in the row's PERSISTENT slot, see "The slot").
 //
 // The walk.  The beam holds at most W prefixes; a frame proposes the fixed grid of W (K + 1) SLOTS: slot (i, j < K) is beam
 // entry i extended by candidate j, slot (i, K) is entry i itself (its blank and repeat mass).  Two extension slots never
@@ -22,8 +24,21 @@
 //   l2 in hyps: a scan of the W beam entries;
 //   l2 in dp:   an open-addressed table in LDS (linear probing, at most half full, rebuilt every frame from the members of
 //               the frame that did not stay in the beam) over the slot records (hash, parent, token, length, p_nb, p_b).
-// Every loop is bounded at launch: frames (xlens), slots, K, W, probes (<= table size), chain steps (<= T + 1), binary
-// search halvings (32).
+// Every loop is bounded at launch: frames (xlens / n_new), slots, K, W, probes (<= table size), chain steps (<= T + 1, for
+// the resumable form max_frames + 1), binary search halvings (32).
+//
+// The slot (em_ctc_tsync_extend).  What the one-shot walk carries from one frame to the next is the beam (LDS), the slot
+// records of the last frame's members that left the beam (scratch; the LDS table only indexes them) and the node arena
+// (scratch).  A slot of the state slab holds exactly that, at offsets that depend on (K, W, max_frames) alone:
+//   header  16 words: magic, frames consumed, beam count, parity of the (p_nb, p_b) halves, K, W, max_frames as first used
+//   the one-shot scratch layout for T = max_frames: dp_hash, the arena (node ids 1 + t W + r with the ABSOLUTE frame t),
+//           v_nb / v_b [2][S], v_ng, dp_par / dp_tok / dp_ntok
+//   the beam entries: hash, node, par, tok, ntok, nb, b, prev, ng, ctx[]
+//   a flag byte per grid slot: a member of the last frame that left the beam (the table is rebuilt from these on entry;
+//           which entry of the table a record lands in depends on the insertion order, what a probe FINDS does not: the
+//           members of a frame are distinct sequences and a hit compares the whole sequence)
+// Nothing in a slot is an address or a slot index, so a slot may be copied anywhere.  A row with reset != 0 reads nothing
+// of its slot; emission (the <eos> term, the final order) works on LDS copies and never changes the slot.
 #include "em_common.h"
 #include "ngram_trie.h"
 
@@ -95,16 +110,30 @@ struct TsArgs {
   const float *cand_lp, *blank_lp;
   const int32_t* xlens;
   int T, K, W, nbest, sos, blank, cap, has_ng;
+  int Tn;  // frames the node arena and a tokens row hold: T (one shot) or max_frames (resumable)
   float w_ctc, w_ng, pen;
   int32_t *tokens, *lens, *count;
   float *score, *score_ctc, *score_ng, *score_len;
-  char* ws;
+  char* ws;  // one shot: scratch, ws_per per utterance; resumable: the state slab, ws_per = slot_bytes
   size_t ws_per;
+  // the resumable form only
+  const int32_t *n_new, *slot, *reset;
+  int32_t *frames, *status;
+  int n_slots;
 };
+
+constexpr int TS_MAGIC = 0x54535931, TS_HDR_WORDS = 16;
+enum { TS_H_MAGIC = 0, TS_H_FRAMES, TS_H_COUNT, TS_H_PARITY, TS_H_K, TS_H_W, TS_H_TMAX };
 
 __host__ __device__ inline size_t ts_ws_per(long T, long K, long W) {
   const long S = W * (K + 1), NN = T * W + 1;
   return (size_t)(40 * S + 8 * NN);
+}
+
+__host__ __device__ inline size_t ts_beam_bytes(long W) { return (size_t)((W * (8 + 4 * 8 + 4 * TS_LD) + 7) & ~7L); }
+// a slot: header | the one-shot layout for T = max_frames | beam entries | a flag byte per grid slot
+__host__ __device__ inline size_t ts_state_per(long Tn, long K, long W) {
+  return (size_t)((4 * TS_HDR_WORDS + ts_ws_per(Tn, K, W) + ts_beam_bytes(W) + W * (K + 1) + 15) & ~15L);
 }
 
 __device__ __forceinline__ float lae(float a, float b) {  // logaddexp, shifted by the larger term; -inf, -inf -> -inf
@@ -137,7 +166,8 @@ __device__ __forceinline__ float ts_total(float w_ctc, float lse, float w_ng, fl
   return w_ctc * lse + w_ng * ng + pen * (float)ntok;
 }
 
-__global__ __launch_bounds__(TS_THREADS) void tsync_search_kernel(EmNgramModel m, TsArgs a) {
+template <bool RS>
+__global__ __launch_bounds__(TS_THREADS) void tsync_kernel(EmNgramModel m, TsArgs a) {
   __shared__ int32_t s_tab[TS_CAP_MAX];
   __shared__ float s_score[TS_S_MAX];
   __shared__ unsigned char s_keep[TS_S_MAX];
@@ -153,13 +183,47 @@ __global__ __launch_bounds__(TS_THREADS) void tsync_search_kernel(EmNgramModel m
   __shared__ int s_count;
 
   const int b = blockIdx.x, tid = threadIdx.x, nthr = blockDim.x;
-  const int T = a.T, K = a.K, W = a.W, K1 = a.K + 1, S = a.W * K1, cap = a.cap, blank = a.blank;
+  const int T = a.T, Tn = a.Tn, K = a.K, W = a.W, K1 = a.K + 1, S = a.W * K1, cap = a.cap, blank = a.blank;
   const int nord = a.has_ng ? m.order - 1 : 0;  // context nodes carried per entry
-  int Tb = a.xlens[b];
+  // t0 frames are behind this row, Tb are walked now; st: the row's status; fresh: the walk starts from the empty prefix
+  int Tb, t0 = 0, cnt0 = 0, st = 0;
+  bool fresh = true;
+  char* ws;
+  int32_t* hdr = nullptr;
+  if (RS) {
+    const int sl = a.slot[b];
+    Tb = a.n_new[b];
+    fresh = a.reset[b] != 0;
+    if (sl < 0 || sl >= a.n_slots) {
+      st = 3;
+      ws = a.ws;  // (never dereferenced)
+    } else {
+      hdr = (int32_t*)(a.ws + (size_t)sl * a.ws_per);
+      ws = (char*)(hdr + TS_HDR_WORDS);
+      if (!fresh) {  // (every thread reads the same words; the header is rewritten behind the last barrier only)
+        if (hdr[TS_H_MAGIC] != TS_MAGIC || hdr[TS_H_K] != K || hdr[TS_H_W] != W || hdr[TS_H_TMAX] != Tn) st = 2;
+        else {
+          t0 = hdr[TS_H_FRAMES];
+          cnt0 = hdr[TS_H_COUNT];
+          t0 = t0 < 0 ? 0 : (t0 > Tn ? Tn : t0);
+          cnt0 = cnt0 < 0 ? 0 : (cnt0 > W ? W : cnt0);
+        }
+      }
+    }
+  } else {
+    Tb = a.xlens[b];
+    ws = a.ws + (size_t)b * a.ws_per;
+  }
   Tb = Tb < 0 ? 0 : (Tb > T ? T : Tb);
+  if (RS) {
+    if (st >= 2) Tb = 0;
+    else if (t0 + Tb > Tn) {  // all or nothing
+      st = 1;
+      Tb = 0;
+    }
+  }
 
-  char* ws = a.ws + (size_t)b * a.ws_per;
-  const long NN = (long)T * W + 1;
+  const long NN = (long)Tn * W + 1;
   u64* dp_hash = (u64*)ws;
   int32_t* node_par = (int32_t*)(dp_hash + S);
   int32_t* node_tok = node_par + NN;
@@ -169,8 +233,31 @@ __global__ __launch_bounds__(TS_THREADS) void tsync_search_kernel(EmNgramModel m
   int32_t* dp_par = (int32_t*)(v_ng + S);
   int32_t* dp_tok = dp_par + S;
   int32_t* dp_ntok = dp_tok + S;
+  // (the resumable form's beam entries and flags, behind the one-shot layout)
+  u64* g_hash = (u64*)(dp_ntok + S);
+  int32_t* g_i = (int32_t*)(g_hash + W);  // node, par, tok, ntok [W] each
+  float* g_f = (float*)(g_i + 4 * W);     // nb, b, prev, ng [W] each
+  int32_t* g_ctx = (int32_t*)(g_f + 4 * W);
+  unsigned char* g_left = (unsigned char*)g_hash + ts_beam_bytes(W);
 
-  if (tid == 0) {
+  if (RS && st >= 2) {
+    if (tid == 0) s_count = 0;
+  } else if (RS && !fresh) {
+    if (tid < cnt0) {
+      const int i = tid;
+      h_hash[0][i] = g_hash[i];
+      h_node[0][i] = g_i[i];
+      h_par[0][i] = g_i[W + i];
+      h_tok[0][i] = g_i[2 * W + i];
+      h_ntok[0][i] = g_i[3 * W + i];
+      h_nb[0][i] = g_f[i];
+      h_b[0][i] = g_f[W + i];
+      h_prev[0][i] = g_f[2 * W + i];
+      h_ng[0][i] = g_f[3 * W + i];
+      for (int k = 0; k < TS_LD; ++k) h_ctx[0][i][k] = g_ctx[i * TS_LD + k];
+    }
+    if (tid == 0) s_count = cnt0;
+  } else if (tid == 0) {
     h_node[0][0] = 0;
     h_par[0][0] = -1;
     h_tok[0][0] = a.sos;
@@ -187,11 +274,24 @@ __global__ __launch_bounds__(TS_THREADS) void tsync_search_kernel(EmNgramModel m
   }
   for (int e = tid; e < cap; e += nthr) s_tab[e] = -1;
   __syncthreads();
+  if (RS && !fresh && st < 2 && t0 > 0) {  // the table of the frame before this call, from the slot's records
+    for (int s = tid; s < S; s += nthr) {
+      if (!g_left[s]) continue;
+      int pos = (int)(dp_hash[s] & (u64)(cap - 1));
+      for (int pr = 0; pr < cap; ++pr) {
+        if (atomicCAS(&s_tab[pos], -1, s) == -1) break;
+        pos = (pos + 1) & (cap - 1);
+      }
+    }
+    __syncthreads();
+  }
 
-  int cur = 0, vb = 0;  // the beam buffer and the (p_nb, p_b) buffer this frame WRITES is vb, the last frame's vb ^ 1
-  for (int t = 0; t < Tb; ++t) {
+  // the beam buffer; the (p_nb, p_b) half this frame WRITES is vb, the last frame's vb ^ 1 (vb = the frame's parity)
+  int cur = 0, vb = RS && !fresh && st < 2 ? (hdr[TS_H_PARITY] & 1) : 0;
+  for (int tl = 0; tl < Tb; ++tl) {
+    const int t = t0 + tl;  // the absolute frame: node ids
     const int count = s_count;
-    const size_t fr = (size_t)b * T + t;
+    const size_t fr = (size_t)b * T + tl;
     if (tid < K) {
       s_cand[tid] = a.cand_id[fr * K + tid];
       s_clp[tid] = a.cand_lp[fr * K + tid];
@@ -223,7 +323,7 @@ __global__ __launch_bounds__(TS_THREADS) void tsync_search_kernel(EmNgramModel m
         int hit = -1;
         for (int i2 = 0; i2 < count; ++i2)
           if (h_ntok[cur][i2] == nt && h_tok[cur][i2] == c && h_hash[cur][i2] == h2 &&
-              chain_equal(node_par, node_tok, h_par[cur][i2], node_i, T)) {
+              chain_equal(node_par, node_tok, h_par[cur][i2], node_i, Tn)) {
             hit = i2;
             break;
           }
@@ -236,7 +336,7 @@ __global__ __launch_bounds__(TS_THREADS) void tsync_search_kernel(EmNgramModel m
             const int idx = s_tab[pos];
             if (idx < 0) break;
             if (dp_hash[idx] == h2 && dp_ntok[idx] == nt && dp_tok[idx] == c &&
-                chain_equal(node_par, node_tok, dp_par[idx], node_i, T)) {
+                chain_equal(node_par, node_tok, dp_par[idx], node_i, Tn)) {
               const float pnb = nb_r[idx], pb = b_r[idx];
               bb = lpb + lae(pnb, pb);
               nb = lae(nb, lpc + pnb);
@@ -341,7 +441,9 @@ __global__ __launch_bounds__(TS_THREADS) void tsync_search_kernel(EmNgramModel m
 
     // E. dp of the next frame: the members that did not stay in the beam, found by their hash
     for (int s = tid; s < S; s += nthr) {
-      if (!(s_score[s] > -INFINITY) || s_keep[s]) continue;
+      const bool left = s_score[s] > -INFINITY && !s_keep[s];
+      if (RS && tl == Tb - 1) g_left[s] = left ? 1 : 0;
+      if (!left) continue;
       const int i = s / K1, j = s - i * K1;
       u64 h;
       if (j == K) {
@@ -367,10 +469,41 @@ __global__ __launch_bounds__(TS_THREADS) void tsync_search_kernel(EmNgramModel m
     vb ^= 1;
   }
 
+  if (RS && st < 2 && (fresh || Tb > 0)) {  // the slot takes the beam; the records and the arena are in it already
+    const int n = s_count;
+    if (tid < n) {
+      const int i = tid;
+      g_hash[i] = h_hash[cur][i];
+      g_i[i] = h_node[cur][i];
+      g_i[W + i] = h_par[cur][i];
+      g_i[2 * W + i] = h_tok[cur][i];
+      g_i[3 * W + i] = h_ntok[cur][i];
+      g_f[i] = h_nb[cur][i];
+      g_f[W + i] = h_b[cur][i];
+      g_f[2 * W + i] = h_prev[cur][i];
+      g_f[3 * W + i] = h_ng[cur][i];
+      for (int k = 0; k < TS_LD; ++k) g_ctx[i * TS_LD + k] = h_ctx[cur][i][k];
+    }
+    if (tid == 0) {
+      hdr[TS_H_MAGIC] = TS_MAGIC;
+      hdr[TS_H_FRAMES] = t0 + Tb;
+      hdr[TS_H_COUNT] = n;
+      hdr[TS_H_PARITY] = vb;
+      hdr[TS_H_K] = K;
+      hdr[TS_H_W] = W;
+      hdr[TS_H_TMAX] = Tn;
+      for (int k = TS_H_TMAX + 1; k < TS_HDR_WORDS; ++k) hdr[k] = 0;
+    }
+  }
+  if (RS && tid == 0) {
+    a.frames[b] = t0 + Tb;
+    a.status[b] = st;
+  }
+
   // the end: the <eos> term of the n-gram, the final order, the n-best rows
   const int count = s_count, nbest = a.nbest;
   const size_t ob = (size_t)b * nbest;
-  for (long e = tid; e < (long)nbest * T; e += nthr) a.tokens[ob * T + e] = -1;
+  for (long e = tid; e < (long)nbest * Tn; e += nthr) a.tokens[ob * Tn + e] = -1;
   for (int e = tid; e < nbest; e += nthr) {
     a.lens[ob + e] = 0;
     a.score[ob + e] = 0.f;
@@ -381,7 +514,7 @@ __global__ __launch_bounds__(TS_THREADS) void tsync_search_kernel(EmNgramModel m
   if (tid < count) {
     const int i = tid;
     const float core = ts_total(a.w_ctc, h_prev[cur][i], a.w_ng, h_ng[cur][i], a.pen, h_ntok[cur][i]);
-    const float e = (a.has_ng && Tb > 0) ? lane_score(m, h_ctx[cur][i], tok_word(m, a.sos)) : 0.f;
+    const float e = (a.has_ng && t0 + Tb > 0) ? lane_score(m, h_ctx[cur][i], tok_word(m, a.sos)) : 0.f;
     f_ng[i] = h_ng[cur][i] + e;
     f_final[i] = core + a.w_ng * e;
   }
@@ -399,8 +532,8 @@ __global__ __launch_bounds__(TS_THREADS) void tsync_search_kernel(EmNgramModel m
       a.score_ng[ob + rank] = f_ng[i];
       a.score_len[ob + rank] = (float)n;
       int node = h_node[cur][i];
-      for (int k = n - 1; k >= 0 && node > 0; --k) {  // (n <= Tb <= T tokens; the root holds <sos>, not a token)
-        a.tokens[(ob + rank) * T + k] = node_tok[node];
+      for (int k = n - 1; k >= 0 && node > 0; --k) {  // (n <= t0 + Tb <= Tn tokens; the root holds <sos>, not a token)
+        a.tokens[(ob + rank) * Tn + k] = node_tok[node];
         node = node_par[node];
       }
     }
@@ -459,7 +592,8 @@ extern "C" int em_ctc_tsync_search(const int32_t* cand_id, const float* cand_lp,
   if (ws_bytes < (size_t)B * ts_ws_per(T, K, W)) return EM_ERR_WORKSPACE;
   TsArgs a;
   a.cand_id = cand_id, a.cand_lp = cand_lp, a.blank_lp = blank_lp, a.xlens = xlens;
-  a.T = T, a.K = K, a.W = W, a.nbest = nbest, a.sos = sos, a.blank = blank;
+  a.T = T, a.Tn = T, a.K = K, a.W = W, a.nbest = nbest, a.sos = sos, a.blank = blank;
+  a.n_new = a.slot = a.reset = nullptr, a.frames = a.status = nullptr, a.n_slots = 0;
   int cap = 16;
   while (cap < 2 * W * (K + 1)) cap <<= 1;
   a.cap = cap;
@@ -470,7 +604,50 @@ extern "C" int em_ctc_tsync_search(const int32_t* cand_id, const float* cand_lp,
   a.ws = (char*)ws, a.ws_per = ts_ws_per(T, K, W);
   EmNgramModel m = {};
   if (ngram) m = *ngram;
-  hipLaunchKernelGGL(tsync_search_kernel, dim3(B), dim3(TS_THREADS), 0, (hipStream_t)stream, m, a);
+  hipLaunchKernelGGL(tsync_kernel<false>, dim3(B), dim3(TS_THREADS), 0, (hipStream_t)stream, m, a);
+  EM_CHECK_LAUNCH();
+  return EM_OK;
+}
+
+extern "C" size_t em_ctc_tsync_state_bytes(int32_t max_frames, int32_t K, int32_t W) {
+  if (max_frames < 1 || K < 1 || K > TS_K_MAX || W < 1 || W > TS_W_MAX) return 0;
+  if ((long)max_frames * W + 1 > INT_MAX / 2) return 0;
+  return ts_state_per(max_frames, K, W);
+}
+
+extern "C" int em_ctc_tsync_extend(const int32_t* cand_id, const float* cand_lp, const float* blank_lp, const int32_t* n_new,
+                                   const int32_t* slot, const int32_t* reset, int32_t S, int32_t Tc, int32_t K, int32_t W,
+                                   int32_t max_frames, int32_t nbest, int32_t sos, int32_t blank, float w_ctc, float w_ngram,
+                                   float penalty, const EmNgramModel* ngram, void* state, int32_t n_slots, size_t slot_bytes,
+                                   int32_t* tokens, int32_t* lens, int32_t* count, float* score, float* score_ctc,
+                                   float* score_ngram, float* score_len, int32_t* frames, int32_t* status, void* stream) {
+  if (S < 0 || Tc < 1 || K < 1 || W < 1 || max_frames < 1 || nbest < 1 || n_slots < 1 || sos < 0 || blank < 0 || sos == blank)
+    return EM_ERR_BAD_ARG;
+  if (K > TS_K_MAX || W > TS_W_MAX || (long)max_frames * W + 1 > INT_MAX / 2 || (long)S * nbest * max_frames > INT_MAX ||
+      (long)S * Tc * K > INT_MAX)
+    return EM_ERR_UNSUPPORTED;
+  if (S == 0) return EM_OK;
+  if (!cand_id || !cand_lp || !blank_lp || !n_new || !slot || !reset || !state || !tokens || !lens || !count || !score ||
+      !score_ctc || !score_ngram || !score_len || !frames || !status)
+    return EM_ERR_BAD_ARG;
+  if (ngram && ts_check_model(ngram) != EM_OK) return EM_ERR_BAD_ARG;
+  if (slot_bytes < ts_state_per(max_frames, K, W)) return EM_ERR_WORKSPACE;
+  if (slot_bytes % 8 != 0 || (size_t)state % 8 != 0) return EM_ERR_BAD_ARG;  // (a slot starts with 64-bit records)
+  TsArgs a;
+  a.cand_id = cand_id, a.cand_lp = cand_lp, a.blank_lp = blank_lp, a.xlens = nullptr;
+  a.T = Tc, a.Tn = max_frames, a.K = K, a.W = W, a.nbest = nbest, a.sos = sos, a.blank = blank;
+  int cap = 16;
+  while (cap < 2 * W * (K + 1)) cap <<= 1;
+  a.cap = cap;
+  a.has_ng = ngram ? 1 : 0;
+  a.w_ctc = w_ctc, a.w_ng = ngram ? w_ngram : 0.f, a.pen = penalty;
+  a.tokens = tokens, a.lens = lens, a.count = count;
+  a.score = score, a.score_ctc = score_ctc, a.score_ng = score_ngram, a.score_len = score_len;
+  a.ws = (char*)state, a.ws_per = slot_bytes;
+  a.n_new = n_new, a.slot = slot, a.reset = reset, a.frames = frames, a.status = status, a.n_slots = n_slots;
+  EmNgramModel m = {};
+  if (ngram) m = *ngram;
+  hipLaunchKernelGGL(tsync_kernel<true>, dim3(S), dim3(TS_THREADS), 0, (hipStream_t)stream, m, a);
   EM_CHECK_LAUNCH();
   return EM_OK;
 }

@@ -416,6 +416,10 @@ _SIGNATURES = {
                                       C.c_float, C.POINTER(EmNgramModel), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "em_ctc_tsync_search_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32]),
     "em_ctc_tsync_limits": (None, [_vp, _vp]),
+    "em_ctc_tsync_state_bytes": (_sz, [_i32, _i32, _i32]),
+    "em_ctc_tsync_extend": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, C.c_float,
+                                      C.c_float, C.c_float, C.POINTER(EmNgramModel), _vp, _i32, _sz, _vp, _vp, _vp, _vp, _vp,
+                                      _vp, _vp, _vp, _vp, _vp]),
     "em_ngram_score": (C.c_int, [C.POINTER(EmNgramModel), _i32, _vp, _vp, _vp, _vp, _i32, _vp, _vp]),
     "em_arpa_count": (C.c_int, [C.c_char_p, _vp, _vp, _vp]),
     "em_arpa_load": (C.c_int, [C.c_char_p, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -37,6 +37,7 @@
  *         (tests/test_gpu_maskctc.py).
  *       em_ctc_frame_topk: cand_id, cand_lp [M][K] and blank_lp [M] whole; em_ctc_tsync_search: every output whole
  *         (tokens -1 behind lens; lens 0 and scores 0 behind count) (tests/test_gpu_ctc_tsync.py).
+ *       em_ctc_tsync_extend: every output whole, in the same way; its `state` is NOT scratch (persistent, see there).
  *   - EmSearchBuffers: the caller writes xlens / maxlens / minlens per search and ZEROES ONCE, at allocation, mem_vT,
  *     rnn_hs, rnn_cs and rnn_hin (and again mem_vT whenever Tpad changes under it: the streaming search).  The library
  *     leaves their zero regions zero - the columns T .. Tpad of mem_vT, the channels nhid .. d of every recurrent state
@@ -1381,6 +1382,41 @@ int em_ctc_tsync_search(const int32_t* cand_id, const float* cand_lp, const floa
                         size_t ws_bytes, void* stream);
 size_t em_ctc_tsync_search_workspace_bytes(int32_t B, int32_t T, int32_t K, int32_t W);
 void em_ctc_tsync_limits(int32_t* W_max, int32_t* K_max);
+
+/*   em_ctc_tsync_extend: the same walk, RESUMABLE: a call feeds row r the next n_new[r] frames of the utterance that lives
+ *      in slot[r] of a state slab and returns that utterance's n-best list so far.  The defining property: after any
+ *      sequence of calls that fed a slot the frames 0 .. t-1, however they were split (calls with no new frame included)
+ *      and whatever else the launches served, every output of the row is, bit for bit, what em_ctc_tsync_search returns
+ *      for the same candidate tables with xlens = t - the <eos> term of the n-gram included: a partial result is "the
+ *      result if the utterance ended here".  Emission never changes the state; there is no final flag.
+ *      cand_id / cand_lp [S][Tc][K], blank_lp [S][Tc]: the NEW frames of this call, row r's at [r][0 .. n_new[r]);
+ *      n_new [S] is clamped to [0, Tc] (Tc >= 1; all zeros: emission only); slot [S]: DISTINCT slots in [0, n_slots) - the
+ *      caller's duty; reset [S]: nonzero = the slot starts a new utterance: it is initialised as the one-shot walk
+ *      initialises itself and nothing of its previous contents is read.
+ *      state: n_slots slots of slot_bytes each (a multiple of 8, >= em_ctc_tsync_state_bytes(max_frames, K, W), which is 0
+ *      for refused shapes; a smaller one: EM_ERR_WORKSPACE).  The slab is PERSISTENT: it is the search's memory between two
+ *      calls, the caller keeps it and hands it back untouched - it is not scratch, and "Scratch memory" above does not
+ *      cover it.  A slot whose first call did not say reset is refused per row (status 2).  A slot holds a header (frames
+ *      consumed, beam count, parity of the (p_nb, p_b) halves, K, W, max_frames as first used), the beam entries, the slot
+ *      records of the last frame's members that left the beam, and the node arena (max_frames W + 1 nodes, ids by the
+ *      absolute frame).  It holds no address and no slot index: a slot, or the slab, may be copied or moved to another
+ *      index between two calls.
+ *      status [S]: 0; 1 = frames + n_new[r] > max_frames: the row consumed NOTHING (all or nothing), its outputs are those
+ *      of the frames so far; 2 = the slot's header does not carry this call's K, W, max_frames (or was never reset): nothing
+ *      consumed, the slot untouched, count 0; 3 = slot[r] outside [0, n_slots): nothing touched, count 0.  A row never
+ *      degrades silently.  frames [S]: the frames consumed so far, after this call (0 for status 2 and 3).
+ *      Outputs as em_ctc_tsync_search's with the row stride max_frames: tokens [S][nbest][max_frames]; every element of
+ *      every output is written on every call (tokens -1 behind lens; lens 0 and scores 0 behind count); no frames so far:
+ *      the empty hypothesis, every score 0.  A row depends on its own slot, its own tables and n_new[r] only - not on S,
+ *      Tc or the other rows.  Refusals before any launch as em_ctc_tsync_search's (limits, nbest >= 1, sos != blank, the
+ *      model).  One workgroup per row, every loop bounded at launch, enqueue only.  (tests/test_gpu_ctc_tsync_stream.py) */
+size_t em_ctc_tsync_state_bytes(int32_t max_frames, int32_t K, int32_t W);
+int em_ctc_tsync_extend(const int32_t* cand_id, const float* cand_lp, const float* blank_lp, const int32_t* n_new,
+                        const int32_t* slot, const int32_t* reset, int32_t S, int32_t Tc, int32_t K, int32_t W,
+                        int32_t max_frames, int32_t nbest, int32_t sos, int32_t blank, float w_ctc, float w_ngram,
+                        float penalty, const struct EmNgramModel* ngram, void* state, int32_t n_slots, size_t slot_bytes,
+                        int32_t* tokens, int32_t* lens, int32_t* count, float* score, float* score_ctc, float* score_ngram,
+                        float* score_len, int32_t* frames, int32_t* status, void* stream);
 
 /* ---- transducer (RNN-T) decoding (csrc/transducer.hip): the prediction network as a decoder, the joint network and the
  *      greedy search.  Reference: espnet2/asr/decoder/transducer_decoder.py (TransducerDecoder), espnet2/asr_transducer/
