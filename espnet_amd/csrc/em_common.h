@@ -156,6 +156,12 @@ __device__ __forceinline__ int wave_allmin_dpp(int v) {
   const int c = __builtin_amdgcn_readlane(v, 32), d = __builtin_amdgcn_readlane(v, 48);
   return min(min(a, b), min(c, d));
 }
+// One arg-max round over a wave's (value, index) pairs: *wb = the largest value, *wi = the lowest index among the lanes that
+// hold it (0x7fffffff marks "no index").  Every lane returns the same pair.
+__device__ __forceinline__ void wave_argmax_lowest(float best, int bi, float* wb, int* wi) {
+  *wb = wave_allmax_dpp(best);
+  *wi = wave_allmin_dpp(best == *wb ? bi : 0x7fffffff);
+}
 
 #define EM_CHECK_LAUNCH()                                  \
   do {                                                     \

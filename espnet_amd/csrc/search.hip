@@ -20,7 +20,13 @@
 // CTC prefix scoring: a candidate's log psi is a reduction over frames of terms built from the
 // PREFIX's forward variables, so it is computed by one wave per (row, candidate) with lanes over
 // frames; the forward-variable recurrence itself (sequential in t) runs only for the W winners
-// per utterance, in the update kernel.  CTC log-probs are kept transposed ([V][B*T]).
+// per utterance (ctc_chain_wg), in the step's tail.  CTC log-probs are kept transposed ([V][B*T]).
+//
+// The tail of a step (selection, the winners' CTC state, the new rows, the ended list) has three forms: one launch
+// (tail_kernel, the default), three launches (select_kernel, ctc_state_kernel, update_kernel: beams above 16, long
+// memories, ESPNET_AMD_NO_TAIL_FUSION) and the streaming search's host-driven pair (online_best_kernel /
+// online_commit_kernel).  They differ in who does what when; what is computed is written once (new_row_record,
+// copy_ancestors, commit_row, ended_pass, winner_ctc_operands) and called from each.
 #include <math.h>
 #include <stdlib.h>
 
@@ -52,8 +58,8 @@ __device__ __forceinline__ float logaddexp_(float a, float b) {
 // log psi of a candidate needs NO recurrence: log_psi = logsumexp_t(log_phi[t-1] + x[t]) (+)
 // r[start-1, 0] where log_phi comes from the PREFIX's forward variables (ctc_prefix_score.py
 // :135-144, :166-181).  It is a pure reduction over t -> one wave per (row, candidate), lanes over
-// frames (`candidate_kernel`).  Only the W winners per utterance need the sequential recurrence
-// r[t] (:158-164), which yields the next step's r_prev (`ctc_state_scan`).
+// frames (`ctc_psi_wave`; 16 lanes per slot in `logsoftmax_prebeam_kernel`).  Only the W winners per utterance need
+// the sequential recurrence r[t] (:158-164), which yields the next step's r_prev (`ctc_chain_wg`).
 
 struct Ctx {
   EmSearchParams p;
@@ -235,8 +241,9 @@ __global__ __launch_bounds__(256) void logsoftmax_prebeam_kernel(Ctx c, int i_ho
     int pops = 0;
     bool exact = false;
     for (int k = 0; k < SS; ++k) {
-      const float wb = wave_allmax_dpp(v1);
-      const int wi = wave_allmin_dpp(v1 == wb ? i1 : 0x7fffffff);  // lowest id among the holders of the maximum
+      float wb;
+      int wi;
+      wave_argmax_lowest(v1, i1, &wb, &wi);  // lowest id among the holders of the maximum
       if (lane == 0) {
         m_v[wave * SS + k] = wb;
         m_i[wave * SS + k] = wi;
@@ -263,8 +270,9 @@ __global__ __launch_bounds__(256) void logsoftmax_prebeam_kernel(Ctx c, int i_ho
             best = w[q];
             bi = tid + 256 * q;
           }
-        const float wb = wave_allmax_dpp(best);
-        const int wi = wave_allmin_dpp(best == wb ? bi : 0x7fffffff);
+        float wb;
+        int wi;
+        wave_argmax_lowest(best, bi, &wb, &wi);
         if (lane == 0) {
           m_v[wave * SS + k] = wb;
           m_i[wave * SS + k] = wi;
@@ -289,8 +297,9 @@ __global__ __launch_bounds__(256) void logsoftmax_prebeam_kernel(Ctx c, int i_ho
       float cv = lane < 4 * SS ? m_v[lane] : -INFINITY;
       const int ci = lane < 4 * SS ? m_i[lane] : 0x7fffffff;
       for (int k = 0; k < SS; ++k) {
-        const float wb = wave_allmax_dpp(cv);
-        const int wi = wave_allmin_dpp(cv == wb ? ci : 0x7fffffff);
+        float wb;
+        int wi;
+        wave_argmax_lowest(cv, ci, &wb, &wi);
         emit(k, wb, wi);
         if (ci == wi) cv = -INFINITY;
       }
@@ -313,8 +322,9 @@ __global__ __launch_bounds__(256) void logsoftmax_prebeam_kernel(Ctx c, int i_ho
             best = cv[q];
             bi = ci[q];
           }
-        const float wb = wave_allmax_dpp(best);
-        const int wi = wave_allmin_dpp(best == wb ? bi : 0x7fffffff);
+        float wb;
+        int wi;
+        wave_argmax_lowest(best, bi, &wb, &wi);
         emit(k, wb, wi);
 #pragma unroll
         for (int q = 0; q < NQ; ++q)
@@ -469,6 +479,20 @@ __device__ __forceinline__ float ctc_psi_wave(const float2* __restrict__ rprev, 
   return M + logf(sm);
 }
 
+// log psi of one candidate slot by one wave: blank -> logzero (:188-190), <eos> -> the prefix's total probability
+// logaddexp(r[xlen-1]) (:184-186), any other label -> ctc_psi_wave.  rprev = the row's forward variables, lpT_b = the
+// utterance's first column of the transposed log-probs, BT = the stride between labels, *last = the prefix's last label.
+__device__ __forceinline__ float slot_log_psi(const float2* __restrict__ rprev, const float* __restrict__ lpT_b, size_t BT,
+                                              int tk, const int* __restrict__ last, int eos, int blank, int i, int xlen,
+                                              int lane) {
+  if (tk == blank && eos != blank) return LOGZERO;
+  if (tk == eos) {
+    const float2 re = rprev[xlen - 1];
+    return logaddexp_(re.x, re.y);
+  }
+  return ctc_psi_wave(rprev, lpT_b + (size_t)tk * BT, tk == *last, i, xlen, lane);
+}
+
 // ---- step 2: candidate totals.  One wave per (row, candidate slot), 4 waves per block ----------
 //   pre-beam mode  : slots 0..S-1 = cand_tok, slot S = <eos> (always scored, :186-187)
 //   all-vocab mode : slot s = token s (S == V, NC == V)
@@ -524,17 +548,8 @@ __global__ __launch_bounds__(256) void candidate_kernel(Ctx c, int i_host) {
     const int xlen = c.b.xlens[b];
     const int LT = ldt(c.p);
     const float2* rprev = (const float2*)(i & 1 ? c.b.r_b : c.b.r_a) + (size_t)r * LT;
-    float psi;
-    if (tokc == c.p.blank && c.p.eos != c.p.blank) {
-      psi = LOGZERO;  // :188-190
-    } else if (tokc == c.p.eos) {
-      const float2 re = rprev[xlen - 1];
-      psi = logaddexp_(re.x, re.y);  // :184-186
-    } else {
-      const bool same = (tokc == c.b.tok[(size_t)i * c.p.B * c.p.W + r]);
-      const float* xc = c.b.ctc_lpT + (size_t)tokc * c.p.B * LT + (size_t)b * LT;
-      psi = ctc_psi_wave(rprev, xc, same, i, xlen, lane);
-    }
+    const float psi = slot_log_psi(rprev, c.b.ctc_lpT + (size_t)b * LT, (size_t)c.p.B * LT, tokc,
+                                   c.b.tok + (size_t)i * c.p.B * c.p.W + r, c.p.eos, c.p.blank, i, xlen, lane);
     if (lane == 0) c.b.cand_psi[(size_t)r * NC + s] = psi;
     total = total + c.p.w_ctc * (psi - c.b.s_prev[r]);
   }
@@ -577,8 +592,9 @@ __device__ __forceinline__ void select_wave(const Ctx& c, int b, int lane, int* 
         best = x[k];
         bi = lane + 64 * k;
       }
-    const float wb = wave_allmax_dpp(best);
-    const int wi = wave_allmin_dpp(best == wb ? bi : 0x7fffffff);
+    float wb;
+    int wi;
+    wave_argmax_lowest(best, bi, &wb, &wi);
     if (lane == 0) {
       const int sel = (wb > -INFINITY) ? wi : -1;
       c.b.sel_idx[b * W + r] = sel;
@@ -622,8 +638,9 @@ __global__ __launch_bounds__(64) void select_kernel(Ctx c) {
         bi = v;
       }
     }
-    const float wb = wave_allmax_dpp(best);
-    const int wi = wave_allmin_dpp(best == wb ? bi : 0x7fffffff);
+    float wb;
+    int wi;
+    wave_argmax_lowest(best, bi, &wb, &wi);
     best = wb;
     bi = wi;
     if (lane == 0) {
@@ -636,18 +653,13 @@ __global__ __launch_bounds__(64) void select_kernel(Ctx c) {
 }
 
 // ---- step 3b: CTC forward variables of the winners (scorers/ctc.py:54-62) ---------------------
-// One 64-thread workgroup per new row (prefix of row `prow` + label tk).  The recurrence
-// r[t] = logsumexp(..) (ctc_prefix_score.py:158-164) is sequential in t, so everything that is
-// not on the chain is taken off it: all lanes stage x[t][tk], x[t][blank] and the phi terms
-// (:135-144, computed in parallel from the prefix's r_prev) in LDS with coalesced reads, lane 0
-// walks the chain LDS -> LDS, all lanes write the result back coalesced.  Only t >= max(i,1)-1
-// is produced: a later step's recurrence starts at t = i+1 and reads r_prev[t-1].
-// Forward variables r[t] = (r^n, r^b) of prefix + label (ctc_prefix_score.py:131-132, 158-164) by one
-// 64-thread workgroup: all lanes stage x[t][label], x[t][blank] and the phi terms in LDS with coalesced
-// reads, lane 0 walks the sequential chain LDS -> LDS, all lanes write the result back coalesced.  Only
+// Forward variables r[t] = (r^n, r^b) of a new row (prefix of row `prow` + label tk; ctc_prefix_score.py:131-132,
+// 158-164) by 64 threads.  The recurrence is sequential in t, so everything that is not on the chain is taken off it:
+// all lanes stage x[t][tk], x[t][blank] and the phi terms (:135-144, computed in parallel from the prefix's r_prev) in
+// LDS with coalesced reads, the chain runs LDS -> LDS, all lanes write the result back coalesced.  Only
 // t >= max(i,1)-1 is produced: a later step's recurrence starts at t = i+1 and reads r_prev[t-1].
 //
-// Round 3: the chain is no longer walked by one lane.  In the log semiring the step t is LINEAR in (r^n, r^b, 1):
+// The chain is not walked by one lane.  In the log semiring the step t is LINEAR in (r^n, r^b, 1):
 //     r^n[t] = logsum(x_n[t] + r^n[t-1], (x_n[t] + phi[t]) + 0)        r^b[t] = logsum(x_b[t] + r^n[t-1], x_b[t] + r^b[t-1])
 // i.e. a matrix M_t = [[a, -, c], [d, e, f], [-, -, 0]] with a = x_n, c = x_n + phi, d = e = x_b, f = "zero", and
 // products of such matrices keep that shape (five numbers).  So: every lane composes the steps of its own chunk of
@@ -735,13 +747,33 @@ __device__ __forceinline__ void ctc_chain_wg(const float2* __restrict__ rprev, c
   ctc_sync<WG_SYNC>();
   for (int t = start - 1 + lane; t < xlen; t += 64) rout[t] = s_out[t];
 }
+// The operands of ctc_chain_wg for the winner (row prow of utterance b) + label tk -> new row rnew, at step i: the
+// label's and the blank's log-prob columns, the prefix's forward variables (parity i & 1), the new row's (the other
+// parity) and whether the label repeats the prefix's last one.
+struct CtcOperands {
+  const float *xc, *xb;
+  const float2* rprev;
+  float2* rout;
+  bool same;
+};
+__device__ __forceinline__ CtcOperands winner_ctc_operands(const Ctx& c, int b, int prow, int rnew, int tk, int i) {
+  const int LT = ldt(c.p), n = c.p.B * c.p.W;
+  const size_t BT = (size_t)c.p.B * LT;
+  CtcOperands o;
+  o.xc = c.b.ctc_lpT + (size_t)tk * BT + (size_t)b * LT;
+  o.xb = c.b.ctc_lpT + (size_t)c.p.blank * BT + (size_t)b * LT;
+  o.rprev = (const float2*)((i & 1) ? c.b.r_b : c.b.r_a) + (size_t)prow * LT;
+  o.rout = (float2*)((i & 1) ? c.b.r_a : c.b.r_b) + (size_t)rnew * LT;
+  o.same = (tk == c.b.tok[(size_t)i * n + prow]);
+  return o;
+}
 __global__ __launch_bounds__(64) void ctc_state_kernel(Ctx c, int i_host) {
   const int i = c.b.step ? *c.b.step : i_host;
   if (i >= c.p.Lmax - 1) return;
   __shared__ float s_xn[CTC_TMAX], s_xb[CTC_TMAX], s_phi[CTC_TMAX];
   __shared__ float2 s_out[CTC_TMAX];
   const int rnew = blockIdx.x, lane = threadIdx.x;
-  const int W = c.p.W, NC = c.p.NC, n = c.p.B * c.p.W;
+  const int W = c.p.W, NC = c.p.NC;
   const int b = rnew / W;
   if (c.b.done[b]) return;
   const int sel = c.b.sel_idx[rnew];
@@ -750,15 +782,8 @@ __global__ __launch_bounds__(64) void ctc_state_kernel(Ctx c, int i_host) {
   const int prow = b * W + pk;
   const int tk = c.b.cand_tok[(size_t)prow * NC + slot];
   if (tk == c.p.eos || i == c.b.maxlens[b] - 1) return;  // ended: no state needed
-  const int xlen = c.b.xlens[b];
-  const int LT = ldt(c.p);
-  const size_t BT = (size_t)c.p.B * LT;
-  const float* xc = c.b.ctc_lpT + (size_t)tk * BT + (size_t)b * LT;
-  const float* xb = c.b.ctc_lpT + (size_t)c.p.blank * BT + (size_t)b * LT;
-  const float2* rprev = (const float2*)((i & 1) ? c.b.r_b : c.b.r_a) + (size_t)prow * LT;
-  float2* rout = (float2*)((i & 1) ? c.b.r_a : c.b.r_b) + (size_t)rnew * LT;
-  const bool same = (tk == c.b.tok[(size_t)i * n + prow]);
-  ctc_chain_wg<true>(rprev, xc, xb, same, i, xlen, rout, lane, s_xn, s_xb, s_phi, s_out);
+  const CtcOperands o = winner_ctc_operands(c, b, prow, rnew, tk, i);
+  ctc_chain_wg<true>(o.rprev, o.xc, o.xb, o.same, i, c.b.xlens[b], o.rout, lane, s_xn, s_xb, s_phi, s_out);
 }
 
 // ---- step 4: build the new rows (batch_beam_search.py:317-357 + post_process :359-423) ---------
@@ -774,6 +799,135 @@ __device__ __forceinline__ void step_advance(const Ctx& c, int lane) {
     __hip_atomic_fetch_add((unsigned*)c.b.step, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
 }
+
+// The pieces of step 4, each written once for its three forms: update_kernel (after select_kernel and ctc_state_kernel),
+// tail_kernel (the three in one launch) and the streaming pair online_best_kernel / online_commit_kernel.
+//
+// `best` of BatchBeamSearch.search (batch_beam_search.py:317-357) for one new row: the total, the per-scorer sums in
+// the reference's scorer order, the CTC scorer's new state (sprev), the parent row, the token and the two flags.
+struct RowRecord {
+  float score, sdec, sctc, slen, sprev, slm, sng;
+  int prow, tok, valid, ended;
+};
+// sel = the winner's flat index pk * NC + slot among utterance b's candidates (< 0: no winner); tk, psi, total = the
+// winner's token, CTC log psi and total, read only where the row is valid (psi only under a CTC weight).
+__device__ __forceinline__ RowRecord new_row_record(const Ctx& c, int b, int i, int maxlen, int sel, int tk, float psi,
+                                                    float total) {
+  const int W = c.p.W, NC = c.p.NC, V = c.p.V;
+  RowRecord r = {-INFINITY, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, b * W, c.p.eos, sel >= 0, 0};
+  if (r.valid) {
+    const int pk = sel / NC, s = sel - pk * NC;
+    const int prow = b * W + pk;
+    r.prow = prow;
+    r.tok = tk;
+    r.score = total;
+    if (c.p.w_dec != 0.f) r.sdec = c.b.run_sdec[prow] + c.b.dec_logp[(size_t)prow * V + tk];
+    if (c.p.w_len != 0.f) r.slen = c.b.run_slen[prow] + 1.0f;
+    if (c.p.w_lm != 0.f) r.slm = c.b.run_slm[prow] + c.b.lm_logp[(size_t)prow * V + tk];
+    if (c.p.w_ngram != 0.f)
+      r.sng = c.b.run_sngram[prow] + (c.p.ngram_part ? c.b.cand_ngram[(size_t)prow * NC + s] : c.b.ngram_logp[(size_t)prow * V + tk]);
+    if (c.p.w_ctc != 0.f) {
+      r.sctc = c.b.run_sctc[prow] + (psi - c.b.s_prev[prow]);
+      r.sprev = psi;  // select_state: s = log_psi[i, new_id] (scorers/ctc.py:56)
+    }
+  }
+  // ended: the new token is <eos>, or <eos> is forced at the last position (:393-410)
+  r.ended = r.valid && (r.tok == c.p.eos || i == maxlen - 1);
+  return r;
+}
+// new_row_record's inputs of new row rnew where the selection left them in global memory (select_kernel)
+__device__ __forceinline__ void winner_from_tables(const Ctx& c, int b, int rnew, int sel, int* tk, float* psi,
+                                                   float* total) {
+  const size_t at = (size_t)b * c.p.W * c.p.NC + sel;  // = (parent row) * NC + slot
+  *tk = c.b.cand_tok[at];
+  if (c.p.w_ctc != 0.f) *psi = c.b.cand_psi[at];
+  *total = c.b.sel_total[rnew];
+}
+// Ancestor table of new row rnew at step i, by one wave: the parent's positions 0..i, then the row itself.
+__device__ __forceinline__ void copy_ancestors(const Ctx& c, int i, int prow, int rnew, int lane) {
+  const int Lmax = c.p.Lmax;
+  const int* src = ((i & 1) ? c.b.anc_b : c.b.anc_a) + (size_t)prow * Lmax;
+  int* dst = ((i & 1) ? c.b.anc_a : c.b.anc_b) + (size_t)rnew * Lmax;
+  for (int j = lane; j <= i; j += 64) dst[j] = src[j];
+  if (lane == 0 && i + 1 < Lmax) dst[i + 1] = rnew;
+}
+// The state of new row rnew after step i: tree node, alive flag, running scores, CTC state.  A row lives on unless it
+// ended - r.ended is the caller's: offline "<eos> or forced <eos>" (new_row_record), in a stream "<eos>" alone
+// (batch_beam_search.py:412-423).  stash_total: leave the total in sel_total, where update_kernel's ended pass reads it.
+__device__ __forceinline__ void commit_row(const Ctx& c, int i, int rnew, const RowRecord& r, bool stash_total) {
+  const int n = c.p.B * c.p.W;
+  if (r.valid) {
+    c.b.tok[(size_t)(i + 1) * n + rnew] = r.tok;
+    c.b.parent[(size_t)(i + 1) * n + rnew] = r.prow;
+  }
+  const int alive = r.valid && !r.ended;
+  c.b.alive[rnew] = alive;
+  c.b.run_score[rnew] = alive ? r.score : -INFINITY;
+  c.b.run_sdec[rnew] = r.sdec;
+  c.b.run_sctc[rnew] = r.sctc;
+  c.b.run_slen[rnew] = r.slen;
+  if (c.b.run_slm) c.b.run_slm[rnew] = r.slm;
+  if (c.b.run_sngram) c.b.run_sngram[rnew] = r.sng;
+  c.b.s_prev[rnew] = r.sprev;
+  if (stash_total) c.b.sel_total[rnew] = r.score;
+}
+// The serial end of a step for utterance b, by one thread: the ended list in row order (the reference appends in
+// batch order; post_process, batch_beam_search.py:359-423), best_all / best_by_len, end detection and `done`.
+// cnt = the list's length before the step; s_valid / s_end = the new rows' flags; scores(k) = the scores of new row k
+// as an EndedScores, from wherever the caller keeps them.
+struct EndedScores {
+  float total, sdec, sctc, slen, slm, sng;
+};
+template <typename Scores>
+__device__ __forceinline__ void ended_pass(const Ctx& c, int b, int i, int cnt, int minlen, int maxlen,
+                                           const int* s_valid, const int* s_end, const Scores& scores) {
+  const int W = c.p.W, Lmax = c.p.Lmax, cap = c.p.end_cap;
+  int n_alive = 0;
+  for (int k = 0; k < W; ++k) {
+    const int rnew = b * W + k;
+    if (!s_valid[k]) continue;
+    if (!s_end[k]) {
+      ++n_alive;
+      continue;
+    }
+    if (i < minlen) continue;  // :417-418
+    const int forced = (i == maxlen - 1);
+    const int ylen = i + 2 + forced;  // <sos> + (i+1) tokens [+ forced <eos>]
+    const EndedScores row = scores(k);
+    const float sc = row.total;
+    if (cnt < cap) {
+      const size_t e = (size_t)b * cap + cnt;
+      c.b.end_pos[e] = i + 1;
+      c.b.end_slot[e] = rnew;
+      c.b.end_forced[e] = forced;
+      c.b.end_score[e] = sc;
+      c.b.end_sdec[e] = row.sdec;
+      c.b.end_sctc[e] = row.sctc;
+      c.b.end_slen[e] = row.slen;
+      if (c.b.end_slm) c.b.end_slm[e] = row.slm;
+      if (c.b.end_sngram) c.b.end_sngram[e] = row.sng;
+      ++cnt;
+    }
+    if (sc > c.b.best_all[b]) c.b.best_all[b] = sc;
+    float* bl = c.b.best_by_len + (size_t)b * (Lmax + 2) + ylen;
+    if (sc > *bl) *bl = sc;
+  }
+  c.b.end_count[b] = cnt;
+  // end detection (e2e_asr_common.py:14-44) and "no hypothesis" (beam_search.py:446-448)
+  int done = (n_alive == 0);
+  if (!done && c.p.use_end_detect && cnt > 0) {
+    int count = 0;
+    for (int m = 0; m < 3; ++m) {
+      const int len = i - m;
+      if (len < 0) continue;
+      const float v = c.b.best_by_len[(size_t)b * (Lmax + 2) + len];
+      if (v > -INFINITY && v - c.b.best_all[b] < D_END) ++count;
+    }
+    if (count == 3) done = 1;
+  }
+  if (done) c.b.done[b] = 1;
+}
+
 __global__ __launch_bounds__(64) void update_kernel(Ctx c, int i_host) {
   const int i = c.b.step ? *c.b.step : i_host;
   if (i >= c.p.Lmax - 1) {
@@ -781,120 +935,37 @@ __global__ __launch_bounds__(64) void update_kernel(Ctx c, int i_host) {
     return;
   }
   const int b = blockIdx.x, lane = threadIdx.x;
-  const int W = c.p.W, NC = c.p.NC, V = c.p.V, Lmax = c.p.Lmax, n = c.p.B * c.p.W;
-  __shared__ int s_prev_row[64], s_tok[64], s_valid[64], s_end[64];
-  const int* anc_old = (i & 1) ? c.b.anc_b : c.b.anc_a;
-  int* anc_new = (i & 1) ? c.b.anc_a : c.b.anc_b;
-  const float2* r_old = (const float2*)((i & 1) ? c.b.r_b : c.b.r_a);
-  float2* r_new = (float2*)((i & 1) ? c.b.r_a : c.b.r_b);
+  const int W = c.p.W;
+  __shared__ int s_prev_row[64], s_valid[64], s_end[64];
   const bool was_done = c.b.done[b] != 0;
   const int maxlen = c.b.maxlens[b], minlen = c.b.minlens[b];
-
-  float n_score = -INFINITY, n_sdec = 0.f, n_sctc = 0.f, n_slen = 0.f, n_sprev = 0.f, n_slm = 0.f, n_sng = 0.f;
+  RowRecord rec = {};
   if (lane < W) {
     const int rnew = b * W + lane;
     const int sel = was_done ? -1 : c.b.sel_idx[rnew];
-    int valid = sel >= 0, prow = b * W, tk = c.p.eos;
-    if (valid) {
-      const int pk = sel / NC, s = sel - pk * NC;
-      prow = b * W + pk;
-      tk = c.b.cand_tok[(size_t)prow * NC + s];
-      n_score = c.b.sel_total[rnew];
-      if (c.p.w_dec != 0.f) n_sdec = c.b.run_sdec[prow] + c.b.dec_logp[(size_t)prow * V + tk];
-      if (c.p.w_len != 0.f) n_slen = c.b.run_slen[prow] + 1.0f;
-      if (c.p.w_lm != 0.f) n_slm = c.b.run_slm[prow] + c.b.lm_logp[(size_t)prow * V + tk];
-      if (c.p.w_ngram != 0.f)
-        n_sng = c.b.run_sngram[prow] + (c.p.ngram_part ? c.b.cand_ngram[(size_t)prow * NC + s] : c.b.ngram_logp[(size_t)prow * V + tk]);
-      if (c.p.w_ctc != 0.f) {
-        const float psi = c.b.cand_psi[(size_t)prow * NC + s];
-        n_sctc = c.b.run_sctc[prow] + (psi - c.b.s_prev[prow]);
-        n_sprev = psi;  // select_state: s = log_psi[i, new_id] (scorers/ctc.py:56)
-      }
-    }
-    s_prev_row[lane] = prow;
-    s_tok[lane] = tk;
-    s_valid[lane] = valid;
-    // ended: the new token is <eos>, or <eos> is forced at the last position (:393-410)
-    s_end[lane] = valid && (tk == c.p.eos || i == maxlen - 1);
+    int tk = c.p.eos;
+    float psi = 0.f, total = -INFINITY;
+    if (sel >= 0) winner_from_tables(c, b, rnew, sel, &tk, &psi, &total);
+    rec = new_row_record(c, b, i, maxlen, sel, tk, psi, total);
+    s_prev_row[lane] = rec.prow;
+    s_valid[lane] = rec.valid;
+    s_end[lane] = rec.ended;
   }
   __syncthreads();
-  // (a) ancestor tables of the new rows
-  for (int k = 0; k < W; ++k) {
-    if (!s_valid[k]) continue;
-    const int rnew = b * W + k;
-    const int* src = anc_old + (size_t)s_prev_row[k] * Lmax;
-    int* dst = anc_new + (size_t)rnew * Lmax;
-    for (int j = lane; j <= i; j += 64) dst[j] = src[j];
-    if (lane == 0 && i + 1 < Lmax) dst[i + 1] = rnew;
-  }
+  // (a) ancestor tables of the new rows, one after the other
+  for (int k = 0; k < W; ++k)
+    if (s_valid[k]) copy_ancestors(c, i, s_prev_row[k], b * W + k, lane);
   __syncthreads();  // every read of the old per-row state is done
-  if (lane < W) {
-    const int rnew = b * W + lane;
-    if (s_valid[lane]) {
-      c.b.tok[(size_t)(i + 1) * n + rnew] = s_tok[lane];
-      c.b.parent[(size_t)(i + 1) * n + rnew] = s_prev_row[lane];
-    }
-    const int alive = s_valid[lane] && !s_end[lane];
-    c.b.alive[rnew] = alive;
-    c.b.run_score[rnew] = alive ? n_score : -INFINITY;
-    c.b.run_sdec[rnew] = n_sdec;
-    c.b.run_sctc[rnew] = n_sctc;
-    c.b.run_slen[rnew] = n_slen;
-    if (c.b.run_slm) c.b.run_slm[rnew] = n_slm;
-    if (c.b.run_sngram) c.b.run_sngram[rnew] = n_sng;
-    c.b.s_prev[rnew] = n_sprev;
-    // stash for the serial ended-list pass
-    c.b.sel_total[rnew] = n_score;
-  }
+  // (b) the rows' state; the totals are stashed in sel_total for the serial pass
+  if (lane < W) commit_row(c, i, b * W + lane, rec, true);
   __syncthreads();
-  if (lane == 0 && !was_done) {
-    // (c) ended list, in row order (the reference appends in batch order)
-    int cnt = c.b.end_count[b];
-    const int cap = c.p.end_cap;
-    int n_alive = 0;
-    for (int k = 0; k < W; ++k) {
-      const int rnew = b * W + k;
-      if (!s_valid[k]) continue;
-      if (!s_end[k]) {
-        ++n_alive;
-        continue;
-      }
-      if (i < minlen) continue;  // :417-418
-      const int forced = (i == maxlen - 1);
-      const int ylen = i + 2 + forced;  // <sos> + (i+1) tokens [+ forced <eos>]
-      const float sc = c.b.sel_total[rnew];
-      if (cnt < cap) {
-        const size_t e = (size_t)b * cap + cnt;
-        c.b.end_pos[e] = i + 1;
-        c.b.end_slot[e] = rnew;
-        c.b.end_forced[e] = forced;
-        c.b.end_score[e] = sc;
-        c.b.end_sdec[e] = c.b.run_sdec[rnew];
-        c.b.end_sctc[e] = c.b.run_sctc[rnew];
-        c.b.end_slen[e] = c.b.run_slen[rnew];
-        if (c.b.end_slm) c.b.end_slm[e] = c.b.run_slm[rnew];
-        if (c.b.end_sngram) c.b.end_sngram[e] = c.b.run_sngram[rnew];
-        ++cnt;
-      }
-      if (sc > c.b.best_all[b]) c.b.best_all[b] = sc;
-      float* bl = c.b.best_by_len + (size_t)b * (Lmax + 2) + ylen;
-      if (sc > *bl) *bl = sc;
-    }
-    c.b.end_count[b] = cnt;
-    // (d) end detection (e2e_asr_common.py:14-44) and "no hypothesis" (beam_search.py:446-448)
-    int done = (n_alive == 0);
-    if (!done && c.p.use_end_detect && cnt > 0) {
-      int count = 0;
-      for (int m = 0; m < 3; ++m) {
-        const int len = i - m;
-        if (len < 0) continue;
-        const float v = c.b.best_by_len[(size_t)b * (Lmax + 2) + len];
-        if (v > -INFINITY && v - c.b.best_all[b] < D_END) ++count;
-      }
-      if (count == 3) done = 1;
-    }
-    if (done) c.b.done[b] = 1;
-  }
+  // (c) + (d) ended list and end detection, from the rows' scores in global memory
+  if (lane == 0 && !was_done)
+    ended_pass(c, b, i, c.b.end_count[b], minlen, maxlen, s_valid, s_end, [&](int k) {
+      const int r = b * W + k;
+      return EndedScores{c.b.sel_total[r], c.b.run_sdec[r], c.b.run_sctc[r], c.b.run_slen[r],
+                         c.b.run_slm ? c.b.run_slm[r] : 0.f, c.b.run_sngram ? c.b.run_sngram[r] : 0.f};
+    });
   step_advance(c, lane);
 }
 
@@ -903,8 +974,9 @@ __global__ __launch_bounds__(64) void update_kernel(Ctx c, int i_host) {
 // (select 9.7 us, ctc_state 6.7 us, update 12 us per label step): the selection's rounds were ds_bpermute chains (now
 // DPP, select_wave), and update copied the W ancestor rows one after the other in one wave - W x ceil(i / 64) dependent
 // load -> store round trips - where here wave k copies row k while it also walks row k's CTC chain.
-// Same arithmetic, same order of the ended list as the three kernels (which stay for W > 16, long memories whose
-// chains do not fit the LDS W at a time, and the streaming search, which commits rows under the host's control).
+// The records, the rows' state and the ended list come from the functions shared with the three kernels
+// (new_row_record, commit_row, ended_pass; the three kernels stay for W > 16, long memories whose chains do not fit
+// the LDS W at a time, and the streaming search, which commits rows under the host's control).
 __global__ __launch_bounds__(1024) void tail_kernel(Ctx c, int i_host, int lt_cap) {
   extern __shared__ float tail_lds[];  // per wave: s_xn, s_xb, s_phi [lt_cap] + s_out [lt_cap] float2
   __shared__ int s_prev_row[64], s_tok[64], s_valid[64], s_end[64], s_sel[64];
@@ -918,9 +990,7 @@ __global__ __launch_bounds__(1024) void tail_kernel(Ctx c, int i_host, int lt_ca
     return;
   }
   const int b = blockIdx.x;
-  const int W = c.p.W, NC = c.p.NC, V = c.p.V, Lmax = c.p.Lmax, n = c.p.B * c.p.W;
-  const int* anc_old = (i & 1) ? c.b.anc_b : c.b.anc_a;
-  int* anc_new = (i & 1) ? c.b.anc_a : c.b.anc_b;
+  const int W = c.p.W, NC = c.p.NC;
   const bool was_done = c.b.done[b] != 0;
   const int maxlen = c.b.maxlens[b], minlen = c.b.minlens[b];
   const int cnt0 = c.b.end_count[b];  // (read at entry: not one more dependent round trip at the end)
@@ -931,79 +1001,39 @@ __global__ __launch_bounds__(1024) void tail_kernel(Ctx c, int i_host, int lt_ca
   }
   __syncthreads();
   // ---- the new rows' records (batch_beam_search.py:317-357), wave 0, a lane per row
-  float n_score = -INFINITY, n_sdec = 0.f, n_sctc = 0.f, n_slen = 0.f, n_sprev = 0.f, n_slm = 0.f, n_sng = 0.f;
+  RowRecord rec = {};
   if (wave == 0 && lane < W) {
-    const int sel = was_done ? -1 : s_sel[lane];
-    int valid = sel >= 0, prow = b * W, tk = c.p.eos;
-    if (valid) {
-      const int pk = sel / NC;
-      prow = b * W + pk;
-      tk = s_wtok[lane];  // (= cand_tok[prow][slot], handed over by the selection with the totals)
-      n_score = s_seltot[lane];
-      if (c.p.w_dec != 0.f) n_sdec = c.b.run_sdec[prow] + c.b.dec_logp[(size_t)prow * V + tk];
-      if (c.p.w_len != 0.f) n_slen = c.b.run_slen[prow] + 1.0f;
-      if (c.p.w_lm != 0.f) n_slm = c.b.run_slm[prow] + c.b.lm_logp[(size_t)prow * V + tk];
-      if (c.p.w_ngram != 0.f)
-        n_sng = c.b.run_sngram[prow] + (c.p.ngram_part ? c.b.cand_ngram[(size_t)prow * NC + (sel - pk * NC)]
-                                                       : c.b.ngram_logp[(size_t)prow * V + tk]);
-      if (c.p.w_ctc != 0.f) {
-        const float psi = s_wpsi[lane];
-        n_sctc = c.b.run_sctc[prow] + (psi - c.b.s_prev[prow]);
-        n_sprev = psi;  // select_state: s = log_psi[i, new_id] (scorers/ctc.py:56)
-      }
-    }
-    s_prev_row[lane] = prow;
-    s_tok[lane] = tk;
-    s_valid[lane] = valid;
-    // ended: the new token is <eos>, or <eos> is forced at the last position (:393-410)
-    s_end[lane] = valid && (tk == c.p.eos || i == maxlen - 1);
+    // (token, log psi and total = cand_tok / cand_psi[prow][slot] and sel_total, handed over by the selection.  A row
+    // without a winner, or any row of a done utterance, reads LDS that nobody wrote: new_row_record drops the three
+    // values when sel < 0)
+    rec = new_row_record(c, b, i, maxlen, was_done ? -1 : s_sel[lane], s_wtok[lane], s_wpsi[lane], s_seltot[lane]);
+    s_prev_row[lane] = rec.prow;
+    s_tok[lane] = rec.tok;
+    s_valid[lane] = rec.valid;
+    s_end[lane] = rec.ended;
   }
   __syncthreads();  // every read of the old per-row scalars is done (wave 0 made them all)
   // ---- wave k: row k's ancestor table and CTC forward variables (scorers/ctc.py:54-62)
   if (wave < W && s_valid[wave]) {
-    const int k = wave, rnew = b * W + k, prow = s_prev_row[k], tk = s_tok[k];
-    const int* src = anc_old + (size_t)prow * Lmax;
-    int* dst = anc_new + (size_t)rnew * Lmax;
-    for (int j = lane; j <= i; j += 64) dst[j] = src[j];
-    if (lane == 0 && i + 1 < Lmax) dst[i + 1] = rnew;
+    const int k = wave, rnew = b * W + k, prow = s_prev_row[k];
+    copy_ancestors(c, i, prow, rnew, lane);
     if (c.p.w_ctc != 0.f && !s_end[k]) {  // ended rows need no state
-      const int xlen = c.b.xlens[b];
-      const int LT = ldt(c.p);
-      const size_t BT = (size_t)c.p.B * LT;
-      const float* xc = c.b.ctc_lpT + (size_t)tk * BT + (size_t)b * LT;
-      const float* xb = c.b.ctc_lpT + (size_t)c.p.blank * BT + (size_t)b * LT;
-      const float2* rprev = (const float2*)((i & 1) ? c.b.r_b : c.b.r_a) + (size_t)prow * LT;
-      float2* rout = (float2*)((i & 1) ? c.b.r_a : c.b.r_b) + (size_t)rnew * LT;
-      const bool same = (tk == c.b.tok[(size_t)i * n + prow]);
+      const CtcOperands o = winner_ctc_operands(c, b, prow, rnew, s_tok[k], i);
       float* base = tail_lds + (size_t)wave * 5 * lt_cap;
-      ctc_chain_wg<false>(rprev, xc, xb, same, i, xlen, rout, lane, base, base + lt_cap, base + 2 * lt_cap,
-                          (float2*)(base + 3 * lt_cap));
+      ctc_chain_wg<false>(o.rprev, o.xc, o.xb, o.same, i, c.b.xlens[b], o.rout, lane, base, base + lt_cap,
+                          base + 2 * lt_cap, (float2*)(base + 3 * lt_cap));
     }
   }
-  // ---- wave 0: the rows' scalars, the ended list, end detection (as update_kernel)
+  // ---- wave 0: the rows' state, the ended list, end detection
   if (wave == 0) {
     if (lane < W) {
-      const int rnew = b * W + lane;
-      if (s_valid[lane]) {
-        c.b.tok[(size_t)(i + 1) * n + rnew] = s_tok[lane];
-        c.b.parent[(size_t)(i + 1) * n + rnew] = s_prev_row[lane];
-      }
-      const int alive = s_valid[lane] && !s_end[lane];
-      c.b.alive[rnew] = alive;
-      c.b.run_score[rnew] = alive ? n_score : -INFINITY;
-      c.b.run_sdec[rnew] = n_sdec;
-      c.b.run_sctc[rnew] = n_sctc;
-      c.b.run_slen[rnew] = n_slen;
-      if (c.b.run_slm) c.b.run_slm[rnew] = n_slm;
-      if (c.b.run_sngram) c.b.run_sngram[rnew] = n_sng;
-      c.b.s_prev[rnew] = n_sprev;
-      c.b.sel_total[rnew] = n_score;  // (what update_kernel leaves there)
-      s_seltot[lane] = n_score;
-      s_rec[0][lane] = n_sdec;
-      s_rec[1][lane] = n_sctc;
-      s_rec[2][lane] = n_slen;
-      s_rec[3][lane] = n_slm;
-      s_rec[4][lane] = n_sng;
+      commit_row(c, i, b * W + lane, rec, true);  // (sel_total: what update_kernel leaves there)
+      s_seltot[lane] = rec.score;
+      s_rec[0][lane] = rec.sdec;
+      s_rec[1][lane] = rec.sctc;
+      s_rec[2][lane] = rec.slen;
+      s_rec[3][lane] = rec.slm;
+      s_rec[4][lane] = rec.sng;
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
@@ -1014,54 +1044,10 @@ __global__ __launch_bounds__(1024) void tail_kernel(Ctx c, int i_host, int lt_ca
     const unsigned long long endm = __ballot(lanerow && s_end[lanerow ? lane : 0]);
     const unsigned long long alivem = __ballot(lanerow && s_valid[lanerow ? lane : 0] && !s_end[lanerow ? lane : 0]);
     const bool need_tail = endm != 0ull || alivem == 0ull || (c.p.use_end_detect && cnt0 > 0);
-    if (lane == 0 && !was_done && need_tail) {
-      // ended list, in row order (the reference appends in batch order)
-      int cnt = cnt0;
-      const int cap = c.p.end_cap;
-      int n_alive = 0;
-      for (int k = 0; k < W; ++k) {
-        const int rnew = b * W + k;
-        if (!s_valid[k]) continue;
-        if (!s_end[k]) {
-          ++n_alive;
-          continue;
-        }
-        if (i < minlen) continue;  // :417-418
-        const int forced = (i == maxlen - 1);
-        const int ylen = i + 2 + forced;  // <sos> + (i+1) tokens [+ forced <eos>]
-        const float sc = s_seltot[k];
-        if (cnt < cap) {
-          const size_t e = (size_t)b * cap + cnt;
-          c.b.end_pos[e] = i + 1;
-          c.b.end_slot[e] = rnew;
-          c.b.end_forced[e] = forced;
-          c.b.end_score[e] = sc;
-          c.b.end_sdec[e] = s_rec[0][k];
-          c.b.end_sctc[e] = s_rec[1][k];
-          c.b.end_slen[e] = s_rec[2][k];
-          if (c.b.end_slm) c.b.end_slm[e] = s_rec[3][k];
-          if (c.b.end_sngram) c.b.end_sngram[e] = s_rec[4][k];
-          ++cnt;
-        }
-        if (sc > c.b.best_all[b]) c.b.best_all[b] = sc;
-        float* bl = c.b.best_by_len + (size_t)b * (Lmax + 2) + ylen;
-        if (sc > *bl) *bl = sc;
-      }
-      c.b.end_count[b] = cnt;
-      // end detection (e2e_asr_common.py:14-44) and "no hypothesis" (beam_search.py:446-448)
-      int done = (n_alive == 0);
-      if (!done && c.p.use_end_detect && cnt > 0) {
-        int count = 0;
-        for (int m = 0; m < 3; ++m) {
-          const int len = i - m;
-          if (len < 0) continue;
-          const float v = c.b.best_by_len[(size_t)b * (Lmax + 2) + len];
-          if (v > -INFINITY && v - c.b.best_all[b] < D_END) ++count;
-        }
-        if (count == 3) done = 1;
-      }
-      if (done) c.b.done[b] = 1;
-    }
+    if (lane == 0 && !was_done && need_tail)
+      ended_pass(c, b, i, cnt0, minlen, maxlen, s_valid, s_end, [&](int k) {
+        return EndedScores{s_seltot[k], s_rec[0][k], s_rec[1][k], s_rec[2][k], s_rec[3][k], s_rec[4][k]};
+      });
   }
   step_advance(c, tid);
 }
@@ -1515,7 +1501,7 @@ __global__ void online_extend_r_kernel(Ctx c, int i, int t_old) {
 // [valid, parent slot, token, total, decoder, ctc, length_bonus, lm]; the new s_prev goes to online_psi.
 __global__ __launch_bounds__(64) void online_best_kernel(Ctx c) {
   const int b = blockIdx.x, k = threadIdx.x;
-  const int W = c.p.W, NC = c.p.NC, V = c.p.V;
+  const int W = c.p.W;
   if (k >= W) return;
   const int rnew = b * W + k;
   float* o = c.b.online_best + (size_t)rnew * 8;
@@ -1525,19 +1511,14 @@ __global__ __launch_bounds__(64) void online_best_kernel(Ctx c) {
     c.b.online_psi[rnew] = 0.f;
     return;
   }
-  const int pk = sel / NC, sl = sel - pk * NC, prow = b * W + pk;
-  const int tk = c.b.cand_tok[(size_t)prow * NC + sl];
-  float sdec = 0.f, sctc = 0.f, slen = 0.f, slm = 0.f, psi = 0.f;
-  if (c.p.w_dec != 0.f) sdec = c.b.run_sdec[prow] + c.b.dec_logp[(size_t)prow * V + tk];
-  if (c.p.w_len != 0.f) slen = c.b.run_slen[prow] + 1.0f;
-  if (c.p.w_lm != 0.f) slm = c.b.run_slm[prow] + c.b.lm_logp[(size_t)prow * V + tk];
-  if (c.p.w_ctc != 0.f) {
-    psi = c.b.cand_psi[(size_t)prow * NC + sl];
-    sctc = c.b.run_sctc[prow] + (psi - c.b.s_prev[prow]);
-  }
-  o[0] = 1.f; o[1] = (float)pk; o[2] = (float)tk; o[3] = c.b.sel_total[rnew];
-  o[4] = sdec; o[5] = sctc; o[6] = slen; o[7] = slm;
-  c.b.online_psi[rnew] = psi;
+  int tk;
+  float psi = 0.f, total;
+  winner_from_tables(c, b, rnew, sel, &tk, &psi, &total);
+  // (no forced <eos> here: the host ends a stream's hypotheses, so no maxlen and `ended` is not used)
+  const RowRecord r = new_row_record(c, b, /*i=*/0, /*maxlen=*/0, sel, tk, psi, total);
+  o[0] = 1.f; o[1] = (float)(r.prow - b * W); o[2] = (float)r.tok; o[3] = r.score;
+  o[4] = r.sdec; o[5] = r.sctc; o[6] = r.slen; o[7] = r.slm;
+  c.b.online_psi[rnew] = r.sprev;
 }
 
 // prev_hyps = running_hyps (:459): the per-row scalars are copied; r / anc of the state before step i
@@ -1563,43 +1544,22 @@ __global__ void online_snapshot_kernel(Ctx c, int restore) {
 __global__ __launch_bounds__(64) void online_commit_kernel(Ctx c, int i_host) {
   const int i = c.b.step ? *c.b.step : i_host;  // (graph mode: the host writes the step index before the replay)
   const int b = blockIdx.x, lane = threadIdx.x;
-  const int W = c.p.W, Lmax = c.p.Lmax, n = c.p.B * c.p.W;
-  __shared__ int s_prow[64], s_tok[64], s_valid[64];
-  const int* anc_old = (i & 1) ? c.b.anc_b : c.b.anc_a;
-  int* anc_new = (i & 1) ? c.b.anc_a : c.b.anc_b;
-  float rec[8];
-  if (lane < W) {
-    const float* o = c.b.online_best + (size_t)(b * W + lane) * 8;
-    for (int j = 0; j < 8; ++j) rec[j] = o[j];
-    s_valid[lane] = rec[0] != 0.f;
-    s_prow[lane] = b * W + (int)rec[1];
-    s_tok[lane] = (int)rec[2];
-  }
-  __syncthreads();
-  for (int k = 0; k < W; ++k) {
-    if (!s_valid[k]) continue;
-    const int rnew = b * W + k;
-    const int* src = anc_old + (size_t)s_prow[k] * Lmax;
-    int* dst = anc_new + (size_t)rnew * Lmax;
-    for (int j = lane; j <= i; j += 64) dst[j] = src[j];
-    if (lane == 0 && i + 1 < Lmax) dst[i + 1] = rnew;
-  }
-  __syncthreads();
-  if (lane < W) {
+  const int W = c.p.W;
+  __shared__ int s_prow[64], s_valid[64];
+  RowRecord rec = {};
+  if (lane < W) {  // the record as online_best_kernel left it; a row of a stream ends on <eos> alone
     const int rnew = b * W + lane;
-    if (s_valid[lane]) {
-      c.b.tok[(size_t)(i + 1) * n + rnew] = s_tok[lane];
-      c.b.parent[(size_t)(i + 1) * n + rnew] = s_prow[lane];
-    }
-    const int alive = s_valid[lane] && s_tok[lane] != c.p.eos;
-    c.b.alive[rnew] = alive;
-    c.b.run_score[rnew] = alive ? rec[3] : -INFINITY;
-    c.b.run_sdec[rnew] = rec[4];
-    c.b.run_sctc[rnew] = rec[5];
-    c.b.run_slen[rnew] = rec[6];
-    if (c.b.run_slm) c.b.run_slm[rnew] = rec[7];
-    c.b.s_prev[rnew] = c.b.online_psi[rnew];
+    const float* o = c.b.online_best + (size_t)rnew * 8;
+    rec = {o[3], o[4], o[5], o[6], c.b.online_psi[rnew], o[7], 0.f, b * W + (int)o[1], (int)o[2], o[0] != 0.f, 0};
+    rec.ended = rec.tok == c.p.eos;
+    s_valid[lane] = rec.valid;
+    s_prow[lane] = rec.prow;
   }
+  __syncthreads();
+  for (int k = 0; k < W; ++k)
+    if (s_valid[k]) copy_ancestors(c, i, s_prow[k], b * W + k, lane);
+  __syncthreads();
+  if (lane < W) commit_row(c, i, b * W + lane, rec, false);
 }
 
 int check_online(const EmSearchParams* p, const EmSearchBuffers* b) {
@@ -1728,16 +1688,8 @@ __global__ __launch_bounds__(256) void ctc_prefix_score_kernel(
   const int b = r / W;
   const int tk = cand ? (s < S ? cand[(size_t)r * S + s] : eos) : s;
   const int xlen = xlens[b];
-  const float2* rp = r_prev + (size_t)r * LT;
-  float psi;
-  if (tk == blank && eos != blank) {
-    psi = LOGZERO;  // :188-190
-  } else if (tk == eos) {
-    const float2 re = rp[xlen - 1];
-    psi = logaddexp_(re.x, re.y);  // :184-186
-  } else {
-    psi = ctc_psi_wave(rp, lpT + (size_t)tk * B * LT + (size_t)b * LT, tk == last[r], i, xlen, lane);
-  }
+  const float psi = slot_log_psi(r_prev + (size_t)r * LT, lpT + (size_t)b * LT, (size_t)B * LT, tk, last + r, eos, blank, i,
+                                 xlen, lane);
   if (lane == 0) {
     log_psi[(size_t)r * NC + s] = psi;
     if (scores) scores[(size_t)r * NC + s] = psi - s_prev[r];

@@ -271,6 +271,38 @@ def test_search_with_ngram_part_scorer(tmp_path):
     print(f"{outside} of {len(hyps)} hypotheses end on an <eos> outside their last pre-beam")
 
 
+# ------------------------------------------------------------------------------------------- 5b. the three-launch tail
+@pytest.mark.parametrize("part", [False, True], ids=["full", "part"])
+def test_search_with_ngram_unfused_tail_equals_default(monkeypatch, tmp_path, part):
+    """The n-gram records (run_sngram -> end_sngram) through update_kernel: ESPNET_AMD_NO_TAIL_FUSION=1 returns the
+    hypotheses of the default one-launch tail, bit for bit."""
+    from espnet_amd import lib as L
+    from espnet_amd.nets.scorers.ngram import NgramPartScorer
+
+    g = load_golden("tiny_beam5")
+    sd = golden_state_dict(g)
+    enc, olens = oracle_enc(g, sd)
+    T = int(olens[0])
+    tokens = _tokens(int(g["vocab"]))
+    path = _arpa_for(tmp_path, tokens, 3, seed=21)
+    ng = NgramPartScorer(str(path), tokens) if part else _full(path, tokens)
+    bs = _search(g, sd, "float32", ngram=ng, ngram_weight=0.7)
+    x = enc[:, :T].contiguous().cuda()
+    default = bs.search_batch(x, [T])[0]
+    monkeypatch.setenv("ESPNET_AMD_NO_TAIL_FUSION", "1")
+    L.load().em_dev_switches_reload()
+    try:
+        unfused = bs.search_batch(x, [T])[0]
+    finally:
+        monkeypatch.delenv("ESPNET_AMD_NO_TAIL_FUSION")
+        L.load().em_dev_switches_reload()
+    assert len(default) > 0 and all("ngram" in h.scores for h in default)
+    assert [h.yseq.tolist() for h in unfused] == [h.yseq.tolist() for h in default]
+    for a, b in zip(default, unfused):
+        assert float(a.score) == float(b.score)
+        assert {k: float(v) for k, v in a.scores.items()} == {k: float(v) for k, v in b.scores.items()}
+
+
 # ------------------------------------------------------------------------------------------- 6. weight 0
 def test_zero_ngram_weight_is_the_plain_search(tmp_path):
     g = load_golden("tiny_beam5")
