@@ -13,9 +13,16 @@ Mirrors espnet2/asr/transducer/beam_search_transducer.py (constructor keywords, 
     is the route of an utterance the walk stopped on (a capacity of `beam_limits()`, MAX_EXPANSIONS_PER_FRAME) and of
     beams above the walk's limit; both routes see the same log-probability bits and sum scores in double, so they
     return the same lists.
-  * tsd / alsd / nsc / maes, a language model and multi-blank models raise NotImplementedError.
+  * `lm=` a SequentialRNNLM (lstm / gru), beam_size > 1: shallow fusion as the reference's `use_lm` - the popped
+    hypothesis goes through the LM once (fed sos = vocab - 1, then its labels), `lm_weight * lm_logp[k]` is added to
+    the beam_k label children, which are still chosen on the joint log-probabilities alone; the blank extension gets no
+    LM term.  The walk is `em_transducer_beam_search_lm`, the host route calls `em_transducer_lm_step` one row at a
+    time (the same kernels, so the same bits) and both add the term in double.  LM fusion exists at the beams the walk
+    holds (`beam_limits()["beam"]`); other LMs raise NotImplementedError.
+  * tsd / alsd / nsc / maes and multi-blank models raise NotImplementedError.
 """
 import ctypes as C
+import logging
 from dataclasses import dataclass
 from typing import Any, List, Optional, Sequence, Tuple
 
@@ -23,6 +30,8 @@ import numpy as np
 import torch
 
 from espnet_amd import lib as L
+
+logger = logging.getLogger(__name__)
 
 MAX_WALK_ROWS = 64  # em_transducer_greedy: utterances per call
 # default beam search: expansions of one frame before the search gives up.  The reference's loop has no cap: a model
@@ -55,7 +64,21 @@ class BeamSearchTransducer:
                  nbest: int = 1, token_list: Optional[List[str]] = None, multi_blank_durations: Sequence[int] = (),
                  **other):
         if lm is not None:
-            raise NotImplementedError("BeamSearchTransducer(lm=...): language-model fusion is not on the device path")
+            from espnet_amd.lm.seq_rnn_lm import SequentialRNNLM
+
+            if not isinstance(lm, SequentialRNNLM) or lm.rnn_type not in ("LSTM", "GRU"):
+                kind = f"SequentialRNNLM(rnn_type={lm.rnn_type.lower()!r})" if isinstance(lm, SequentialRNNLM) \
+                    else type(lm).__name__
+                raise NotImplementedError(f"BeamSearchTransducer(lm=...): lm is a {kind}; the transducer search fuses a "
+                                          "SequentialRNNLM with rnn_type lstm or gru")
+            if lm.vocab_size != decoder.vocab_size:
+                raise ValueError(f"BeamSearchTransducer(lm=...): the lm has {lm.vocab_size} tokens, the transducer "
+                                 f"{decoder.vocab_size}")
+            if beam_size > beam_limits()["beam"]:
+                raise NotImplementedError(f"BeamSearchTransducer(lm=...): lm fusion with beam_size={beam_size}; it runs at "
+                                          f"the beams the device walk holds, up to {beam_limits()['beam']}")
+            if beam_size <= 1:
+                logger.info("BeamSearchTransducer: beam_size <= 1 is the greedy search, which does not use the lm")
         if multi_blank_durations:
             raise NotImplementedError("BeamSearchTransducer(multi_blank_durations=...): multi-blank transducers are not on "
                                       "the device path")
@@ -70,6 +93,8 @@ class BeamSearchTransducer:
         self.vocab_size = decoder.vocab_size
         self.blank_id = decoder.blank_id
         self.beam_size = int(beam_size)
+        self.lm, self.lm_weight = lm, float(lm_weight)
+        self.sos = self.vocab_size - 1  # (the reference's: what the LM reads before the first label)
         self.search_type = search_type
         self.score_norm, self.nbest = score_norm, nbest
         self.token_list = token_list
@@ -117,7 +142,7 @@ class BeamSearchTransducer:
         `beam_limits()` or MAX_EXPANSIONS_PER_FRAME - or that has no frame; `search_batch` decodes those with
         `default_beam_search`.  `last_beam` holds the status rows, the steps enqueued and the steps needed.
         Tests: `max_steps` ends the walk after that many steps; `trace` enqueues step by step and keeps each step's
-        (log-prob rows (B, V), trace rows (B, 4 + Lmax)) in `last_beam["steps"]`."""
+        (log-prob rows (B, V), trace rows (B, 4 + Lmax)) - with an LM also its rows (B, V) - in `last_beam["steps"]`."""
         dec, jn = self.decoder, self.joint_network
         L.require_gpu(enc_act, "enc_act")
         B, T, _ = enc_act.shape
@@ -132,13 +157,15 @@ class BeamSearchTransducer:
                                       f"{lim['expansions']} expansions of one frame, {lim['labels']} labels of a hypothesis)")
         dev = enc_act.device
         w, keep = dec.weights(dev)
+        lw, lm_keep = self.lm.transducer_lm_weights(dev) if self.lm is not None else (None, None)
+        lw_ref = C.byref(lw) if lw is not None else None
         # lin_enc per utterance, on exactly the rows default_beam_search hands it: the same GEMM call, so the same bits
         enc_proj = torch.zeros(B, T, w.jp, dtype=torch.float32, device=dev)
         for b in range(B):
             if olens[b] > 0:
                 enc_proj[b, : olens[b]] = jn.enc_proj_device(enc_act[b, : olens[b]])
         lib = L.load()
-        need = int(lib.em_transducer_beam_workspace_bytes(dec.em_dtype, C.byref(w), B, T, self.beam_size))
+        need = int(lib.em_transducer_beam_workspace_bytes_lm(dec.em_dtype, C.byref(w), lw_ref, B, T, self.beam_size))
         if need == 0:
             raise NotImplementedError(f"em_transducer_beam_search: B={B}, T={T}, beam={self.beam_size} are outside one call")
         Tmax = max(olens + [1])
@@ -153,14 +180,16 @@ class BeamSearchTransducer:
         out_cnt = torch.zeros(B, dtype=torch.int32, device=dev)
         step_logp = torch.zeros(B, self.vocab_size, dtype=torch.float32, device=dev) if trace else None
         step_tr = torch.zeros(B, 4 + Lmax, dtype=torch.int32, device=dev) if trace else None
+        step_lm = torch.zeros(B, self.vocab_size, dtype=torch.float32, device=dev) if trace and lw is not None else None
         max_exp = int(MAX_EXPANSIONS_PER_FRAME)  # (read at call time: a test lowers it)
 
         def enqueue(first, steps):
-            L.check(lib.em_transducer_beam_search(dec.em_dtype, C.byref(w), L.ptr(enc_proj), L.ptr(ol), B, T, self.beam_size,
-                                                  max_exp, Lmax, ncap, int(first), int(steps), L.ptr(status), L.ptr(out_tok),
-                                                  L.ptr(out_len), L.ptr(out_score), L.ptr(out_cnt), L.ptr(step_logp),
-                                                  L.ptr(step_tr), L.ptr(ws), need, L.current_stream_ptr()),
-                    "em_transducer_beam_search")
+            L.check(lib.em_transducer_beam_search_lm(dec.em_dtype, C.byref(w), lw_ref, self.lm_weight, L.ptr(enc_proj),
+                                                     L.ptr(ol), B, T, self.beam_size, max_exp, Lmax, ncap, int(first),
+                                                     int(steps), L.ptr(status), L.ptr(out_tok), L.ptr(out_len),
+                                                     L.ptr(out_score), L.ptr(out_cnt), L.ptr(step_logp), L.ptr(step_tr),
+                                                     L.ptr(step_lm), L.ptr(ws), need, L.current_stream_ptr()),
+                    "em_transducer_beam_search_lm")
 
         enqueued, first, steps_kept = 0, True, []
         chunk = Tmax * beam
@@ -172,7 +201,7 @@ class BeamSearchTransducer:
                     step_tr.zero_()
                     enqueue(first, 1)
                     first = False
-                    steps_kept.append((step_logp.clone(), step_tr.clone()))
+                    steps_kept.append((step_logp.clone(), step_tr.clone()) + ((step_lm.clone(),) if lw is not None else ()))
             else:
                 enqueue(first, chunk)
                 first = False
@@ -198,7 +227,7 @@ class BeamSearchTransducer:
                 # the reference's final list: the qualifying kept entries by ascending score (a stable sort)
                 out[b] = self.sort_nbest(sorted(hyps, key=lambda x: x.score))
         self.last_beam = dict(status=st, enqueued=enqueued, needed=int(st[:, 2].max()) if B else 0,
-                              steps=[(a.cpu(), t.cpu()) for a, t in steps_kept] if trace else None)
+                              steps=[tuple(x.cpu() for x in st_) for st_ in steps_kept] if trace else None)
         return out
 
     @torch.no_grad()
@@ -246,8 +275,10 @@ class BeamSearchTransducer:
         beam_k = min(beam, V - 1)
         dev = enc_out.device
         enc_proj = jn.enc_proj_device(enc_out)  # (T, jpad): every frame at once
-        kept = [Hypothesis(score=0.0, yseq=[self.blank_id], dec_state=dec.select_state(dec.init_state(1, dev), 0))]
-        cache = {}
+        lm = self.lm
+        kept = [Hypothesis(score=0.0, yseq=[self.blank_id], dec_state=dec.select_state(dec.init_state(1, dev), 0),
+                           lm_state=lm.init_rows_state(1, dev) if lm is not None else None)]
+        cache, cache_lm = {}, {}
         for t in range(int(enc_out.shape[0])):
             hyps, kept = kept, []
             for expansion in range(MAX_EXPANSIONS_PER_FRAME + 1):
@@ -259,10 +290,22 @@ class BeamSearchTransducer:
                 _, state, _ = dec.score(h, cache)
                 dec_proj = cache["_".join(map(str, h.yseq))][2]
                 logp = jn.logp_device(dec, enc_proj[t : t + 1], dec_proj.unsqueeze(0))[0].cpu().numpy()
-                kept.append(Hypothesis(score=h.score + float(logp[0]), yseq=h.yseq[:], dec_state=h.dec_state))
+                kept.append(Hypothesis(score=h.score + float(logp[0]), yseq=h.yseq[:], dec_state=h.dec_state,
+                                       lm_state=h.lm_state))
                 order = np.argsort(-logp[1:], kind="stable")[:beam_k]  # (ties: the lowest id first, like topk)
+                lm_logp = lm_state = None
+                if lm is not None:  # one row per call: the bits the walk's row of this utterance carries
+                    key = "_".join(map(str, h.yseq))
+                    if key not in cache_lm:
+                        tok = torch.full((1,), self.sos if len(h.yseq) == 1 else h.yseq[-1], dtype=torch.int32, device=dev)
+                        row, st = lm.step_rows(tok, h.lm_state)
+                        cache_lm[key] = (row[0].cpu().numpy(), st)
+                    lm_logp, lm_state = cache_lm[key]
                 for k in order:
-                    hyps.append(Hypothesis(score=h.score + float(logp[1 + k]), yseq=h.yseq + [int(k) + 1], dec_state=state))
+                    score = h.score + float(logp[1 + k])
+                    if lm is not None:  # (Python floats: the product and the sum are rounded one after the other)
+                        score = score + self.lm_weight * float(lm_logp[1 + k])
+                    hyps.append(Hypothesis(score=score, yseq=h.yseq + [int(k) + 1], dec_state=state, lm_state=lm_state))
                 best_left = max(x.score for x in hyps)
                 most_prob = sorted([x for x in kept if x.score > best_left], key=lambda x: x.score)
                 if len(most_prob) >= beam:

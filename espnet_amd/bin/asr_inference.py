@@ -50,6 +50,23 @@ def resolve_dtype(dtype: str) -> str:
     raise ValueError(f"unknown dtype {dtype!r}")
 
 
+def check_transducer_lm(asr_model, lm_train_config, ngram_file, beam_size):
+    """What a transducer model refuses of the LM options, decided before any LM file is opened: an n-gram, and a neural LM
+    at a beam the device walk does not hold (the per-utterance host search with an LM takes tens of seconds per batch
+    there; it is not a silent default)."""
+    if not asr_model.use_transducer_decoder:
+        return
+    if ngram_file is not None:
+        raise NotImplementedError("ngram_file with a transducer model: n-gram fusion in the transducer search is outside "
+                                  "the MI355X hot path")
+    if lm_train_config is not None:
+        from espnet_amd.asr.transducer.beam_search_transducer import beam_limits
+
+        limit = beam_limits()["beam"]
+        if beam_size > limit:
+            raise NotImplementedError(f"lm_train_config with a transducer model at beam_size={beam_size}: language-model "
+                                      f"fusion runs at the beams the device walk holds, up to {limit}")
+
 
 def pack_modules(device, modules):
     """The weights of the modules a decode will use repacked for the kernels now, not inside the first decode call (an LM
@@ -129,15 +146,22 @@ class Speech2Text:
                 sos=asr_model.sos, beam_size=beam_size, scorers=scorers, token_list=token_list, blank=asr_model.blank_id,
                 weights=dict(ctc=ctc_weight, ngram=ngram_weight if self.ngram is not None else 0.0, length_bonus=penalty))
         elif asr_model.use_transducer_decoder:  # asr_inference.py: BeamSearchTransducer in place of the joint search
-            if lm_train_config is not None or ngram_file is not None:
-                raise NotImplementedError("lm_train_config / ngram_file with a transducer model: language-model fusion in "
-                                          "the transducer search is outside the MI355X hot path")
+            check_transducer_lm(asr_model, lm_train_config, ngram_file, beam_size)
+            if ctc_greedy and lm_train_config is not None:
+                logger.info("ctc_greedy=True decodes with the CTC head alone: lm_train_config is not used")
             if not ctc_greedy:
                 from espnet_amd.asr.transducer.beam_search_transducer import BeamSearchTransducer
 
+                lm_kw = {}
+                if lm_train_config is not None:  # shallow fusion: BeamSearchTransducer(lm=..., lm_weight=...)
+                    from espnet_amd.tasks.lm import LMTask
+
+                    self.lm_model, _ = LMTask.build_model_from_file(lm_train_config, lm_file, device, compute_dtype=dtype)
+                    self.lm = self.lm_model.lm
+                    lm_kw = dict(lm=self.lm, lm_weight=lm_weight)
                 self.beam_search_transducer = BeamSearchTransducer(
                     decoder=asr_model.decoder, joint_network=asr_model.joint_network, beam_size=beam_size,
-                    nbest=nbest, token_list=token_list, **(transducer_conf or {}))
+                    nbest=nbest, token_list=token_list, **lm_kw, **(transducer_conf or {}))
         elif transducer_conf is not None:
             raise ValueError("transducer_conf was given, but the model has no joint network (decoder: transducer)")
         elif not ctc_greedy:  # (greedy CTC decodes without scorers: an n-gram does not apply there)

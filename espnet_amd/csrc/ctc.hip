@@ -69,13 +69,7 @@ __global__ __launch_bounds__(256) void log_softmax_rows_kernel(float* __restrict
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= M) return;
   float* xr = x + (size_t)row * V;
-  float mx = -INFINITY;
-  for (int c = lane; c < V; c += 64) mx = fmaxf(mx, xr[c]);
-  mx = wave_max(mx);
-  float s = 0.f;
-  for (int c = lane; c < V; c += 64) s += expf(xr[c] - mx);
-  s = wave_sum(s);
-  const float lse = mx + logf(s);
+  const float lse = wave_row_lse(xr, V, lane);
   for (int c = lane; c < V; c += 64) xr[c] = xr[c] - lse;
 }
 

@@ -85,6 +85,17 @@ __device__ __forceinline__ float wave_max(float v) {
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
   return v;
 }
+// log-sum-exp of a row of V floats, taken by one wave whose lanes stride the row: the one definition behind
+// em_log_softmax_rows_f32 and every kernel that must reproduce its bits (the transducer walks' expand, the masked LM step)
+__device__ __forceinline__ float wave_row_lse(const float* row, int V, int lane) {
+  float mx = -INFINITY;
+  for (int c = lane; c < V; c += 64) mx = fmaxf(mx, row[c]);
+  mx = wave_max(mx);
+  float s = 0.f;
+  for (int c = lane; c < V; c += 64) s += expf(row[c] - mx);
+  s = wave_sum(s);
+  return mx + logf(s);
+}
 
 // ---- cross-lane moves on the DPP path (VALU rate, ~8 cycles) instead of ds_bpermute (an LDS-pipe round trip of
 // 100+ cycles): a chain of __shfl_xor steps is a chain of dependent LDS round trips, and the search kernels' arg-max

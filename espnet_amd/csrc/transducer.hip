@@ -88,10 +88,40 @@ int joint_logp_t(const EmTransducerWeights* w, const float* enc_proj, const int3
   for (int r0 = 0; r0 < n; r0 += MAXROWS) {
     const int m = n - r0 < MAXROWS ? n - r0 : MAXROWS;
     hipLaunchKernelGGL((joint_kernel<T, true>), dim3(em_cdiv(V, 16)), dim3(256), 0, s, (const T*)z_ws + (size_t)r0 * jp,
-                       (const T*)w->lin_out, w->out_b, m, V, jp, logp + (size_t)r0 * V, (float4*)nullptr, (const int32_t*)nullptr);
+                       (const T*)w->lin_out, w->out_b, m, V, jp, logp + (size_t)r0 * V, (float4*)nullptr, (const int32_t*)nullptr,
+                       (const int32_t*)nullptr);
   }
   EM_CHECK_LAUNCH();
   return em_log_softmax_rows_f32(logp, n, V, s);
+}
+
+// em_log_softmax_rows_f32 (csrc/ctc.hip: one wave per row, wave_row_lse) for the rows with
+// mask[r] != 0 only: the masked call of em_transducer_lm_step leaves the other rows as they are
+__global__ __launch_bounds__(256) void masked_log_softmax_rows_kernel(float* __restrict__ x, const int32_t* __restrict__ mask,
+                                                                      int M, int V) {
+  const int lane = threadIdx.x & 63;
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= M || mask[row] == 0) return;
+  float* xr = x + (size_t)row * V;
+  const float lse = wave_row_lse(xr, V, lane);
+  for (int c = lane; c < V; c += 64) xr[c] = xr[c] - lse;
+}
+
+template <typename T>
+int lm_step_t(const EmTransducerLmWeights* w, const int32_t* tok, const int32_t* mask, int n, const void* hs_in,
+              const float* cs_in, void* hs_out, float* cs_out, float* logp, hipStream_t s) {
+  const size_t ls = (size_t)n * w->d;
+  for (int r0 = 0; r0 < n; r0 += MAXROWS) {
+    const int m = n - r0 < MAXROWS ? n - r0 : MAXROWS;
+    const size_t o = (size_t)r0 * w->d;
+    const int32_t* mk = mask ? mask + r0 : nullptr;
+    EM_TRY(lm_rows<T>(w, tok + r0, mk, mk, m, ls, (const T*)hs_in + o, cs_in + o, (T*)hs_out + o, cs_out + o,
+                      logp + (size_t)r0 * w->vocab, s));
+  }
+  if (!mask) return em_log_softmax_rows_f32(logp, n, w->vocab, s);
+  hipLaunchKernelGGL(masked_log_softmax_rows_kernel, dim3(em_cdiv(n, 4)), dim3(256), 0, s, logp, mask, n, w->vocab);
+  EM_CHECK_LAUNCH();
+  return EM_OK;
 }
 
 // workspace of the walk: the carve-up below and em_transducer_greedy_workspace_bytes must agree
@@ -134,7 +164,7 @@ int greedy_t(int dtype, const EmTransducerWeights* w, const float* enc_proj, con
   int cur = 1;
   for (int t = 0; t < T_frames; ++t) {
     hipLaunchKernelGGL((joint_kernel<T, false>), dim3(ntiles), dim3(256), 0, s, (const T*)z, (const T*)w->lin_out, w->out_b,
-                       B, V, w->jp, (float*)nullptr, part, (const int32_t*)nullptr);
+                       B, V, w->jp, (float*)nullptr, part, (const int32_t*)nullptr, (const int32_t*)nullptr);
     hipLaunchKernelGGL(decide_kernel, dim3(B), dim3(64), 0, s, (const float4*)part, ntiles, t, T_frames, w->blank, olens,
                        tokens, ylens, score, tok_cur, emit, frame_tok, frame_top, frame_margin);
     if (t + 1 == T_frames) break;
@@ -157,6 +187,17 @@ extern "C" int em_transducer_dec_step(int dtype, const EmTransducerWeights* w, c
   hipStream_t s = (hipStream_t)stream;
   if (dtype == EM_BF16) return dec_step_t<bf16>(w, tok, mask, n, hs_in, cs_in, hs_out, cs_out, dec_out, dec_proj, s);
   return dec_step_t<float>(w, tok, mask, n, hs_in, cs_in, hs_out, cs_out, dec_out, dec_proj, s);
+}
+
+extern "C" int em_transducer_lm_step(int dtype, const EmTransducerLmWeights* w, const int32_t* tok, const int32_t* mask,
+                                     int32_t n, const void* hs_in, const float* cs_in, void* hs_out, float* cs_out,
+                                     float* logp, void* stream) {
+  EM_TRY(check_lm_weights(dtype, w));
+  if (n <= 0 || !tok || !hs_in || !cs_in || !hs_out || !cs_out || !logp || hs_in == hs_out || cs_in == cs_out)
+    return EM_ERR_BAD_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  if (dtype == EM_BF16) return lm_step_t<bf16>(w, tok, mask, n, hs_in, cs_in, hs_out, cs_out, logp, s);
+  return lm_step_t<float>(w, tok, mask, n, hs_in, cs_in, hs_out, cs_out, logp, s);
 }
 
 extern "C" int em_transducer_joint_logp(int dtype, const EmTransducerWeights* w, const float* enc_proj, const int32_t* enc_idx,

@@ -24,6 +24,14 @@
 //           carried nodes' is free again (a used flag per slot; nothing is copied).
 // A frame ends when the kept entries strictly above the best open score number at least `beam`; exactly those are
 // carried, in kept order (equal scores stay in insertion order, as the reference's stable sort leaves them).
+//
+// With a language model (em_transducer_beam_search_lm, shallow fusion) a step is
+//     select -> cell.. -> lin_dec -> tanh -> joint logits -> LM cell (one launch per layer) -> LM head -> expand
+// and every slot also holds the LM's h / c per layer: the state after the LM has read sos and the node's labels.  A
+// child reads its parent's slot as the LM's pre-state; for a carried entry select lays the node's OWN slot into the LM's
+// input state, the masked cells copy it through and the head recomputes the node's LM row from its stored top h (V-wide
+// rows are not kept per slot).  expand adds lm_weight * lm_logp[k] to the beam_k children in double, product and sum
+// rounded separately, as the host route's Python floats are.
 #include <math.h>
 
 #include "em_common.h"
@@ -65,7 +73,21 @@ struct BeamP {
   double* out_scores;
   float* step_logp;
   int32_t* step_trace;
+  // the fused language model (lmL == 0: none)
+  int lmL, lmd;
+  double lm_weight;
+  void *lm_slot_hs, *lm_hs_in, *lm_hs_out;
+  float *lm_slot_cs, *lm_cs_in, *lm_cs_out;
+  int32_t* lm_tok;
+  float *lm_logits, *step_lm_logp;
 };
+
+// (base + w * x) with the product and the sum rounded one after the other: what the host route's Python floats give
+__device__ __forceinline__ double add_lm_term(double base, double w, double x) {
+#pragma clang fp contract(off)
+  const double t = w * x;
+  return base + t;
+}
 
 // the better of two (score, index) pairs: the higher score, the LOWER index of equal scores; index < 0: none
 struct Best {
@@ -111,6 +133,7 @@ __global__ __launch_bounds__(64) void beam_init_kernel(BeamP p) {
     p.open_node[(size_t)b * p.ocap] = -1;
     p.open_tok[(size_t)b * p.ocap] = p.blank;
     p.tok[b] = p.blank;
+    if (p.lmL) p.lm_tok[b] = p.V - 1;
     p.mask[b] = 0;
     p.enc_idx[b] = b * p.T;
     p.dec_idx[b] = p.B * NSLOT + b;
@@ -128,7 +151,7 @@ __global__ __launch_bounds__(64) void beam_init_kernel(BeamP p) {
 template <typename T>
 __global__ __launch_bounds__(WG) void beam_select_kernel(BeamP p) {
   __shared__ Best sh[4];
-  __shared__ int s_pre, s_skip;
+  __shared__ int s_pre, s_skip, s_lm;
   const int b = blockIdx.x, tid = threadIdx.x;
   if (*p.g_live == 0) return;
   int32_t* ctl = p.ctl + b * C_N;
@@ -144,6 +167,7 @@ __global__ __launch_bounds__(WG) void beam_select_kernel(BeamP p) {
   if (tid == 0) {
     s_pre = -1;
     s_skip = 1;
+    s_lm = -2;  // the slot the LM's input state comes from; -1: the zero state, -2: none (the utterance ended here)
     if (v.i < 0) {  // (an open set is never empty: every expansion appends beam_k >= 1 children)
       beam_end(p, b, ctl, ST_CAP_EXPANSIONS);
     } else {
@@ -152,8 +176,11 @@ __global__ __launch_bounds__(WG) void beam_select_kernel(BeamP p) {
       if (tk == TOK_CARRIED) {
         p.mask[b] = 0;
         p.dec_idx[b] = b * NSLOT + p.node[(size_t)b * p.ncap + node].w;
+        s_lm = p.node[(size_t)b * p.ncap + node].w;  // its own state: the masked cells copy it, the head reads its top h
       } else {
         if (node >= 0) s_pre = p.node[(size_t)b * p.ncap + node].w;
+        s_lm = s_pre;
+        if (p.lmL) p.lm_tok[b] = node < 0 ? p.V - 1 : tk;  // the first hypothesis feeds sos = V - 1
         p.tok[b] = tk;
         p.mask[b] = 1;
         p.dec_idx[b] = p.B * NSLOT + b;
@@ -166,6 +193,17 @@ __global__ __launch_bounds__(WG) void beam_select_kernel(BeamP p) {
     }
   }
   __syncthreads();
+  if (p.lmL && s_lm != -2) {
+    const int src = s_lm, d = p.lmd, L = p.lmL;
+    const T* shs = (const T*)p.lm_slot_hs + ((size_t)b * NSLOT + max(src, 0)) * L * d;
+    const float* scs = p.lm_slot_cs + ((size_t)b * NSLOT + max(src, 0)) * L * d;
+    for (int i = tid; i < L * d; i += WG) {
+      const int l = i / d, c = i - l * d;
+      const size_t o = ((size_t)l * p.B + b) * d + c;
+      ((T*)p.lm_hs_in)[o] = src < 0 ? from_f32<T>(0.f) : shs[i];
+      p.lm_cs_in[o] = src < 0 ? 0.f : scs[i];
+    }
+  }
   if (s_skip) return;
   const int pre = s_pre, d = p.d, L = p.L;
   const T* shs = (const T*)p.slot_hs + ((size_t)b * NSLOT + max(pre, 0)) * L * d;
@@ -182,7 +220,7 @@ __global__ __launch_bounds__(WG) void beam_select_kernel(BeamP p) {
 template <typename T>
 __global__ __launch_bounds__(WG) void beam_expand_kernel(BeamP p) {
   __shared__ Best sh[4];
-  __shared__ float s_lse;
+  __shared__ float s_lse, s_lm_lse;
   __shared__ int s_w[4], s_e, s_slot, s_ended;
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   if (*p.g_live == 0) return;
@@ -193,26 +231,23 @@ __global__ __launch_bounds__(WG) void beam_expand_kernel(BeamP p) {
   const bool marked = cur_tok == TOK_CARRIED;
   const double score = p.cur_score[b];
   float* row = p.logits + (size_t)b * V;
+  const float* lm_row = p.lmL ? p.lm_logits + (size_t)b * V : nullptr;
   int4* nodes = p.node + (size_t)b * p.ncap;
   int32_t* su = p.slot_used + b * NSLOT;
-  // the log-softmax exactly as em_log_softmax_rows_f32 takes it (csrc/ctc.hip): one wave, its lanes stride the row
-  if (wave == 0) {
-    float mx = -INFINITY;
-    for (int c = lane; c < V; c += 64) mx = fmaxf(mx, row[c]);
-    mx = wave_max(mx);
-    float s = 0.f;
-    for (int c = lane; c < V; c += 64) s += expf(row[c] - mx);
-    s = wave_sum(s);
-    if (lane == 0) s_lse = mx + logf(s);
+  // the log-softmax exactly as em_log_softmax_rows_f32 takes it (wave_row_lse): one wave, its lanes stride the row
+  if (wave == 0 || (wave == 1 && p.lmL)) {  // (wave 1: the LM row's, the same way, beside it)
+    const float v = wave_row_lse(wave == 0 ? row : lm_row, V, lane);
+    if (lane == 0) (wave == 0 ? s_lse : s_lm_lse) = v;
   }
   const unsigned long long fm = __ballot(su[tid] == 0);
   if (lane == 0) s_w[wave] = fm ? wave * 64 + __ffsll((long long)fm) - 1 : NSLOT;
   __syncthreads();
-  const float lse = s_lse;
+  const float lse = s_lse, lm_lse = p.lmL ? s_lm_lse : 0.f;
   for (int c = tid; c < V; c += WG) {
     const float x = row[c] - lse;
     row[c] = x;
     if (p.step_logp) p.step_logp[(size_t)b * V + c] = x;
+    if (p.step_lm_logp) p.step_lm_logp[(size_t)b * V + c] = lm_row[c] - lm_lse;
   }
   if (tid == 0) {
     s_ended = 0;
@@ -252,6 +287,17 @@ __global__ __launch_bounds__(WG) void beam_expand_kernel(BeamP p) {
     const float* src = p.dec_proj_all + ((size_t)p.B * NSLOT + b) * p.jp;
     float* dst = p.dec_proj_all + ((size_t)b * NSLOT + slot) * p.jp;
     for (int j = tid; j < p.jp; j += WG) dst[j] = src[j];
+    if (p.lmL) {  // and the LM cells' results
+      const int dl = p.lmd, Ll = p.lmL;
+      T* lhs = (T*)p.lm_slot_hs + ((size_t)b * NSLOT + slot) * Ll * dl;
+      float* lcs = p.lm_slot_cs + ((size_t)b * NSLOT + slot) * Ll * dl;
+      for (int i = tid; i < Ll * dl; i += WG) {
+        const int l = i / dl, c = i - l * dl;
+        const size_t o = ((size_t)l * p.B + b) * dl + c;
+        lhs[i] = ((const T*)p.lm_hs_out)[o];
+        lcs[i] = p.lm_cs_out[o];
+      }
+    }
   }
   double* os = p.open_score + (size_t)b * p.ocap;
   int32_t* on = p.open_node + (size_t)b * p.ocap;
@@ -280,7 +326,8 @@ __global__ __launch_bounds__(WG) void beam_expand_kernel(BeamP p) {
     v = block_best(v, sh);
     if (v.i < 0) break;  // (fewer than beam_k comparable labels: a row of NaN)
     if (tid == 0) {
-      os[n_open0 + j] = score + v.s;
+      const double child = score + v.s;
+      os[n_open0 + j] = p.lmL ? add_lm_term(child, p.lm_weight, (double)(lm_row[v.i] - lm_lse)) : child;
       on[n_open0 + j] = e;
       ot[n_open0 + j] = v.i;
     }
@@ -356,14 +403,15 @@ __global__ __launch_bounds__(WG) void beam_expand_kernel(BeamP p) {
 
 struct BeamWs {
   size_t g_live, ctl, cur_score, open_score, open_node, open_tok, kept_score, kept_node, node, slot_used, slot_hs, slot_cs,
-      dec_proj_all, hs_in, hs_out, cs_in, cs_out, tok, mask, enc_idx, dec_idx, z, logits, total;
+      dec_proj_all, hs_in, hs_out, cs_in, cs_out, tok, mask, enc_idx, dec_idx, z, logits, lm_slot_hs, lm_slot_cs, lm_hs_in,
+      lm_hs_out, lm_cs_in, lm_cs_out, lm_tok, lm_logits, total;
 };
 int beam_ocap(const EmTransducerWeights* w, int beam) {
   const int bm = beam < w->vocab ? beam : w->vocab;
   const int bk = bm < w->vocab - 1 ? bm : w->vocab - 1;
   return EXP_CAP + EXP_CAP * bk;
 }
-BeamWs beam_layout(int dtype, const EmTransducerWeights* w, int B, int T, int beam) {
+BeamWs beam_layout(int dtype, const EmTransducerWeights* w, const EmTransducerLmWeights* lm, int B, int T, int beam) {
   const size_t es = dtype == EM_BF16 ? 2 : 4;
   const size_t ocap = beam_ocap(w, beam), st = (size_t)w->num_layers * w->d;
   BeamWs o;
@@ -391,19 +439,32 @@ BeamWs beam_layout(int dtype, const EmTransducerWeights* w, int B, int T, int be
   o.dec_idx = b.take((size_t)B * 4);
   o.z = b.take((size_t)B * w->jp * es);
   o.logits = b.take((size_t)B * w->vocab * 4);
+  o.lm_slot_hs = o.lm_slot_cs = o.lm_hs_in = o.lm_hs_out = o.lm_cs_in = o.lm_cs_out = o.lm_tok = o.lm_logits = 0;
+  if (lm) {
+    const size_t lst = (size_t)lm->num_layers * lm->d;
+    o.lm_slot_hs = b.take((size_t)B * NSLOT * lst * es);
+    o.lm_slot_cs = b.take((size_t)B * NSLOT * lst * 4);
+    o.lm_hs_in = b.take((size_t)B * lst * es);
+    o.lm_hs_out = b.take((size_t)B * lst * es);
+    o.lm_cs_in = b.take((size_t)B * lst * 4);
+    o.lm_cs_out = b.take((size_t)B * lst * 4);
+    o.lm_tok = b.take((size_t)B * 4);
+    o.lm_logits = b.take((size_t)B * w->vocab * 4);
+  }
   o.total = b.o;
   return o;
 }
 
-bool beam_shape_ok(int dtype, const EmTransducerWeights* w, int B, int T, int beam) {
+bool beam_shape_ok(int dtype, const EmTransducerWeights* w, const EmTransducerLmWeights* lm, int B, int T, int beam) {
   if (check_weights(dtype, w) != EM_OK || B <= 0 || T <= 0 || beam < 1) return false;
+  if (lm && (check_lm_weights(dtype, lm) != EM_OK || lm->vocab != w->vocab)) return false;
   return B <= MAXROWS && beam <= MAX_BEAM && (long long)T * EXP_CAP < (1ll << 30) / B;
 }
 
 template <typename T>
-int beam_t(int dtype, const EmTransducerWeights* w, BeamP p, const float* enc_proj, int T_frames, int first, int steps,
-           unsigned char* ws, hipStream_t s) {
-  const BeamWs o = beam_layout(dtype, w, p.B, T_frames, p.beam);
+int beam_t(int dtype, const EmTransducerWeights* w, const EmTransducerLmWeights* lm, BeamP p, const float* enc_proj,
+           int T_frames, int first, int steps, unsigned char* ws, hipStream_t s) {
+  const BeamWs o = beam_layout(dtype, w, lm, p.B, T_frames, p.beam);
   p.g_live = (int32_t*)(ws + o.g_live), p.ctl = (int32_t*)(ws + o.ctl), p.cur_score = (double*)(ws + o.cur_score);
   p.open_score = (double*)(ws + o.open_score), p.open_node = (int32_t*)(ws + o.open_node);
   p.open_tok = (int32_t*)(ws + o.open_tok), p.kept_score = (double*)(ws + o.kept_score);
@@ -412,6 +473,11 @@ int beam_t(int dtype, const EmTransducerWeights* w, BeamP p, const float* enc_pr
   p.hs_in = ws + o.hs_in, p.hs_out = ws + o.hs_out, p.cs_in = (float*)(ws + o.cs_in), p.cs_out = (float*)(ws + o.cs_out);
   p.tok = (int32_t*)(ws + o.tok), p.mask = (int32_t*)(ws + o.mask), p.enc_idx = (int32_t*)(ws + o.enc_idx);
   p.dec_idx = (int32_t*)(ws + o.dec_idx), p.logits = (float*)(ws + o.logits);
+  if (lm) {
+    p.lm_slot_hs = ws + o.lm_slot_hs, p.lm_slot_cs = (float*)(ws + o.lm_slot_cs), p.lm_hs_in = ws + o.lm_hs_in;
+    p.lm_hs_out = ws + o.lm_hs_out, p.lm_cs_in = (float*)(ws + o.lm_cs_in), p.lm_cs_out = (float*)(ws + o.lm_cs_out);
+    p.lm_tok = (int32_t*)(ws + o.lm_tok), p.lm_logits = (float*)(ws + o.lm_logits);
+  }
   T* z = (T*)(ws + o.z);
   const int B = p.B, V = p.V;
   if (first) hipLaunchKernelGGL(beam_init_kernel, dim3(1), dim3(64), 0, s, p);
@@ -422,7 +488,10 @@ int beam_t(int dtype, const EmTransducerWeights* w, BeamP p, const float* enc_pr
     hipLaunchKernelGGL(pair_tanh_kernel<T>, dim3(B), dim3(128), 0, s, enc_proj, (const int32_t*)p.enc_idx,
                        (const float*)p.dec_proj_all, (const int32_t*)p.dec_idx, B, w->jp, z, (const int32_t*)p.g_live);
     hipLaunchKernelGGL((joint_kernel<T, true>), dim3(em_cdiv(V, 16)), dim3(256), 0, s, (const T*)z, (const T*)w->lin_out,
-                       w->out_b, B, V, w->jp, p.logits, (float4*)nullptr, (const int32_t*)p.g_live);
+                       w->out_b, B, V, w->jp, p.logits, (float4*)nullptr, (const int32_t*)p.g_live, (const int32_t*)nullptr);
+    if (lm)  // (every row's head runs: a carried entry's LM row is recomputed from the state its masked cells copied)
+      EM_TRY(lm_rows<T>(lm, p.lm_tok, p.mask, nullptr, B, (size_t)B * lm->d, (const T*)p.lm_hs_in, p.lm_cs_in,
+                        (T*)p.lm_hs_out, p.lm_cs_out, p.lm_logits, s, p.g_live));
     hipLaunchKernelGGL(beam_expand_kernel<T>, dim3(B), dim3(WG), 0, s, p);
   }
   EM_CHECK_LAUNCH();
@@ -440,22 +509,31 @@ extern "C" void em_transducer_beam_limits(int32_t* beam_max, int32_t* open_max, 
   if (labels_max) *labels_max = MAX_LABELS;
 }
 
-extern "C" size_t em_transducer_beam_workspace_bytes(int dtype, const EmTransducerWeights* w, int32_t B, int32_t T,
-                                                     int32_t beam) {
-  if (!beam_shape_ok(dtype, w, B, T, beam)) return 0;
-  return beam_layout(dtype, w, B, T, beam).total;
+extern "C" size_t em_transducer_beam_workspace_bytes_lm(int dtype, const EmTransducerWeights* w,
+                                                        const EmTransducerLmWeights* lm, int32_t B, int32_t T, int32_t beam) {
+  if (!beam_shape_ok(dtype, w, lm, B, T, beam)) return 0;
+  return beam_layout(dtype, w, lm, B, T, beam).total;
 }
 
-extern "C" int em_transducer_beam_search(int dtype, const EmTransducerWeights* w, const float* enc_proj, const int32_t* olens,
-                                         int32_t B, int32_t T, int32_t beam, int32_t max_expansions, int32_t Lmax,
-                                         int32_t nbest_cap, int32_t first, int32_t steps, int32_t* status,
-                                         int32_t* out_tokens, int32_t* out_lens, double* out_scores, int32_t* out_count,
-                                         float* step_logp, int32_t* step_trace, void* ws, size_t ws_bytes, void* stream) {
+extern "C" size_t em_transducer_beam_workspace_bytes(int dtype, const EmTransducerWeights* w, int32_t B, int32_t T,
+                                                     int32_t beam) {
+  return em_transducer_beam_workspace_bytes_lm(dtype, w, nullptr, B, T, beam);
+}
+
+extern "C" int em_transducer_beam_search_lm(int dtype, const EmTransducerWeights* w, const EmTransducerLmWeights* lm,
+                                            double lm_weight, const float* enc_proj, const int32_t* olens, int32_t B,
+                                            int32_t T, int32_t beam, int32_t max_expansions, int32_t Lmax, int32_t nbest_cap,
+                                            int32_t first, int32_t steps, int32_t* status, int32_t* out_tokens,
+                                            int32_t* out_lens, double* out_scores, int32_t* out_count, float* step_logp,
+                                            int32_t* step_trace, float* step_lm_logp, void* ws, size_t ws_bytes,
+                                            void* stream) {
   EM_TRY(check_weights(dtype, w));
+  if (lm) EM_TRY(check_lm_weights(dtype, lm));
+  if ((lm && lm->vocab != w->vocab) || (!lm && step_lm_logp)) return EM_ERR_BAD_ARG;
   if (B <= 0 || T <= 0 || beam < 1 || max_expansions < 1 || Lmax < 1 || nbest_cap < 1 || steps < 0) return EM_ERR_BAD_ARG;
   if (!enc_proj || !olens || !status || !out_tokens || !out_lens || !out_scores || !out_count) return EM_ERR_BAD_ARG;
-  if (!beam_shape_ok(dtype, w, B, T, beam) || Lmax > MAX_LABELS || nbest_cap > EXP_CAP) return EM_ERR_UNSUPPORTED;
-  if (!ws || ws_bytes < beam_layout(dtype, w, B, T, beam).total) return EM_ERR_UNSUPPORTED;
+  if (!beam_shape_ok(dtype, w, lm, B, T, beam) || Lmax > MAX_LABELS || nbest_cap > EXP_CAP) return EM_ERR_UNSUPPORTED;
+  if (!ws || ws_bytes < beam_layout(dtype, w, lm, B, T, beam).total) return EM_ERR_UNSUPPORTED;
   BeamP p{};
   p.B = B, p.T = T, p.V = w->vocab, p.L = w->num_layers, p.d = w->d, p.jp = w->jp;
   p.beam = beam < w->vocab ? beam : w->vocab;
@@ -464,8 +542,19 @@ extern "C" int em_transducer_beam_search(int dtype, const EmTransducerWeights* w
   p.blank = w->blank, p.olens = olens;
   p.status = status, p.out_tokens = out_tokens, p.out_lens = out_lens, p.out_scores = out_scores, p.out_count = out_count;
   p.step_logp = step_logp, p.step_trace = step_trace;
+  if (lm) p.lmL = lm->num_layers, p.lmd = lm->d, p.lm_weight = lm_weight, p.step_lm_logp = step_lm_logp;
   hipStream_t s = (hipStream_t)stream;
   unsigned char* q = (unsigned char*)ws;
-  if (dtype == EM_BF16) return beam_t<bf16>(dtype, w, p, enc_proj, T, first, steps, q, s);
-  return beam_t<float>(dtype, w, p, enc_proj, T, first, steps, q, s);
+  if (dtype == EM_BF16) return beam_t<bf16>(dtype, w, lm, p, enc_proj, T, first, steps, q, s);
+  return beam_t<float>(dtype, w, lm, p, enc_proj, T, first, steps, q, s);
+}
+
+extern "C" int em_transducer_beam_search(int dtype, const EmTransducerWeights* w, const float* enc_proj, const int32_t* olens,
+                                         int32_t B, int32_t T, int32_t beam, int32_t max_expansions, int32_t Lmax,
+                                         int32_t nbest_cap, int32_t first, int32_t steps, int32_t* status,
+                                         int32_t* out_tokens, int32_t* out_lens, double* out_scores, int32_t* out_count,
+                                         float* step_logp, int32_t* step_trace, void* ws, size_t ws_bytes, void* stream) {
+  return em_transducer_beam_search_lm(dtype, w, nullptr, 0.0, enc_proj, olens, B, T, beam, max_expansions, Lmax, nbest_cap,
+                                      first, steps, status, out_tokens, out_lens, out_scores, out_count, step_logp,
+                                      step_trace, nullptr, ws, ws_bytes, stream);
 }

@@ -79,11 +79,15 @@ __device__ __forceinline__ Top top_shfl_xor(Top v, int o) {
 // tanh(enc_proj + dec_proj).  One workgroup per 16 vocabulary columns; the waves split jp.
 //   LOGITS: the f32 logits [n][V] are stored (em_transducer_joint_logp; the log-softmax follows in its own launch)
 //   else  : one Top per (row, tile) goes to part [n][ntiles] (the greedy walk: the [B][V] logits never exist)
+// rmask (NULL: none; LOGITS only): the logits of a row with rmask[r] == 0 are not stored.
+// The same kernel is the language model's head in em_transducer_lm_step and the LM-fused beam search (z = the top
+// layer's h, jp = the LM's padded hidden size).
 template <typename T, bool LOGITS>
 __global__ __launch_bounds__(256) void joint_kernel(const T* __restrict__ z, const T* __restrict__ w_out,
                                                     const float* __restrict__ out_b, int n, int V, int jp,
                                                     float* __restrict__ logits, float4* __restrict__ part,
-                                                    const int32_t* __restrict__ live) {
+                                                    const int32_t* __restrict__ live,
+                                                    const int32_t* __restrict__ rmask) {
   using MM = Mma<T>;
   __shared__ f32x4 red[4][MAXRT][64];
   if (live && *live == 0) return;
@@ -115,7 +119,7 @@ __global__ __launch_bounds__(256) void joint_kernel(const T* __restrict__ z, con
     const int r = wave * 16 + lg * 4 + q;
     const float x = v[q] + bias;
     if constexpr (LOGITS) {
-      if (r < n && col < V) logits[(size_t)r * V + col] = x;
+      if (r < n && col < V && (!rmask || rmask[r] != 0)) logits[(size_t)r * V + col] = x;
     } else {
       Top t{col < V ? x : -INFINITY, col, -INFINITY, col < V ? 1.f : 0.f};
 #pragma unroll
@@ -261,28 +265,65 @@ inline int check_weights(int dtype, const EmTransducerWeights* w) {
   return EM_OK;
 }
 
-// the prediction-network layers and lin_dec for n <= 64 rows (states: per-layer pointers at stride `lstride` elements)
+// the recurrent layers of a prediction network or a language model for n <= 64 rows (states: per-layer pointers at stride
+// `lstride` elements): layer 0 reads its input rows, `kin0` wide, from the embedding table, the others the h below, d wide
+template <typename T>
+void rnn_layers(int kind, const EmRnnLayer* rnn, int num_layers, const void* embed, int vocab, int kin0, int nh, int d,
+                const int32_t* tok, const int32_t* mask, int n, size_t lstride, const T* hs_in, const float* cs_in,
+                T* hs_out, float* cs_out, float* dec_out, hipStream_t s) {
+  for (int l = 0; l < num_layers; ++l) {
+    const EmRnnLayer& q = rnn[l];
+    const T* x = l == 0 ? (const T*)embed : hs_out + (size_t)(l - 1) * lstride;
+    const int kin = l == 0 ? kin0 : d;
+    float* dout = l == num_layers - 1 ? dec_out : nullptr;
+    const dim3 grid(d / 16), block(256);
+    if (kind == EM_LM_LSTM)
+      hipLaunchKernelGGL((cell_kernel<T, EM_LM_LSTM>), grid, block, 0, s, x, l == 0 ? tok : nullptr, vocab, kin,
+                         (const T*)q.w_ih, (const T*)q.w_hh, q.bias, mask, n, nh, d, hs_in + l * lstride,
+                         cs_in + l * lstride, hs_out + l * lstride, cs_out + l * lstride, dout);
+    else
+      hipLaunchKernelGGL((cell_kernel<T, EM_LM_GRU>), grid, block, 0, s, x, l == 0 ? tok : nullptr, vocab, kin,
+                         (const T*)q.w_ih, (const T*)q.w_hh, q.bias, mask, n, nh, d, hs_in + l * lstride,
+                         cs_in + l * lstride, hs_out + l * lstride, cs_out + l * lstride, dout);
+  }
+}
+
+// the prediction-network layers and lin_dec for n <= 64 rows
 template <typename T>
 int dec_rows(const EmTransducerWeights* w, const int32_t* tok, const int32_t* mask, int n, size_t lstride, const T* hs_in,
              const float* cs_in, T* hs_out, float* cs_out, float* dec_out, float* dec_proj, const float* enc_proj,
              int T_frames, int t_next, T* z, hipStream_t s, const int32_t* live = nullptr) {
-  const int d = w->d, nh = w->nhid;
-  for (int l = 0; l < w->num_layers; ++l) {
-    const EmRnnLayer& q = w->rnn[l];
-    const T* x = l == 0 ? (const T*)w->embed : hs_out + (size_t)(l - 1) * lstride;
-    float* dout = l == w->num_layers - 1 ? dec_out : nullptr;
-    const dim3 grid(d / 16), block(256);
-    if (w->kind == EM_LM_LSTM)
-      hipLaunchKernelGGL((cell_kernel<T, EM_LM_LSTM>), grid, block, 0, s, x, l == 0 ? tok : nullptr, w->vocab, d,
-                         (const T*)q.w_ih, (const T*)q.w_hh, q.bias, mask, n, nh, d, hs_in + l * lstride,
-                         cs_in + l * lstride, hs_out + l * lstride, cs_out + l * lstride, dout);
-    else
-      hipLaunchKernelGGL((cell_kernel<T, EM_LM_GRU>), grid, block, 0, s, x, l == 0 ? tok : nullptr, w->vocab, d,
-                         (const T*)q.w_ih, (const T*)q.w_hh, q.bias, mask, n, nh, d, hs_in + l * lstride,
-                         cs_in + l * lstride, hs_out + l * lstride, cs_out + l * lstride, dout);
-  }
+  const int d = w->d;
+  rnn_layers<T>(w->kind, w->rnn, w->num_layers, w->embed, w->vocab, d, w->nhid, d, tok, mask, n, lstride, hs_in, cs_in,
+                hs_out, cs_out, dec_out, s);
   hipLaunchKernelGGL(proj_kernel<T>, dim3(w->jp / 16), dim3(256), 0, s, hs_out + (size_t)(w->num_layers - 1) * lstride,
                      (const T*)w->lin_dec, mask, n, d, w->joint, w->jp, dec_proj, enc_proj, T_frames, t_next, z, live);
+  EM_CHECK_LAUNCH();
+  return EM_OK;
+}
+
+// ---- the language model fused into the beam search (EmTransducerLmWeights: a SequentialRNNLM, lstm or gru)
+inline int check_lm_weights(int dtype, const EmTransducerLmWeights* w) {
+  if (!w || (dtype != EM_F32 && dtype != EM_BF16)) return EM_ERR_BAD_ARG;
+  if (!w->embed || !w->rnn || !w->out_w || !w->out_b) return EM_ERR_BAD_ARG;
+  if (w->vocab < 2 || w->nhid < 1 || w->num_layers < 1 || w->embed_unit < 1) return EM_ERR_BAD_ARG;
+  if (w->kind != EM_LM_LSTM && w->kind != EM_LM_GRU) return EM_ERR_UNSUPPORTED;
+  if (w->d % 64 != 0 || w->embed_unit % 64 != 0 || w->d < w->nhid) return EM_ERR_UNSUPPORTED;
+  return EM_OK;
+}
+
+// the LM's layers and its head (logits [n][vocab] f32, no log-softmax yet) for n <= 64 rows; states as dec_rows takes
+// them.  Rows with mask[r] == 0 copy their state; head_mask (NULL: every row) keeps their logits rows unwritten.
+template <typename T>
+int lm_rows(const EmTransducerLmWeights* w, const int32_t* tok, const int32_t* mask, const int32_t* head_mask, int n,
+            size_t lstride, const T* hs_in, const float* cs_in, T* hs_out, float* cs_out, float* logits, hipStream_t s,
+            const int32_t* live = nullptr) {
+  const int d = w->d;
+  rnn_layers<T>(w->kind, w->rnn, w->num_layers, w->embed, w->vocab, w->embed_unit, w->nhid, d, tok, mask, n, lstride, hs_in,
+                cs_in, hs_out, cs_out, (float*)nullptr, s);
+  hipLaunchKernelGGL((joint_kernel<T, true>), dim3(em_cdiv(w->vocab, 16)), dim3(256), 0, s,
+                     (const T*)(hs_out + (size_t)(w->num_layers - 1) * lstride), (const T*)w->out_w, w->out_b, n, w->vocab,
+                     d, logits, (float4*)nullptr, live, head_mask);
   EM_CHECK_LAUNCH();
   return EM_OK;
 }

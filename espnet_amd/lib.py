@@ -248,6 +248,12 @@ class EmTransducerWeights(C.Structure):
                [(n, C.c_void_p) for n in ("lin_dec", "lin_out", "out_b")]
 
 
+class EmTransducerLmWeights(C.Structure):
+    """include/espnet_amd.h EmTransducerLmWeights: the SequentialRNNLM fused into the transducer beam search."""
+    _fields_ = [(n, C.c_int32) for n in ("kind", "vocab", "nhid", "d", "embed_unit", "num_layers")] + \
+               [("embed", C.c_void_p), ("rnn", C.POINTER(EmRnnLayer)), ("out_w", C.c_void_p), ("out_b", C.c_void_p)]
+
+
 SEARCH_BUFFERS = ["xlens", "maxlens", "minlens", "ctc_lpT", "tok", "parent", "anc_a", "anc_b",
                   "alive", "run_score", "run_sdec", "run_sctc", "run_slen", "s_prev", "r_a", "r_b",
                   "cand_tok", "cand_full", "cand_psi", "cand_total", "sel_idx", "sel_total",
@@ -433,6 +439,13 @@ _SIGNATURES = {
     "em_transducer_beam_search": (C.c_int, [C.c_int, C.POINTER(EmTransducerWeights), _vp, _vp, _i32, _i32, _i32, _i32, _i32,
                                             _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "em_transducer_beam_workspace_bytes": (_sz, [C.c_int, C.POINTER(EmTransducerWeights), _i32, _i32, _i32]),
+    "em_transducer_lm_step": (C.c_int, [C.c_int, C.POINTER(EmTransducerLmWeights), _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp,
+                                        _vp]),
+    "em_transducer_beam_search_lm": (C.c_int, [C.c_int, C.POINTER(EmTransducerWeights), C.POINTER(EmTransducerLmWeights),
+                                               C.c_double, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp,
+                                               _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "em_transducer_beam_workspace_bytes_lm": (_sz, [C.c_int, C.POINTER(EmTransducerWeights),
+                                                    C.POINTER(EmTransducerLmWeights), _i32, _i32, _i32]),
     "em_transducer_beam_limits": (None, [_vp, _vp, _vp, _vp, _vp]),
     "em_transducer_lattice_logp": (C.c_int, [C.c_int, C.POINTER(EmTransducerWeights), _vp, _vp, _i32, _i32, _vp, _vp, _i32,
                                              _vp, _vp, _i32, _vp, _vp, _sz, _vp]),

@@ -100,6 +100,61 @@ class SequentialRNNLM(PackedModule, BatchScorerInterface):
         w.rnn = C.cast(layers, C.POINTER(L.EmRnnLayer))
         pk.w, pk.layers = w, layers
 
+    def transducer_lm_weights(self, device):
+        """(EmTransducerLmWeights, what it points into) for `em_transducer_lm_step` and the LM-fused transducer beam search
+        on `device`; lstm and gru only.  The view is built at the first call for a pack, not with the pack: it needs the
+        embedding table once more in the compute dtype (the row kernels read layer 0's input rows from it; with tied
+        weights the head's matrix is that table), which the CTC / attention search never reads."""
+        if self.rnn_type not in ("LSTM", "GRU"):
+            raise NotImplementedError(f"rnn_type={self.rnn_type.lower()!r}: the transducer search fuses lstm and gru LMs")
+        pk = self.packed(torch.device(device))
+        hit = self.__dict__.get("_tlm")
+        if hit is not None and hit[0] == pk.serial:
+            return hit[1], hit[2]
+        w = pk.w
+        if self.decoder.weight is self.encoder.weight:
+            embed = None
+        else:
+            eu = self._pad(self.unit)
+            e = torch.zeros(self.vocab_size, eu, dtype=torch.float32)
+            e[:, : self.unit] = self.encoder.weight.detach().to(torch.float32)
+            embed = e.to(pk.act).to(pk.device)
+            if pk.device.type == "cuda":
+                torch.cuda.current_stream(pk.device).synchronize()
+        t = L.EmTransducerLmWeights()
+        t.kind, t.vocab, t.nhid, t.d, t.embed_unit, t.num_layers = w.kind, w.vocab, w.nhid, w.d, w.embed_unit, w.num_blocks
+        t.embed = w.out_w if embed is None else embed.data_ptr()
+        t.rnn, t.out_w, t.out_b = w.rnn, w.out_w, w.out_b
+        self.__dict__["_tlm"] = (pk.serial, t, (pk, embed))
+        return t, (pk, embed)
+
+    def init_rows_state(self, batch_size: int, device="cuda"):
+        """Zero states for `batch_size` rows as the row kernels take them: (h, master), each (nlayers, batch_size,
+        padded nhid)."""
+        d = self._pad(self.nhid)
+        return (torch.zeros(self.nlayers, batch_size, d, dtype=self.act_dtype, device=device),
+                torch.zeros(self.nlayers, batch_size, d, dtype=torch.float32, device=device))
+
+    @torch.no_grad()
+    def step_rows(self, tok: torch.Tensor, state, mask: Optional[torch.Tensor] = None, logp: Optional[torch.Tensor] = None):
+        """`em_transducer_lm_step` for n rows: tok (n,) int32, state = (h, master) (nlayers, n, padded nhid).  Returns
+        (logp (n, V) f32, new state).  With `mask` (n,) int32 the rows with mask == 0 keep their state and their row of
+        `logp` (the previous step's, then required) is not written.  A row's result does not depend on the other rows."""
+        hs, cs = state
+        L.require_gpu(hs, "state")
+        n, dev = int(tok.numel()), hs.device
+        w, keep = self.transducer_lm_weights(dev)
+        hs, cs = hs.contiguous(), cs.contiguous()
+        hs_out, cs_out = torch.empty_like(hs), torch.empty_like(cs)
+        if logp is None:
+            if mask is not None:
+                raise ValueError("a masked step needs the previous rows (`logp`)")
+            logp = torch.empty(n, self.vocab_size, dtype=torch.float32, device=dev)
+        L.check(L.load().em_transducer_lm_step(self.em_dtype, C.byref(w), L.ptr(tok), L.ptr(mask), n, L.ptr(hs), L.ptr(cs),
+                                               L.ptr(hs_out), L.ptr(cs_out), L.ptr(logp), L.current_stream_ptr()),
+                "em_transducer_lm_step")
+        return logp, (hs_out, cs_out)
+
     # ------------------------------------------------------------------ scorer interface (one call per step)
     @torch.no_grad()
     def batch_score(self, ys: torch.Tensor, states, xs: torch.Tensor):

@@ -1468,6 +1468,28 @@ int em_transducer_greedy(int dtype, const EmTransducerWeights* w, const float* e
                          int32_t T, int32_t* tokens, int32_t* ylens, float* score, int32_t* frame_tok, float* frame_top,
                          float* frame_margin, void* ws, size_t ws_bytes, void* stream);
 size_t em_transducer_greedy_workspace_bytes(int dtype, const EmTransducerWeights* w, int32_t B, int32_t T);
+/*   The language model fused into the transducer beam search (shallow fusion, BeamSearchTransducer(lm=...)): a
+ *   SequentialRNNLM (espnet2/lm/seq_rnn_lm.py) with LSTM or GRU cells, read by the row kernels of the prediction network.
+ *   d = nhid and embed_unit = the embedding width, each padded to a multiple of 64 with zeros; states as above
+ *   ([num_layers][n][d] act + the f32 master state); rnn = EmRnnLayer, layer 0 with in_pad = embed_unit, the others d.
+ *   Unlike EmLmWeights.embed the table here is in the compute dtype (the row kernels read layer 0's input rows from it). */
+typedef struct EmTransducerLmWeights {
+  int32_t kind;            /* EM_LM_LSTM | EM_LM_GRU */
+  int32_t vocab, nhid, d;  /* d = nhid padded */
+  int32_t embed_unit;      /* padded */
+  int32_t num_layers;
+  const void* embed;            /* [vocab][embed_unit] act: encoder.weight */
+  const struct EmRnnLayer* rnn; /* [num_layers], host array */
+  const void* out_w;            /* [vocab][d] act: decoder.weight */
+  const float* out_b;           /* [vocab]: decoder.bias */
+} EmTransducerLmWeights;
+/*   One step of that LM for n rows: tok [n] the token each row reads, states hs_in act / cs_in f32 [num_layers][n][d] ->
+ *   hs_out / cs_out (other buffers than the inputs; pad channels are written zero), logp [n][vocab] f32 = log_softmax of
+ *   decoder(top h).  mask [n] or NULL as em_transducer_dec_step takes it: a row with mask[r] == 0 copies its state bit for
+ *   bit and its logp row is not written.  A row's result depends on that row's operands only (row r of an n-row call
+ *   carries the bits of the one-row call), which em_lm_step's tiled GEMM does not promise.                             */
+int em_transducer_lm_step(int dtype, const EmTransducerLmWeights* w, const int32_t* tok, const int32_t* mask, int32_t n,
+                          const void* hs_in, const float* cs_in, void* hs_out, float* cs_out, float* logp, void* stream);
 
 /* ---- transducer beam search (csrc/transducer_beam.hip): BeamSearchTransducer.default_beam_search for a ragged batch in
  *      lock-step, with no host read-back inside a call.  One STEP is one expansion - the pop of the best open hypothesis,
@@ -1502,6 +1524,24 @@ int em_transducer_beam_search(int dtype, const EmTransducerWeights* w, const flo
                               double* out_scores, int32_t* out_count, float* step_logp, int32_t* step_trace, void* ws,
                               size_t ws_bytes, void* stream);
 size_t em_transducer_beam_workspace_bytes(int dtype, const EmTransducerWeights* w, int32_t B, int32_t T, int32_t beam);
+/*   The same search with a language model fused in (lm NULL: exactly the calls above, which are calls of these).  Every
+ *   hypothesis carries a second recurrent state: its LM row is the log-softmax of the LM after it has read sos =
+ *   vocab - 1 and the hypothesis' labels, its LM post-state the state after that read; children take it as pre-state, the
+ *   blank extension keeps the hypothesis' own.  The labels are chosen on the joint log-probabilities alone, as above;
+ *   child k enters the open set with (parent + (double)logp[k]) + lm_weight * (double)lm_logp[k], taken in double in that
+ *   order, the product and the sum rounded separately (no FMA); the kept entry gets no LM term.  A step runs the LM's
+ *   layers and head (em_transducer_lm_step's kernels, rows = utterances) behind the joint logits; the head recomputes a
+ *   carried hypothesis' row from its stored top h.  lm->vocab must equal w->vocab (EM_ERR_BAD_ARG).  Test hook:
+ *   step_lm_logp [B][vocab] f32 (NULL: none; needs lm), the LM rows of the call's last step.  The workspace grows by
+ *   B * 256 * num_layers * d * (act bytes + 4) for the LM states of the slots plus per-step rows.                        */
+int em_transducer_beam_search_lm(int dtype, const EmTransducerWeights* w, const EmTransducerLmWeights* lm, double lm_weight,
+                                 const float* enc_proj, const int32_t* olens, int32_t B, int32_t T, int32_t beam,
+                                 int32_t max_expansions, int32_t Lmax, int32_t nbest_cap, int32_t first, int32_t steps,
+                                 int32_t* status, int32_t* out_tokens, int32_t* out_lens, double* out_scores,
+                                 int32_t* out_count, float* step_logp, int32_t* step_trace, float* step_lm_logp, void* ws,
+                                 size_t ws_bytes, void* stream);
+size_t em_transducer_beam_workspace_bytes_lm(int dtype, const EmTransducerWeights* w, const EmTransducerLmWeights* lm,
+                                             int32_t B, int32_t T, int32_t beam);
 void em_transducer_beam_limits(int32_t* beam_max, int32_t* open_max, int32_t* kept_max, int32_t* expansions_max,
                                int32_t* labels_max);
 
