@@ -999,24 +999,31 @@ int src_attn_launch(const void* qs, const void* kmem, int ldk, const void* vT, c
 
 }  // namespace
 
-// the beam-tree form of em_dec_self_attention for the offline search's decoder step (bf16, d_k = 64, rows = B x W with
-// W <= 16 consecutive rows per utterance, Lmax <= 512, no token mask); EM_ERR_UNSUPPORTED otherwise (the caller keeps the
-// per-row kernel).  ESPNET_AMD_NO_SA_TREE=1: developer A/B switch.
-int em_dec_self_attention_tree_bf16(const void* qkv, void* kc, void* vc, const int* anc, const int* anc_odd, int n, int d,
-                                    int heads, int Lmax, int pos, const int* pos_dev, int W, void* ctx, void* stream) {
+// Which kernel em_dec_self_attention_beam runs for a shape: 1 the beam-tree kernel, 0 the per-row kernel.  The ONE statement of
+// the tree kernel's acceptance (bf16, d_k = 64, W in 2 .. 16 consecutive rows per utterance, Lmax <= 512, a key list within the
+// 64 KiB default LDS, 32-bit buffer offsets, the row minimum): the launcher below asks it and nothing else.
+// ESPNET_AMD_NO_SA_TREE=1, ESPNET_AMD_SA_TREE_MIN_ROWS: developer A/B switches.
+extern "C" int em_dec_self_attention_beam_route(int dtype, int32_t n, int32_t d, int32_t heads, int32_t Lmax, int32_t W) {
+  if (dtype != EM_BF16 || W <= 1) return 0;
   const bool off = em_sw().no_sa_tree;
-  if (off || heads <= 0 || d != 64 * heads || W < 1 || W > 16 || n % W != 0 || n > 65535 || Lmax > TREE_LMAX || pos < 0 ||
-      pos >= Lmax)
-    return EM_ERR_UNSUPPORTED;
+  if (off || heads <= 0 || d != 64 * heads || W > 16 || n <= 0 || n % W != 0 || n > 65535 || Lmax < 1 || Lmax > TREE_LMAX) return 0;
   // one workgroup per (utterance, head) walks the whole prefix: worth it once the per-row kernel's n x heads waves are several
   // rounds of the chip - configs[3] per GPU (640 rows): 0.620 -> 0.593 ms per label step; 480 / 320 / 240 rows: 0.578 -> 0.557,
   // 0.499 -> 0.492, 0.417 -> 0.410; configs[2] (160 rows): 0.352 -> 0.367, the per-row kernel stays (profiles/
   // r05n_tree_self_attention_ab.txt, r05l_label_step_dispatch_sweep.txt).  ESPNET_AMD_SA_TREE_MIN_ROWS: developer switch.
   const int min_rows = em_sw().sa_tree_min_rows;  // (the kernel tests lower it in-process: em_dev_switches_reload)
-  if (n < min_rows) return EM_ERR_UNSUPPORTED;
-  if ((size_t)Lmax * n * d * 2 >= ((size_t)1 << 31)) return EM_ERR_UNSUPPORTED;  // (buffer offsets are 32-bit)
+  if (n < min_rows) return 0;
+  if ((size_t)Lmax * n * d * 2 >= ((size_t)1 << 31)) return 0;  // (buffer offsets are 32-bit)
+  if (tree_lds_bytes(W, Lmax) > 64 * 1024) return 0;  // (the default dynamic-LDS limit: no attribute call, legal inside a stream capture)
+  return 1;
+}
+
+// the beam-tree form of em_dec_self_attention for the offline search's decoder step (the shapes
+// em_dec_self_attention_beam_route accepts); EM_ERR_UNSUPPORTED otherwise (the caller keeps the per-row kernel).
+int em_dec_self_attention_tree_bf16(const void* qkv, void* kc, void* vc, const int* anc, const int* anc_odd, int n, int d,
+                                    int heads, int Lmax, int pos, const int* pos_dev, int W, void* ctx, void* stream) {
+  if (pos < 0 || pos >= Lmax || !em_dec_self_attention_beam_route(EM_BF16, n, d, heads, Lmax, W)) return EM_ERR_UNSUPPORTED;
   const size_t lds = tree_lds_bytes(W, Lmax);
-  if (lds > 64 * 1024) return EM_ERR_UNSUPPORTED;  // (the default dynamic-LDS limit: no attribute call, legal inside a stream capture)
   dim3 grid(heads, n / W);
 #define EM_TREE_LAUNCH(WT)                                                                                                  \
   hipLaunchKernelGGL(dec_self_attn_tree_kernel<WT>, grid, dim3(256), lds, (hipStream_t)stream, (const bf16*)qkv, (bf16*)kc, \

@@ -782,6 +782,9 @@ int em_dec_self_attention(int dtype, const void* qkv, void* kc, void* vc, const 
 int em_dec_self_attention_beam(int dtype, const void* qkv, void* kc, void* vc, const int32_t* anc,
                                const int32_t* anc_odd, int32_t n, int32_t d, int32_t heads, int32_t Lmax,
                                int32_t pos, const int32_t* pos_dev, int32_t W, void* ctx, void* stream);
+/*   Which kernel em_dec_self_attention_beam runs for a shape: 1 the beam-tree kernel, 0 em_dec_self_attention's per-row kernel.
+ *   The launcher asks this function itself; it honours ESPNET_AMD_NO_SA_TREE and ESPNET_AMD_SA_TREE_MIN_ROWS.            */
+int em_dec_self_attention_beam_route(int dtype, int32_t n, int32_t d, int32_t heads, int32_t Lmax, int32_t W);
 /*   TransformerLM input (espnet2/lm/transformer_lm.py:35, transformer/encoder.py:132-139):
  *   e[r] = embed[tok_row[r]] in the act dtype;  then (after the input Linear) in place on x f32:
  *   torch LayerNorm(eps 1e-5) -> ReLU -> optional x*sqrt(d) + pe[pos].  pos_dev as above.       */

@@ -232,10 +232,10 @@ def worst(got, ref, dtype):
     return float(ratio.reshape(-1)[flat]), tuple(int(x) for x in torch.unravel_index(torch.tensor(flat), ratio.shape))
 
 
-def assert_in_budget(got, ref, dtype, what):
-    """Holds every element of got [B][T][h * 64] to the budget; returns the worst err / budget."""
+def assert_in_budget(got, ref, dtype, what, dk=DK):
+    """Holds every element of got [B][T][h * dk] to the budget; returns the worst err / budget."""
     r, (b, i, c) = worst(got, ref, dtype)
     g = float(got.detach().cpu().to(torch.float64).reshape(ref.ctx.shape)[b, i, c])
-    assert r <= 1.0, (f"{what}: err / budget = {r:.3g} at utterance {b}, head {c // DK}, row {i}, channel {c % DK}: got {g!r}, "
+    assert r <= 1.0, (f"{what}: err / budget = {r:.3g} at utterance {b}, head {c // dk}, row {i}, channel {c % dk}: got {g!r}, "
                       f"reference {float(ref.ctx[b, i, c])!r}, A {float(ref.A[b, i, c]):.3e}, S {float(ref.S[b, i, c]):.3g}")
     return r
