@@ -549,7 +549,7 @@ class Speech2Text:
                      weight is zero or that the model lacks is absent, as in the search;
           score      the sum of `scores` weighted with `self.beam_search.weights` (accumulated on the host, in key order).
         A candidate its utterance has too few frames for has ctc = -inf.  Needs an object built with the joint search;
-        whole-sentence n-gram scoring does not exist (NotImplementedError for an object with `ngram_file`).  The
+        there is no n-gram column here (NotImplementedError for an object with `ngram_file`; `batch_ngram_logp` gives it).  The
         utterances are encoded as `batch_decode` encodes them; the candidates go through in slices of
         `nll_rows_per_call`, a slice's candidates sharing their utterance's CTC log-probabilities and projected memory.
         Every scorer only enqueues; one D2H copy per call."""
@@ -591,6 +591,37 @@ class Speech2Text:
         if "length_bonus" in keys:
             col["length_bonus"] = torch.tensor([n + 1.0 for n in sl.ylens], dtype=torch.float32).to(dev, non_blocking=True)
         return torch.stack([col[k] for k in keys], dim=1)
+
+    # ------------------------------------------------------------------ the n-gram's score of given transcripts
+    @torch.no_grad()
+    def batch_ngram_logp(self, texts):
+        """The n-gram column of given transcripts, text only (no audio): texts[b] is one transcript or a list of candidates
+        of utterance b, strings or token ids as `batch_rescore` takes them.  Returns one list per utterance with a dict per
+        candidate, in the caller's order:
+          token_int  the candidate's ids;
+          tokens     the log10 probability of every token and of the closing <eos>, what the search's n-gram scorer gives
+                     step by step (bit for bit: `Ngrambase.sequence_logp`);
+          ngram      their sum as the search accumulates `Hypothesis.scores["ngram"]`: in f32, in position order.
+        Needs an object built with `ngram_file`.  All candidates go through one enqueue (csrc/ngram_seq.hip) and one D2H
+        copy.  `batch_rescore` itself knows no n-gram column."""
+        if self.ngram is None:
+            raise RuntimeError("batch_ngram_logp: this object was built without ngram_file")
+        cb = CandidateBatch(texts, len(texts), self._target_ids, self.ngram.charlen)
+        if not len(cb):
+            return cb.regroup([])
+        ys = torch.zeros(len(cb), max(max(cb.ylens), 1), dtype=torch.int32)
+        for i, y in enumerate(cb.ids):
+            ys[i, : len(y)] = torch.tensor(y, dtype=torch.int32)
+        _, logp_tok, _ = self.ngram.sequence_logp(ys, torch.tensor(cb.ylens), eos=True, device=self.device)
+        rows = logp_tok.cpu().numpy()
+        res = []
+        for y, row in zip(cb.ids, rows):
+            tok = row[: len(y) + 1]
+            total = np.float32(0.0)
+            for v in tok:  # (the search's running sum: one f32 add per step, from 0)
+                total = np.float32(total + v)
+            res.append(dict(token_int=y, ngram=float(total), tokens=tok.tolist()))
+        return cb.regroup(res)
 
     def decode_greedy_device(self, st):
         """Device-resident G1 result: (tokens (B,T) i32 padded with -1, token_lens (B,) i32)."""

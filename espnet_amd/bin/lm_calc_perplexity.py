@@ -9,7 +9,11 @@ Same keywords as the reference's `calc_perplexity`, same files: `<output_dir>/ut
 `key value` line per sentence, ntokens = the sentence's tokens + <eos>) and `ppl` (the corpus figure from the summed
 nll and token counts).  The sentences of a batch are scored in one device enqueue (ESPnetLanguageModel.nll ->
 TransformerLM.sequence_nll, csrc/lm_seq.hip).  Data entries are `path,text,text_int` (token ids per line) or
-`path,text,text` (plain text, tokenised with the train config's token_type / bpemodel / token_list)."""
+`path,text,text` (plain text, tokenised with the train config's token_type / bpemodel / token_list).
+
+An ARPA n-gram is scored instead of a trained model with `--ngram_file FILE --token_list FILE` (one token per line, the
+ASR model's list; plain text also needs `--token_type`): the same files, the sentences of a batch in one enqueue
+(espnet_amd.lm.ngram.NgramLM, csrc/ngram_seq.hip).  Giving both LM sources is an error."""
 import logging
 from pathlib import Path
 from typing import Dict, List, Optional, Sequence, Tuple, Union
@@ -105,6 +109,46 @@ def calc_perplexity(output_dir: str, batch_size: int, dtype: str, ngpu: int, see
     return ppl
 
 
+def calc_ngram_perplexity(output_dir: str, batch_size: int, ngpu: int, log_level: Union[int, str],
+                          data_path_and_name_and_type: Sequence[Tuple[str, str, str]], key_file: Optional[str],
+                          ngram_file: str, token_list: str, log_base: Optional[float], token_type: Optional[str] = None,
+                          bpemodel: Optional[str] = None):
+    """`calc_perplexity` for an ARPA n-gram (`ngram_file`) over the tokens of the file `token_list`."""
+    import argparse
+
+    from espnet_amd.lm.ngram import NgramLM
+
+    if batch_size < 1:
+        raise ValueError(f"batch_size must be positive: {batch_size}")
+    if ngpu != 1:
+        raise NotImplementedError("espnet_amd scores on one MI355X: pass --ngpu 1 (no CPU fallback)")
+    logging.basicConfig(level=log_level, format="%(asctime)s (%(module)s:%(lineno)d) %(levelname)s: %(message)s")
+    tokens = Path(token_list).read_text(encoding="utf-8").splitlines()
+    model = NgramLM(ngram_file, tokens)
+    data = read_text_entries(data_path_and_name_and_type,
+                             argparse.Namespace(token_type=token_type, bpemodel=bpemodel, token_list=tokens))
+    keys = list(read_2columns_text(key_file)) if key_file is not None else list(data)
+    missing = [k for k in keys if k not in data]
+    if missing:
+        raise RuntimeError(f"{len(missing)} keys of {key_file} are not in the text entry, e.g. {missing[0]}")
+    ppl = write_perplexity(model, data, keys, output_dir, batch_size, log_base, torch.device("cuda"))
+    logger.info(f"perplexity {ppl} over {len(keys)} sentences")
+    return ppl
+
+
+def lm_source(kwargs: dict) -> str:
+    """"model" or "ngram": which of the two LM sources the options name; both, neither or half of one: ValueError."""
+    model = [k for k in ("train_config", "model_file") if kwargs.get(k) is not None]
+    ngram = [k for k in ("ngram_file", "token_list") if kwargs.get(k) is not None]
+    if model and ngram:
+        raise ValueError(f"two LM sources: --{model[0]} and --{ngram[0]}; give a trained model or an n-gram file, not both")
+    if kwargs.get("ngram_file") is not None or kwargs.get("token_list") is not None:
+        if len(ngram) != 2:
+            raise ValueError("an n-gram needs both --ngram_file and --token_list")
+        return "ngram"
+    return "model"
+
+
 def _float_or_none(v: str):
     return None if v.strip().lower() in ("none", "null", "nil", "") else float(v)
 
@@ -133,6 +177,11 @@ def get_parser():
     g = p.add_argument_group("The model configuration related")
     g.add_argument("--train_config", type=str)
     g.add_argument("--model_file", type=str)
+    g = p.add_argument_group("An ARPA n-gram instead of a trained model")
+    g.add_argument("--ngram_file", type=str, help="plain-text ARPA file")
+    g.add_argument("--token_list", type=str, help="the tokens the ids refer to, one per line")
+    g.add_argument("--token_type", type=_str_or_none, default=None, help="tokeniser of a plain-text data entry")
+    g.add_argument("--bpemodel", type=_str_or_none, default=None)
     return p
 
 
@@ -149,6 +198,11 @@ def main(cmd=None):
             parser.set_defaults(**(yaml.safe_load(f) or {}))
     kwargs = vars(parser.parse_args(cmd))
     kwargs.pop("config", None)
+    ngram = {k: kwargs.pop(k) for k in ("ngram_file", "token_list", "token_type", "bpemodel")}
+    if lm_source({**kwargs, **ngram}) == "ngram":
+        return calc_ngram_perplexity(**{k: kwargs[k] for k in ("output_dir", "batch_size", "ngpu", "log_level",
+                                                                "data_path_and_name_and_type", "key_file", "log_base")},
+                                     **ngram)
     return calc_perplexity(**kwargs)
 
 

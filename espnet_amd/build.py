@@ -22,7 +22,9 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc",
 # per-file extras.  block.hip: its kernels live at the 256-VGPR line with MFMA accumulators carried around loops; in
 # hipcc's default "AGPR form" every loop trip copies the accumulators VGPR <-> AGPR (~100 v_accvgpr moves per FFN
 # iteration, as much issue time as the MFMAs).  VGPR form keeps them where the VALU epilogues need them.
-EXTRA_FLAGS = {"block.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"]}
+# ngram_seq.hip: its values must match the step scorer's single f32 adds bit for bit; no packed-f32 VALU forms there.
+EXTRA_FLAGS = {"block.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
+               "ngram_seq.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 def _sources():

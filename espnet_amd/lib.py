@@ -428,6 +428,7 @@ _SIGNATURES = {
                                       C.c_float, C.c_float, C.POINTER(EmNgramModel), _vp, _i32, _sz, _vp, _vp, _vp, _vp, _vp,
                                       _vp, _vp, _vp, _vp, _vp]),
     "em_ngram_score": (C.c_int, [C.POINTER(EmNgramModel), _i32, _vp, _vp, _vp, _vp, _i32, _vp, _vp]),
+    "em_ngram_seq_logp": (C.c_int, [C.POINTER(EmNgramModel), _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     "em_arpa_count": (C.c_int, [C.c_char_p, _vp, _vp, _vp]),
     "em_arpa_load": (C.c_int, [C.c_char_p, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "em_transducer_dec_step": (C.c_int, [C.c_int, C.POINTER(EmTransducerWeights), _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp,

@@ -14,7 +14,7 @@ that is no unigram of the file scores as `<unk>` (ESPnet2's `<sos/eos>` normally
 """
 import ctypes as C
 from pathlib import Path
-from typing import List, Sequence
+from typing import List, Optional, Sequence
 
 import numpy as np
 
@@ -96,6 +96,49 @@ def load_arpa(path) -> ArpaModel:
     words = bytes(vocab[: vbytes.value]).decode("utf-8").split("\0")[:-1]
     assert len(words) == cnt[0]
     return ArpaModel(path, N, words, wid, prob, bow, nxt)
+
+
+class NgramLM:
+    """An ARPA file and a token list as a text-scoring model: `nll` / `batchify_nll` with the shapes and signs of
+    `ESPnetLanguageModel`'s (espnet_amd/lm/transformer_lm.py), so that it stands where that model stands in the perplexity
+    tool (espnet_amd/bin/lm_calc_perplexity.py `write_perplexity`).  The sentences of a call are scored in one enqueue
+    (`Ngrambase.sequence_logp`, csrc/ngram_seq.hip); `<eos>` - the last token of the list - is scored behind each."""
+
+    def __init__(self, ngram_file, token_list: Sequence[str]):
+        from espnet_amd.nets.scorers.ngram import NgramFullScorer  # (that module imports this one)
+
+        self.scorer = NgramFullScorer(ngram_file, token_list)
+        self.sos = self.eos = len(self.scorer.token_list) - 1
+
+    def nll(self, text, text_lengths, max_length: Optional[int] = None):
+        """text (B, Lt) integer ids, text_lengths (B,) -> (nll (B, L + 1) f64 on the device, x_lengths (B,) = text_lengths
+        + 1 where text_lengths lives): nll[i, j] = -ln p(token j of sentence i | its history), the file's log10 turned
+        into nats, `<eos>` at j = text_lengths[i], exactly 0.0 behind.  L is the longest sentence, or `max_length`.  The
+        ids are checked on the host (a device `text` is copied there first)."""
+        import torch
+
+        text, text_lengths = torch.as_tensor(text), torch.as_tensor(text_lengths)
+        if text.dim() != 2 or text_lengths.dim() != 1 or text.size(0) != text_lengths.size(0):
+            raise ValueError(f"text (B, L) and text_lengths (B,) expected, got {tuple(text.shape)}, {tuple(text_lengths.shape)}")
+        longest = int(text_lengths.max()) if text_lengths.numel() else 0
+        width = longest if max_length is None else int(max_length)
+        if longest > width or longest > text.size(1):
+            raise ValueError(f"text_lengths up to {longest} exceed the {min(width, text.size(1))} columns of text that are scored")
+        _, logp_tok, _ = self.scorer.sequence_logp(text[:, :width], text_lengths, eos=True,
+                                                   device=text.device if text.is_cuda else None)
+        return (0.0 - logp_tok.double()) * np.log(10.0), text_lengths + 1
+
+    def batchify_nll(self, text, text_lengths, batch_size: int = 100):
+        """`nll` over slices of `batch_size` sentences, every slice as wide as the longest sentence of the whole call."""
+        import torch
+
+        total = text.size(0)
+        if total <= batch_size:
+            return self.nll(text, text_lengths)
+        max_length = int(text_lengths.max())
+        parts = [self.nll(text[s:s + batch_size], text_lengths[s:s + batch_size], max_length=max_length)
+                 for s in range(0, total, batch_size)]
+        return torch.cat([p[0] for p in parts]), torch.cat([p[1] for p in parts])
 
 
 def chardict(token_list: Sequence[str]) -> List[str]:

@@ -9,6 +9,7 @@ row carries the trie node of each context length and the scorer runs on the devi
 scorer scores all V tokens before the pre-beam, the part scorer only the pre-beam candidates after it.  `score` /
 `batch_score` / `score_partial` / `select_state` are the reference's per-step scorer interface on the same kernels
 (`em_ngram_score`); a state is the hypothesis' context nodes, an int32 device tensor, None before the first step.
+`sequence_logp` scores GIVEN sentences, every position at once (`em_ngram_seq_logp`, csrc/ngram_seq.hip), with the same bits.
 """
 import ctypes as C
 from typing import Any, List
@@ -88,6 +89,44 @@ class Ngrambase(PackedModule):
         L.check(L.load().em_ngram_score(C.byref(pk.w), n, L.ptr(prev), L.ptr(last), L.ptr(out_state), c_ptr, n_cand,
                                         L.ptr(out), L.current_stream_ptr()), "em_ngram_score")
         return out, [out_state[r] for r in range(n)]
+
+    # ------------------------------------------------------------------ whole sentences (one enqueue)
+    @torch.no_grad()
+    def sequence_logp(self, ys, ylens, eos: bool = True, device=None):
+        """Every token of given sentences scored in one enqueue (`em_ngram_seq_logp`, csrc/ngram_seq.hip): ys (N, Lp)
+        HOST token ids (the padding may hold anything), ylens (N,) host lengths; eos: `<eos>` (the last token of the list,
+        as the search scores it) is scored behind each sentence.  Returns device tensors
+          logp (N,) f64                the sum of the row's scored positions, in position order;
+          logp_tok (N, Lp + 1) f32     log10 per position, bit for bit what `batch_score` returns step by step;
+          order_tok (N, Lp + 1) i32    the n-gram order that matched after back-off;
+        the two per-position tensors hold 0 where nothing is scored.  Ids and lengths are checked here, on the host
+        (ValueError), before anything is launched; nothing is read back."""
+        dev = torch.device("cuda") if device is None else torch.device(device)
+        if dev.type != "cuda":
+            raise L.EspnetAmdError(f"sequence_logp on {dev}: espnet_amd runs only on an MI355X (HIP) device")
+        ids_h = torch.as_tensor(ys).cpu()
+        len_h = torch.as_tensor(ylens).cpu()
+        if ids_h.dim() != 2 or len_h.dim() != 1 or len_h.numel() != ids_h.size(0) or ids_h.is_floating_point() or \
+                len_h.is_floating_point():
+            raise ValueError(f"sequence_logp: integer ys (N, Lp) and ylens (N,) expected, got {tuple(ids_h.shape)} and "
+                             f"{tuple(len_h.shape)}")
+        n, Lp = ids_h.shape
+        if n and (int(len_h.min()) < 0 or int(len_h.max()) > Lp):
+            raise ValueError(f"sequence_logp: ylens must lie in [0, {Lp}]")
+        scored = torch.arange(Lp).unsqueeze(0) < len_h.unsqueeze(1)
+        if bool((scored & ((ids_h < 0) | (ids_h >= self.charlen))).any()):
+            raise ValueError(f"sequence_logp: token ids must lie in [0, {self.charlen})")
+        ids_h = ids_h.to(torch.int32).contiguous()
+        len_h = len_h.to(torch.int32).contiguous()
+        pk = self.packed(dev)
+        ids_d, len_d = ids_h.to(dev, non_blocking=True), len_h.to(dev, non_blocking=True)
+        logp = torch.empty(n, dtype=torch.float64, device=dev)
+        logp_tok = torch.zeros(n, Lp + 1, dtype=torch.float32, device=dev)
+        order_tok = torch.zeros(n, Lp + 1, dtype=torch.int32, device=dev)
+        L.check(L.load().em_ngram_seq_logp(C.byref(pk.w), L.ptr(ids_d), L.ptr(len_d), L.ptr(ids_h), L.ptr(len_h), n, Lp,
+                                           self.charlen - 1 if eos else -1, L.ptr(logp_tok), L.ptr(order_tok), L.ptr(logp),
+                                           L.current_stream_ptr()), "em_ngram_seq_logp")
+        return logp, logp_tok, order_tok
 
     def _device(self, x):
         L.require_gpu(x, "x")

@@ -26,6 +26,7 @@
  *         frames at and behind olens[b] too (the padded batch's values, finite); w->ctc_ids [B][T] whole when planned;
  *       em_cb_encode_blocks[_batch], em_cbt_encode_blocks[_batch]: the blocks in place and next_ctx whole;
  *       em_dec_seq_nll, em_lm_seq_nll, em_lm_head_nll: nll whole (exactly 0.0 where nothing is scored);
+ *       em_ngram_seq_logp: logp whole; logp_tok and order_tok [n][< ylens[n] + (eos_id >= 0)] only;
  *       em_ctc_forced_align: every output whole (labels -1, spans -1, scores 0 behind the lengths);
  *       em_ctc_segment: every output whole (columns -1, frames -1, scores 0 off the path and behind the lengths);
  *       em_transducer_greedy: ylens and score whole, tokens[b][< ylens[b]], the traces [b][< olens[b]];
@@ -1654,6 +1655,32 @@ int em_search_online_rewind(const EmSearchParams* p, const EmSearchBuffers* b, v
  *   token ids and out [n][n_cand] (part scorer).  m: device arrays, host struct.                                      */
 int em_ngram_score(const EmNgramModel* m, int32_t n, const int32_t* prev_state, const int32_t* last_tok,
                    int32_t* out_state, const int32_t* cand, int32_t n_cand, float* out, void* stream);
+
+/* ---- n-gram log-probability of given sentences (csrc/ngram_seq.hip): every token of a ragged batch of N sentences scored
+ *      in one enqueue, the whole-sequence form of em_ngram_score as em_lm_seq_nll is of the neural LM's step.
+ *   m: the pack em_ngram_score takes (device arrays, host struct).  ids [N][Lp] i32 token ids in [0, m->vocab), ylens [N] in
+ *      [0, Lp], on the device; ids_host / ylens_host: the caller's HOST copies of the two, which this call checks before
+ *      it launches anything (only ids_host[n][< ylens_host[n]] are checked and only ids[n][< ylens[n]] are read: the padding
+ *      may hold anything).  eos_id: the token scored after the last one (the search's n-gram scorer does score <eos>), or
+ *      negative: none.  Row n scores len_n = ylens[n] + (eos_id >= 0) positions.
+ *   Outputs, on the device:
+ *      logp_tok  [N][Lp+1] f32  log10 probability of position j < len_n: BIT FOR BIT column ids[n][j] (eos_id at j ==
+ *                               ylens[n]) of the row em_ngram_score returns for the state reached from the start state
+ *                               through ids[n][0 .. j-1] - the same table entries, the back-off weights added in the same
+ *                               order, the same handling of tokens that are no unigram (<unk>), of <s> and of the
+ *                               token -> word tables;
+ *      order_tok [N][Lp+1] i32  the order of the n-gram that matched there after back-off (1 = the unigram);
+ *      logp      [N]       f64  the row's logp_tok[n][0 .. len_n-1] added in position order (0.0 for an empty row).
+ *      logp is written whole; logp_tok and order_tok are written at the scored positions ONLY - behind len_n they keep
+ *      what the caller put there.  A row's outputs depend on its own ids and ylens only: bit for bit the same whatever N,
+ *      Lp and the companions are.
+ *   Any Lp >= 0 (rows longer than 256 positions take a second small launch for their sums); no workspace.  Nothing is
+ *      launched and no output is touched when an argument is refused: EM_ERR_BAD_ARG for an id outside [0, vocab) in front
+ *      of its row's length, a length outside [0, Lp], eos_id >= vocab, a NULL array or an inconsistent pack;
+ *      EM_ERR_UNSUPPORTED for a pack of an order above EM_NGRAM_MAX_ORDER or N * ceil((Lp+1) / 256) >= 2^31.            */
+int em_ngram_seq_logp(const EmNgramModel* m, const int32_t* ids, const int32_t* ylens, const int32_t* ids_host,
+                      const int32_t* ylens_host, int32_t N, int32_t Lp, int32_t eos_id, float* logp_tok, int32_t* order_tok,
+                      double* logp, void* stream);
 
 /* ---- A16: streaming (contextual block) Conformer encoder step
  *      (ContextualBlockConformerEncoder.forward_infer, espnet2/asr/encoder/
