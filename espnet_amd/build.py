@@ -23,8 +23,10 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc",
 # hipcc's default "AGPR form" every loop trip copies the accumulators VGPR <-> AGPR (~100 v_accvgpr moves per FFN
 # iteration, as much issue time as the MFMAs).  VGPR form keeps them where the VALU epilogues need them.
 # ngram_seq.hip: its values must match the step scorer's single f32 adds bit for bit; no packed-f32 VALU forms there.
+# rnn_lm_seq.hip: the cells' f32 arithmetic is that of the step kernels, one scalar operation at a time.
+_NO_PACKED_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 EXTRA_FLAGS = {"block.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
-               "ngram_seq.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+               "ngram_seq.hip": _NO_PACKED_F32, "rnn_lm_seq.hip": _NO_PACKED_F32}
 
 
 def _sources():

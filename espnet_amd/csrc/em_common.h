@@ -221,6 +221,12 @@ int em_dec_src_attention_lnq_memfrag_bf16(const float* x, const float* g, const 
                                           const float* bq, const void* kf, const void* vf, const int32_t* klens, int B, int W, int d,
                                           int heads, int T, int Tpad, void* ctx, void* stream);
 
+// csrc/vocab_head.hip: em_lm_head_nll without the LayerNorm, on rows [M][d] in the compute dtype (the recurrent LM's top-layer
+// h, csrc/rnn_lm_seq.hip): nll[r] = logsumexp_v(y[r][v]) - y[r][target[r]], y = rows out_w^T + out_b, 0.0 where target[r] < 0;
+// same shapes, same workspace (em_lm_head_nll_workspace_bytes)
+int em_head_rows_nll(int dtype, const void* rows, const void* out_w, const float* out_b, const int32_t* target, int M, int V,
+                     int d, float* nll, void* ws, size_t ws_bytes, void* stream);
+
 // csrc/gemm_mid.hip: mid_gemm on fragment-major bf16 operands (EM_EPI_RESID_F32; frag 1: A and W, 2: W only)
 int em_gemm_mid_frag(int epilogue, int frag, const EmGemmArgs* p, void* stream);
 

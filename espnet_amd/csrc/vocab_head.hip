@@ -352,6 +352,14 @@ extern "C" int em_lm_head_nll(int dtype, const float* xrows, const float* norm_g
                                       stream);
 }
 
+// (csrc/em_common.h) the same record on rows that are activations already: no LayerNorm in front
+int em_head_rows_nll(int dtype, const void* rows, const void* out_w, const float* out_b, const int32_t* target, int M, int V,
+                     int d, float* nll, void* ws, size_t ws_bytes, void* stream) {
+  if (!rows || !out_w || !out_b || !target || !nll || M <= 0 || V <= 0 || d <= 0) return EM_ERR_BAD_ARG;
+  return head_launch<TargetRec, false>(dtype, rows, nullptr, nullptr, out_w, out_b, {target, nll}, M, V, d, ws, ws_bytes,
+                                       stream);
+}
+
 extern "C" size_t em_lm_head_top1_workspace_bytes(int dtype, int32_t M, int32_t V) { return head_ws_bytes(dtype, M, V); }
 
 extern "C" int em_lm_head_top1(int dtype, const float* xrows, const float* norm_g, const float* norm_b, const void* out_w,

@@ -231,6 +231,7 @@ class EmRnnLayer(C.Structure):
 
 
 EM_LM_TRANSFORMER, EM_LM_LSTM, EM_LM_GRU, EM_LM_RNN_TANH, EM_LM_RNN_RELU = 0, 1, 2, 3, 4
+EM_RNN_SEQ_HOIST, EM_RNN_SEQ_CHAIN, EM_RNN_SEQ_HEAD = 1, 2, 4  # em_rnn_lm_seq_nll_parts: parts
 
 
 class EmLmWeights(C.Structure):
@@ -384,6 +385,10 @@ _SIGNATURES = {
     "em_lm_head_nll": (C.c_int, [C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _sz, _vp]),
     "em_lm_seq_nll_workspace_bytes": (_sz, [C.c_int, C.POINTER(EmLmWeights), _i32, _i32]),
     "em_lm_seq_nll": (C.c_int, [C.c_int, C.POINTER(EmLmWeights), _vp, _vp, _i32, _i32, _vp, _vp, _sz, _vp]),
+    "em_rnn_lm_seq_nll_workspace_bytes": (_sz, [C.c_int, C.POINTER(EmLmWeights), _i32, _i32]),
+    "em_rnn_lm_seq_nll": (C.c_int, [C.c_int, C.POINTER(EmLmWeights), _vp, _vp, _vp, _i32, _i32, _vp, _vp, _sz, _vp]),
+    "em_rnn_lm_seq_nll_parts": (C.c_int, [C.c_int, C.POINTER(EmLmWeights), _vp, _vp, _vp, _i32, _i32, _vp, _vp, _sz, _i32,
+                                          _vp]),
     "em_dec_seq_embed_f32": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
     "em_dec_seq_src_attention": (C.c_int, [C.c_int, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32,
                                            _vp, _vp]),

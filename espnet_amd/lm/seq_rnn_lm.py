@@ -206,6 +206,56 @@ class SequentialRNNLM(PackedModule, BatchScorerInterface):
             states = [(hs[i, :, r], cs[i, :, r]) for r in range(n)]
         return out, states
 
+    @property
+    def sequence_nll_fits(self) -> bool:
+        """Can `sequence_nll` serve this model?  In bfloat16 its vocabulary head keeps 64 hidden rows in LDS: padded nhid
+        <= 1024 (csrc/vocab_head.hip HEAD_DMAX); a wider model is scored through `forward`."""
+        return self.em_dtype != L.EM_BF16 or self._pad(self.nhid) <= 1024
+
+    @torch.no_grad()
+    def sequence_nll(self, x: torch.Tensor, target: torch.Tensor, x_lengths: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Per-token negative log-likelihoods of whole sentences in one enqueue (`em_rnn_lm_seq_nll`, csrc/rnn_lm_seq.hip;
+        its head: csrc/vocab_head.hip): x (B, Lp) integer input tokens, target (B, Lp) the token scored at every position,
+        negative where nothing is scored -> nll (B, Lp) f32, exactly 0.0 there.  x_lengths (B,) (None: every sentence is Lp
+        long) lets the device skip the time steps behind the end of whole tiles of sentences; target must be negative at and
+        behind it.  What `forward` + cross-entropy compute position by position: layer 0's input product of all B * Lp rows
+        as one GEMM, then one launch per time step and wavefront of layers."""
+        L.require_gpu(x, "x")
+        L.require_gpu(target, "target")
+        if x.dim() != 2 or x.shape != target.shape or x.numel() == 0:
+            raise ValueError(f"sequence_nll: x and target must be equal, non-empty (B, Lp) tensors, got {tuple(x.shape)} "
+                             f"and {tuple(target.shape)}")
+        xi = x.to(torch.int32).contiguous()
+        ti = target.to(torch.int32).contiguous()
+        if bool(((xi < 0) | (xi >= self.vocab_size)).any() | (ti >= self.vocab_size).any()):
+            raise ValueError(f"sequence_nll: token ids must lie in [0, {self.vocab_size})")
+        li = None
+        if x_lengths is not None:
+            if x_lengths.shape != (x.size(0),):
+                raise ValueError(f"sequence_nll: x_lengths must be (B,), got {tuple(x_lengths.shape)}")
+            li = x_lengths.to(device=x.device, dtype=torch.int32).contiguous()
+            behind = torch.arange(x.size(1), device=x.device).unsqueeze(0) >= li.unsqueeze(1)
+            if bool(((ti >= 0) & behind).any()):
+                raise ValueError("sequence_nll: target must be negative at and behind x_lengths")
+        return self._sequence_nll(xi, ti, li)
+
+    def _sequence_nll(self, xi: torch.Tensor, ti: torch.Tensor, li: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """`sequence_nll` behind its checks: contiguous int32 device tensors (B, Lp), (B, Lp) and (B,) or None, taken as given
+        (the caller has checked their values).  Only enqueues."""
+        dev = xi.device
+        B, Lp = xi.shape
+        pk = self.packed(dev)
+        lib = L.load()
+        need = lib.em_rnn_lm_seq_nll_workspace_bytes(pk.dtype, C.byref(pk.w), B, Lp)
+        if need == 0:
+            raise NotImplementedError(f"sequence_nll: a batch of {B} x {Lp} tokens (hidden size {self.nhid}) is outside the "
+                                      "device path's range; score it in slices (ESPnetLanguageModel.batchify_nll)")
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        nll = torch.empty(B, Lp, dtype=torch.float32, device=dev)
+        L.check(lib.em_rnn_lm_seq_nll(pk.dtype, C.byref(pk.w), L.ptr(xi), L.ptr(ti), L.ptr(li), B, Lp, L.ptr(nll), L.ptr(ws),
+                                      need, L.current_stream_ptr()), "em_rnn_lm_seq_nll")
+        return nll
+
     def score(self, y: torch.Tensor, state, x: torch.Tensor):
         """seq_rnn_lm.py:118-138: one hypothesis."""
         logp, st = self.batch_score(y.unsqueeze(0), [state], x.unsqueeze(0))

@@ -163,11 +163,12 @@ class TransformerLM(PackedModule, BatchScorerInterface):
         return logp[0], st[0]
 
     @torch.no_grad()
-    def sequence_nll(self, x: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+    def sequence_nll(self, x: torch.Tensor, target: torch.Tensor, x_lengths: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Per-token negative log-likelihoods of whole sentences in one enqueue (`em_lm_seq_nll`, csrc/lm_seq.hip; its
         head: csrc/vocab_head.hip): x (B, Lp) integer input tokens with 0 behind a sentence's end, target (B, Lp) the token
         scored at every position, negative where nothing is scored -> nll (B, Lp) f32, exactly 0.0 there.  What `forward`
-        + cross-entropy compute position by position, over all B * Lp rows at once."""
+        + cross-entropy compute position by position, over all B * Lp rows at once.  x_lengths: the LM scorers' common
+        signature (SequentialRNNLM.sequence_nll); not read here, x's zeros are the key mask."""
         L.require_gpu(x, "x")
         L.require_gpu(target, "target")
         if x.dim() != 2 or x.shape != target.shape or x.numel() == 0:
@@ -179,9 +180,9 @@ class TransformerLM(PackedModule, BatchScorerInterface):
             raise ValueError(f"sequence_nll: token ids must lie in [0, {self.vocab_size})")
         return self._sequence_nll(xi, ti)
 
-    def _sequence_nll(self, xi: torch.Tensor, ti: torch.Tensor) -> torch.Tensor:
+    def _sequence_nll(self, xi: torch.Tensor, ti: torch.Tensor, li: Optional[torch.Tensor] = None) -> torch.Tensor:
         """`sequence_nll` behind its checks: contiguous int32 (B, Lp) device tensors taken as given (the caller has
-        checked their values).  Only enqueues."""
+        checked their values; `li`, the lengths, is not read).  Only enqueues."""
         dev = xi.device
         B, Lp = xi.shape
         pk = self.packed(dev, Lp + 1)
@@ -238,23 +239,29 @@ class ESPnetLanguageModel(torch.nn.Module):
     @torch.no_grad()
     def nll_of_checked(self, text: torch.Tensor, text_lengths: torch.Tensor, device) -> torch.Tensor:
         """`nll`'s first result for HOST text / text_lengths whose ids the caller has checked against the vocabulary:
-        the sentence pair is built on the host and the TransformerLM only enqueues (no verdict is read back).  A
-        recurrent LM goes through `nll`."""
-        if not isinstance(self.lm, TransformerLM):
+        the sentence pair is built on the host and the LM's whole-sentence route only enqueues (no verdict is read back).
+        An LM without that route goes through `nll`."""
+        if not self._whole_sentences():
             return self.nll(text.to(device, non_blocking=True), text_lengths)[0]
-        x, t, _, scored = self._masked_pair(text, text_lengths)
+        x, t, x_lengths, scored = self._masked_pair(text, text_lengths)
         t = torch.where(scored, t, torch.full_like(t, -1))
-        return self.lm._sequence_nll(*(v.to(torch.int32).contiguous().to(device, non_blocking=True) for v in (x, t)))
+        return self.lm._sequence_nll(*(v.to(torch.int32).contiguous().to(device, non_blocking=True) for v in (x, t, x_lengths)))
+
+    def _whole_sentences(self) -> bool:
+        """Does the LM score whole sentences in one enqueue (`sequence_nll`: TransformerLM, SequentialRNNLM)?  A recurrent LM
+        whose hidden rows the vocabulary head cannot hold (`sequence_nll_fits`) stays on its `forward`."""
+        return hasattr(self.lm, "sequence_nll") and getattr(self.lm, "sequence_nll_fits", True)
 
     @torch.no_grad()
     def nll(self, text: torch.Tensor, text_lengths: torch.Tensor, max_length: Optional[int] = None):
         """espnet_model.py:38-80.  text (B, Lt) int64, text_lengths (B,) -> (nll (B, L + 1) f32, x_lengths (B,)):
-        nll[i, j] = -log_softmax(lm(x)[i, j])[t[i, j]] for j < x_lengths[i], exactly 0.0 behind.  The TransformerLM scores
-        all rows in one enqueue (`sequence_nll`); a recurrent LM goes position by position through its `forward`."""
+        nll[i, j] = -log_softmax(lm(x)[i, j])[t[i, j]] for j < x_lengths[i], exactly 0.0 behind.  The TransformerLM and the
+        SequentialRNNLM score all rows in one enqueue (`sequence_nll`); an LM without that route goes position by position
+        through its `forward`."""
         L.require_gpu(text, "text")
         x, t, x_lengths, scored = self._masked_pair(text, text_lengths, max_length)
-        if isinstance(self.lm, TransformerLM):
-            return self.lm.sequence_nll(x, torch.where(scored, t, torch.full_like(t, -1))), x_lengths
+        if self._whole_sentences():
+            return self.lm.sequence_nll(x, torch.where(scored, t, torch.full_like(t, -1)), x_lengths), x_lengths
         logits, _ = self.lm(x, None)
         B, Lp, V = logits.shape
         rows = logits.reshape(B * Lp, V)

@@ -25,7 +25,7 @@
  *       em_conformer_encode, em_ebranchformer_encode, em_transformer_encode: enc_out, enc_act [B][T][d] whole - the
  *         frames at and behind olens[b] too (the padded batch's values, finite); w->ctc_ids [B][T] whole when planned;
  *       em_cb_encode_blocks[_batch], em_cbt_encode_blocks[_batch]: the blocks in place and next_ctx whole;
- *       em_dec_seq_nll, em_lm_seq_nll, em_lm_head_nll: nll whole (exactly 0.0 where nothing is scored);
+ *       em_dec_seq_nll, em_lm_seq_nll, em_rnn_lm_seq_nll, em_lm_head_nll: nll whole (exactly 0.0 where nothing is scored);
  *       em_ngram_seq_logp: logp whole; logp_tok and order_tok [n][< ylens[n] + (eos_id >= 0)] only;
  *       em_ctc_forced_align: every output whole (labels -1, spans -1, scores 0 behind the lengths);
  *       em_ctc_segment: every output whole (columns -1, frames -1, scores 0 off the path and behind the lengths);
@@ -1112,6 +1112,33 @@ int em_lm_head_nll(int dtype, const float* xrows, const float* norm_g, const flo
 size_t em_lm_seq_nll_workspace_bytes(int dtype, const EmLmWeights* lm, int32_t B, int32_t Lp);
 int em_lm_seq_nll(int dtype, const EmLmWeights* lm, const int32_t* x, const int32_t* target, int32_t B, int32_t Lp,
                   float* nll, void* ws, size_t ws_bytes, void* stream);
+
+/* ---- recurrent language model over whole sentences (csrc/rnn_lm_seq.hip): ESPnetLanguageModel.nll for the SequentialRNNLM
+ *      (espnet2/lm/seq_rnn_lm.py), the whole-sentence form of em_lm_step's recurrent route.  x, target, nll as em_lm_seq_nll
+ *      takes them, with one difference: behind a sentence's end x may hold any id in [0, V) (ids are clamped).
+ *   xlens [B] i32  x_lengths, or NULL: every sentence is Lp long.  A tile of 64 sentences that have all ended skips its
+ *                  remaining time steps; every position at and behind xlens[b] must carry target < 0.
+ *   lm: the pack of a SequentialRNNLM, kind EM_LM_LSTM | EM_LM_GRU | EM_LM_RNN_TANH | EM_LM_RNN_RELU (EM_LM_TRANSFORMER:
+ *   EM_ERR_BAD_ARG, nothing is launched), d and embed_unit multiples of 64, any nhid <= d and any depth.
+ *   The chain, enqueue only: em_lm_embed and ONE em_gemm give layer 0's input product of all B * Lp rows; then Lp +
+ *   num_blocks - 1 dependent launches of the step kernel, launch s running layer l at time s - l for every layer that has such
+ *   a time (f32 accumulation, f32 master state c / h, h in the compute dtype between the layers); then the vocabulary head
+ *   without LayerNorm on the top layer's h, the logits never stored.  The stream's order of launches is the only ordering
+ *   between workgroups.  A row depends on the tokens of its own sentence at positions <= its own and on nothing else (bit for
+ *   bit, for a given B and Lp).  ws: em_rnn_lm_seq_nll_workspace_bytes bytes of device memory (0 = shape not covered - B * Lp
+ *   rows of 4 * nhid f32 beyond 31-bit offsets, or d > 1024 in EM_BF16: em_rnn_lm_seq_nll then returns EM_ERR_UNSUPPORTED);
+ *   a smaller one: EM_ERR_WORKSPACE.  Contents of ws on entry: ignored ("Scratch memory" above).                        */
+size_t em_rnn_lm_seq_nll_workspace_bytes(int dtype, const EmLmWeights* lm, int32_t B, int32_t Lp);
+int em_rnn_lm_seq_nll(int dtype, const EmLmWeights* lm, const int32_t* x, const int32_t* target, const int32_t* xlens,
+                      int32_t B, int32_t Lp, float* nll, void* ws, size_t ws_bytes, void* stream);
+/*   em_rnn_lm_seq_nll_parts: the same call restricted to the parts named in `parts` (tools/rnn_lm_nll_bench.py times them one
+ *   by one).  A part reads what the parts before it left in ws, so a restricted call is meaningful only on the workspace of
+ *   an earlier whole call of the same shape; nll is written by the head only.                                             */
+#define EM_RNN_SEQ_HOIST 1 /* embedding + layer 0's input product */
+#define EM_RNN_SEQ_CHAIN 2 /* the step launches */
+#define EM_RNN_SEQ_HEAD 4  /* the vocabulary head */
+int em_rnn_lm_seq_nll_parts(int dtype, const EmLmWeights* lm, const int32_t* x, const int32_t* target, const int32_t* xlens,
+                            int32_t B, int32_t Lp, float* nll, void* ws, size_t ws_bytes, int32_t parts, void* stream);
 
 /* ---- attention decoder over whole transcripts (csrc/dec_seq.hip): ESPnetASRModel.nll (espnet2/asr/espnet_model.py) - the
  *      teacher-forced negative log-likelihood of transcripts given their encoder memories, all M = B * Lp rows of a batch at
