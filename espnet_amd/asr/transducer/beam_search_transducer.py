@@ -19,6 +19,10 @@ Mirrors espnet2/asr/transducer/beam_search_transducer.py (constructor keywords, 
     LM term.  The walk is `em_transducer_beam_search_lm`, the host route calls `em_transducer_lm_step` one row at a
     time (the same kernels, so the same bits) and both add the term in double.  LM fusion exists at the beams the walk
     holds (`beam_limits()["beam"]`); other LMs raise NotImplementedError.
+  * streams: `stream_state` / `extend` - the greedy search RESUMABLE (`em_transducer_greedy_extend`, csrc/
+    transducer_stream.hip): a stream lives in a slot of a state slab and is fed its next frames tick by tick; a round
+    decides all remaining frames of the chunk at once, so a tick costs 1 + (labels emitted) dependent rounds.  beam_size
+    <= 1 only (NotImplementedError above).  Its score sums every frame's log-probability, blanks included.
   * tsd / alsd / nsc / maes and multi-blank models raise NotImplementedError.
 """
 import ctypes as C
@@ -46,6 +50,78 @@ def beam_limits():
     v = [C.c_int32(0) for _ in range(5)]
     L.load().em_transducer_beam_limits(*(C.byref(x) for x in v))
     return dict(zip(("beam", "open", "kept", "expansions", "labels"), (int(x.value) for x in v)))
+
+
+def stream_limits():
+    """`em_transducer_stream_limits`: the resumable greedy walk's capacities - streams per call, new frames per stream
+    and call, labels a slot holds."""
+    v = [C.c_int32(0) for _ in range(3)]
+    L.load().em_transducer_stream_limits(*(C.byref(x) for x in v))
+    return dict(zip(("streams", "frames", "labels"), (int(x.value) for x in v)))
+
+
+class TransducerStreamState:
+    """The PERSISTENT memory of the resumable greedy walk (`em_transducer_greedy_extend`): a slab of `n_slots` slots, one
+    per live stream, their allocator and - on the host - what every slot's stream has emitted so far (`yseq`, `score`,
+    `frames`), kept up by `BeamSearchTransducer.extend`'s read-back.  A slot of zero bytes is a fresh stream: `reset`
+    zeroes slots (enqueue only), `acquire` hands out the lowest free one reset, `release` takes it back.  A slot holds
+    no address, so `grow()` copies the slab into a larger one and every stream keeps its slot number.  Plain Python
+    over one uint8 tensor (which may live on the CPU: the allocator is tested there)."""
+
+    def __init__(self, n_slots: int, slot_bytes: int, device, blank: int = 0):
+        if n_slots < 1 or slot_bytes < 1:
+            raise ValueError("n_slots and slot_bytes must be positive")
+        self.n_slots, self.slot_bytes, self.blank = int(n_slots), int(slot_bytes), int(blank)
+        self.slab = torch.zeros(self.n_slots, self.slot_bytes, dtype=torch.uint8, device=device)
+        self._free = list(range(self.n_slots))  # ascending: the lowest free slot goes first
+        self._used = set()
+        self.yseq = {s: [self.blank] for s in range(self.n_slots)}
+        self.score = {s: 0.0 for s in range(self.n_slots)}
+        self.frames = {s: 0 for s in range(self.n_slots)}
+
+    @property
+    def n_free(self) -> int:
+        return len(self._free)
+
+    @property
+    def live(self):
+        return sorted(self._used)
+
+    def reset(self, slots) -> None:
+        """The slots start new streams: zero bytes on the device, the empty hypothesis on the host."""
+        slots = [int(s) for s in slots]
+        for s in slots:
+            if not 0 <= s < self.n_slots:
+                raise ValueError(f"reset: slot {s} is outside the slab's {self.n_slots} slots")
+            self.yseq[s], self.score[s], self.frames[s] = [self.blank], 0.0, 0
+        if slots:
+            self.slab[torch.tensor(slots, dtype=torch.int64).to(self.slab.device, non_blocking=True)] = 0
+
+    def acquire(self) -> int:
+        if not self._free:
+            self.grow()
+        slot = self._free.pop(0)
+        self._used.add(slot)
+        self.reset([slot])
+        return slot
+
+    def release(self, slot: int) -> None:
+        if slot not in self._used:
+            raise ValueError(f"slot {slot} is not in use")
+        self._used.discard(slot)
+        self._free.append(int(slot))
+        self._free.sort()
+
+    def grow(self, n_slots: Optional[int] = None) -> None:
+        n = 2 * self.n_slots if n_slots is None else int(n_slots)
+        if n <= self.n_slots:
+            raise ValueError(f"grow({n}): the slab holds {self.n_slots} slots already")
+        slab = torch.zeros(n, self.slot_bytes, dtype=torch.uint8, device=self.slab.device)
+        slab[: self.n_slots].copy_(self.slab)
+        for s in range(self.n_slots, n):
+            self.yseq[s], self.score[s], self.frames[s] = [self.blank], 0.0, 0
+        self._free += list(range(self.n_slots, n))
+        self.slab, self.n_slots = slab, n
 
 
 @dataclass
@@ -102,6 +178,7 @@ class BeamSearchTransducer:
         self.last_trace = None
         self.last_beam = None  # beam_device: status rows, steps enqueued / needed
         self.last_routes = None  # search_batch, beam_size > 1: "device" or "host" per utterance
+        self.last_rounds = None  # extend: rounds the last collected tick needed / had enqueued
 
     # ------------------------------------------------------------------ greedy: the fused walk
     @torch.no_grad()
@@ -129,6 +206,99 @@ class BeamSearchTransducer:
                                          L.ptr(tr[1]) if tr else None, L.ptr(tr[2]) if tr else None, L.ptr(ws), int(need),
                                          L.current_stream_ptr()), "em_transducer_greedy")
         return (tokens, ylens, score) + ((tr,) if trace else ())
+
+    # ------------------------------------------------------------------ greedy on streams: the resumable walk
+    def stream_state(self, n_slots: int, device) -> TransducerStreamState:
+        """The state slab of `extend` for this model: `n_slots` fresh slots on `device`."""
+        w, keep = self.decoder.weights(device)
+        nbytes = int(L.load().em_transducer_stream_slot_bytes(self.decoder.em_dtype, C.byref(w)))
+        if nbytes == 0:
+            raise NotImplementedError(f"em_transducer_greedy_extend: joint_space_size={w.joint} is outside the walk's head")
+        return TransducerStreamState(n_slots, nbytes, device, blank=self.blank_id)
+
+    @torch.no_grad()
+    def extend_start(self, state: TransducerStreamState, slots, enc_act: torch.Tensor, nframes, trace: bool = False):
+        """`extend` without the read-back: enqueues lin_enc on the new rows and the tick's rounds and returns what
+        `extend_collect` needs.  Nothing waits for the device."""
+        if self.beam_size > 1:
+            raise NotImplementedError(f"BeamSearchTransducer.extend with beam_size={self.beam_size}: the resumable walk is "
+                                      "the greedy search (beam_size <= 1)")
+        dec, jn = self.decoder, self.joint_network
+        L.require_gpu(enc_act, "enc_act")
+        slots, nframes = [int(s) for s in slots], [int(n) for n in nframes]
+        S, F, D = (int(v) for v in enc_act.shape)
+        lim = stream_limits()
+        if S > lim["streams"] or F > lim["frames"]:
+            raise NotImplementedError(f"BeamSearchTransducer.extend: {S} streams x {F} new frames, one call takes at most "
+                                      f"streams={lim['streams']} and frames={lim['frames']}")
+        if len(slots) != S or len(nframes) != S or len(set(slots)) != S:
+            raise ValueError(f"extend: enc_act has {S} rows; slots and nframes must name {S} distinct slots")
+        if any(not 0 <= s < state.n_slots for s in slots) or any(not 0 <= n <= F for n in nframes):
+            raise ValueError(f"extend: slots outside [0, {state.n_slots}) or nframes outside [0, {F}]")
+        dev = enc_act.device
+        w, keep = dec.weights(dev)
+        lib, stream = L.load(), L.current_stream_ptr()
+        act = enc_act.to(jn.act_dtype).contiguous()
+        pj = jn.packed(dev)
+        enc_proj = torch.empty(S, F, w.jp, dtype=torch.float32, device=dev)
+        L.check(lib.em_transducer_stream_enc_proj(dec.em_dtype, L.ptr(act), C.c_void_p(pj.lin_enc.data_ptr()),
+                                                  C.c_void_p(pj.enc_b.data_ptr()), S * F, D, w.jp, L.ptr(enc_proj), stream),
+                "em_transducer_stream_enc_proj")
+        need = int(lib.em_transducer_greedy_extend_workspace_bytes(dec.em_dtype, C.byref(w), S, F))
+        ws = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
+        words = torch.tensor(slots + nframes, dtype=torch.int32).to(dev, non_blocking=True)
+        # one buffer for everything that travels back: scores (S) f64 | info (S, 5) i32 | labels (S, F) i32
+        out = torch.empty(S * (8 + 4 * (5 + F)), dtype=torch.uint8, device=dev)
+        score, info, labels = out[: 8 * S].view(torch.float64), out[8 * S : 28 * S].view(torch.int32), out[28 * S :].view(torch.int32)
+        tr = None
+        if trace:
+            tr = (torch.full((S, F), -1, dtype=torch.int32, device=dev), torch.zeros(S, F, device=dev),
+                  torch.zeros(S, F, device=dev))
+        L.check(lib.em_transducer_greedy_extend(dec.em_dtype, C.byref(w), L.ptr(state.slab), state.n_slots, L.ptr(words),
+                                                L.ptr(enc_proj), L.ptr(words[S:]), S, F, L.ptr(score), L.ptr(info),
+                                                L.ptr(labels), L.ptr(tr[0]) if tr else None, L.ptr(tr[1]) if tr else None,
+                                                L.ptr(tr[2]) if tr else None, L.ptr(ws), need, stream),
+                "em_transducer_greedy_extend")
+        return dict(state=state, slots=slots, S=S, F=F, out=out, trace=tr, keep=(ws, enc_proj, words, act, keep))
+
+    def extend_collect(self, tick, host: Optional[torch.Tensor] = None) -> List[Hypothesis]:
+        """The read-back of a tick `extend_start` enqueued (`host`: the bytes of `tick["out"]` where the caller copied
+        them already): the new labels join the slots' host lists; returns the hypotheses so far per stream.  A slot whose
+        label list is full raises."""
+        state, S, F = tick["state"], tick["S"], tick["F"]
+        raw = tick["out"].cpu() if host is None else host  # the ONE gathered read-back of the tick
+        score = raw[: 8 * S].view(torch.float64).tolist()
+        info = raw[8 * S : 28 * S].view(torch.int32).view(S, 5).tolist()
+        labels = raw[28 * S :].view(torch.int32).view(S, F).tolist()
+        self.last_rounds = dict(needed=info[0][4], enqueued=F)
+        out, full = [], []
+        for i, slot in enumerate(tick["slots"]):
+            before, after, status, frames, _ = info[i]
+            if len(state.yseq[slot]) - 1 != before:
+                raise RuntimeError(f"extend: slot {slot} holds {before} labels on the device, {len(state.yseq[slot]) - 1} on "
+                                   "the host (ticks of one slot must be collected in order)")
+            state.yseq[slot] = state.yseq[slot] + labels[i][: after - before]
+            state.score[slot], state.frames[slot] = float(score[i]), int(frames)
+            if status != 0:
+                full.append(slot)
+            out.append(Hypothesis(score=state.score[slot], yseq=list(state.yseq[slot])))
+        if full:
+            raise RuntimeError(f"BeamSearchTransducer.extend: the label list of slot(s) {full} is full "
+                               f"(label capacity {stream_limits()['labels']} per stream); the streams stopped there")
+        return out
+
+    def extend(self, state: TransducerStreamState, slots, enc_act: torch.Tensor, nframes, trace: bool = False):
+        """One tick of the resumable greedy walk (`em_transducer_greedy_extend`, csrc/transducer_stream.hip): stream i
+        lives in slot slots[i] of `state` and brings the nframes[i] <= F new encoder frames enc_act[i, :nframes[i]]
+        (enc_act (S, F, D) on the device; 0: it pauses).  Everything is enqueued, then ONE gathered copy brings the new
+        labels and the scores back.  Returns per stream the hypothesis so far, `Hypothesis(score, yseq)` with
+        `yseq[0] == blank`; the score sums the log-probability of every frame's decision, blanks included.  With `trace`
+        also (frame_tok, frame_top, frame_margin) (S, F) host tensors as `greedy_device`'s trace: per new frame the
+        arg-max, its log-prob, the top-1 minus top-2 logit (-1 / 0 / 0 where no frame was consumed).  However the same
+        frames are split into ticks, the slot ends with the same bytes."""
+        tick = self.extend_start(state, slots, enc_act, nframes, trace=trace)
+        hyps = self.extend_collect(tick)
+        return (hyps, tuple(t.cpu() for t in tick["trace"])) if trace else hyps
 
     # ------------------------------------------------------------------ default beam search: the device walk
     @torch.no_grad()

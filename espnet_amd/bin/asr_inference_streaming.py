@@ -61,6 +61,7 @@ class Speech2TextStreaming:
                  normalize_length: bool = False, use_hipgraph: bool = True, search: Optional[str] = None,
                  ngram_file: Union[Path, str, None] = None, ngram_scorer: str = "full", ngram_weight: float = 0.9,
                  tsync_max_frames: int = 1536):
+        search_given = search
         if search is None:
             search = "online" if beam_size > 1 else "greedy"
         if search not in ("online", "greedy", "offline", "tsync"):
@@ -93,6 +94,20 @@ class Speech2TextStreaming:
         if not isinstance(asr_model.encoder, ContextualBlockEncoderBase):
             raise NotImplementedError("Speech2TextStreaming needs encoder: contextual_block_conformer or "
                                       "contextual_block_transformer")
+        self.transducer = None
+        if getattr(asr_model, "use_transducer_decoder", False):
+            # a transducer model streams through the resumable greedy walk (BeamSearchTransducer.extend) and nothing else
+            if search != "greedy":
+                what = f"search={search!r}" if search_given is not None else f"beam_size={beam_size}"
+                raise NotImplementedError(f"{what} with a transducer decoder: a stream is decoded by the resumable greedy walk "
+                                          "only (search='greedy' or beam_size=1)")
+            if lm_train_config is not None:
+                raise NotImplementedError("lm_train_config with a transducer decoder on a stream: the greedy walk does not "
+                                          "use an LM")
+            from espnet_amd.asr.transducer.beam_search_transducer import BeamSearchTransducer
+
+            self.transducer = BeamSearchTransducer(decoder=asr_model.decoder, joint_network=asr_model.joint_network, beam_size=1)
+        self._td_state, self._td_last = None, None
         self.asr_model, self.asr_train_args = asr_model, args
         self.device, self.dtype = device, dtype
         self.maxlenratio, self.minlenratio, self.nbest = maxlenratio, minlenratio, nbest
@@ -155,7 +170,7 @@ class Speech2TextStreaming:
                 weights=dict(ctc=ctc_weight, ngram=ngram_weight if self.ngram is not None else 0.0, length_bonus=penalty))
         m = asr_model
         pack_modules(device, [m.frontend, m.encoder, m.ctc] +
-                     ([] if search == "greedy" else [self.ngram] if search == "tsync" else [m.decoder, lm]))
+                     ([m.decoder, m.joint_network] if self.transducer is not None else [] if search == "greedy" else [self.ngram] if search == "tsync" else [m.decoder, lm]))
         token_type = token_type if token_type is not None else getattr(args, "token_type", None)
         bpemodel = bpemodel if bpemodel is not None else getattr(args, "bpemodel", None)
         self.tokenizer = (None if token_type is None or (token_type == "bpe" and bpemodel is None)
@@ -180,6 +195,9 @@ class Speech2TextStreaming:
         self._last_id = -1
         self._partial_ids: List[int] = []
         self._tsync_started, self._tsync_last = False, None  # (the single stream's slot is reset by its next frames)
+        if self._td_state is not None:  # the single transducer stream starts over
+            self._td_state.reset([0])
+        self._td_last = None
         if self._runner is not None:
             self._runner.reset()
         if self.search == "online" and self.beam_search is not None:
@@ -263,7 +281,9 @@ class Speech2TextStreaming:
         ret = []
         if feats is not None:
             enc = self._encode_chunk(feats[0].contiguous(), is_final)
-            if self.search == "online":  # :323-330
+            if self.transducer is not None:
+                ret = self._transducer_single(enc)
+            elif self.search == "online":  # :323-330
                 nbest_hyps = self.beam_search(x=enc, maxlenratio=self.maxlenratio, minlenratio=self.minlenratio,
                                               is_final=is_final)
                 ret = self.assemble_hyps(nbest_hyps)
@@ -276,9 +296,47 @@ class Speech2TextStreaming:
                 ret = self._results(is_final)
         elif self.search == "tsync":  # (the call only buffered samples: the list so far)
             ret = self.assemble_hyps(self._tsync_single(None))
+        elif self.transducer is not None:
+            ret = self._transducer_single(None)
         if is_final:
             self.reset()
         return ret
+
+    # ------------------------------------------------------------------ transducer models: the resumable greedy walk
+    def _transducer_ticks(self, state, slots, enc, n: int):
+        """The n new encoder frames enc (S, >= n, d) of the streams in `slots` as ticks of at most the walk's frames per
+        call; lin_enc runs on exactly these rows.  Returns the last tick (`BeamSearchTransducer.extend_start`), not yet
+        collected; the ones in front of it - only a chunk longer than one call has them - are collected here."""
+        from espnet_amd.asr.transducer.beam_search_transducer import stream_limits
+
+        bs, step = self.transducer, stream_limits()["frames"]
+        tick = None
+        for t0 in range(0, n, step):
+            if tick is not None:
+                bs.extend_collect(tick)
+            t1 = min(n, t0 + step)
+            tick = bs.extend_start(state, slots, enc[:, t0:t1], [t1 - t0] * len(slots))
+        return tick
+
+    def _transducer_results(self, hyp):
+        token_int = [t for t in hyp.yseq[1:] if t != 0]
+        token = self.converter.ids2tokens(token_int)
+        text = self.tokenizer.tokens2text(token) if self.tokenizer is not None else None
+        return [(text, token, token_int, hyp)]
+
+    def _transducer_single(self, enc):
+        """`__call__`'s step: the new encoder frames enc (T, d) (None or T = 0: none) -> the result so far."""
+        bs = self.transducer
+        if self._td_state is None:
+            self._td_state = bs.stream_state(1, next(self.asr_model.parameters()).device)
+        n = 0 if enc is None else int(enc.size(0))
+        if n > 0:
+            self._td_last = bs.extend_collect(self._transducer_ticks(self._td_state, [0], enc.unsqueeze(0), n))[0]
+        elif self._td_last is None:
+            from espnet_amd.asr.transducer.beam_search_transducer import Hypothesis as TransducerHypothesis
+
+            self._td_last = TransducerHypothesis(score=0.0, yseq=[bs.blank_id])
+        return self._transducer_results(self._td_last)
 
     # ------------------------------------------------------------------ the resumable time-synchronous search
     def _tsync_extend(self, enc, n_new, slots, reset, state, keys):
@@ -363,14 +421,15 @@ class Speech2TextStreaming:
             bst = self._batches[group] = dict(frontend=None, encoder=None, last=[-1] * S, ids=[[] for _ in range(S)], pending=None,
                                               graph=self._tick_graphs.get((group, tuple(speech.shape))))
         m = self.asr_model
-        ids_host, event, collect = None, None, None
+        ids_host, event, collect, td = None, None, None, None
         tsync = self.search == "tsync"
         ctx = torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext()
         with ctx:
             ids = None
             tg = bst.get("graph")
             # (the time-synchronous ticks run as eager launches: their capture is a later step)
-            sig = BatchTickGraph.signature(speech, bst) if (self.use_hipgraph and not is_final and not tsync) else None
+            sig = BatchTickGraph.signature(speech, bst) if (self.use_hipgraph and not is_final and not tsync
+                                                            and self.transducer is None) else None
             if tg is not None and tg.graph is not None and sig is not None and sig == tg.sig:
                 ids = tg.replay(speech, bst)  # steady state: one graph launch
             else:
@@ -380,7 +439,16 @@ class Speech2TextStreaming:
                 feats, bst["frontend"] = self.apply_frontend_batch(speech_dev, bst["frontend"], is_final=is_final)
                 if feats is not None:
                     enc, y_len, bst["encoder"] = m.encoder.forward_infer_batch(feats, bst["encoder"], is_final)  # (a view: the encoder's own cat / contiguous() copies it once)
-                    if y_len > 0 and tsync:  # one state slab per group, slot = row
+                    if y_len > 0 and self.transducer is not None:  # one state slab per group, slot = row
+                        if bst.get("transducer") is None:
+                            bst["transducer"] = self.transducer.stream_state(S, enc.device)
+                        tick = self._transducer_ticks(bst["transducer"], list(range(S)), enc, int(y_len))
+                        host = torch.empty(tick["out"].shape, dtype=torch.uint8, pin_memory=True)
+                        host.copy_(tick["out"], non_blocking=True)  # ONE device -> host read per tick for all streams
+                        event = torch.cuda.Event()
+                        event.record()
+                        td = (tick, host)
+                    elif y_len > 0 and tsync:  # one state slab per group, slot = row
                         bs = self.beam_search_timesync
                         if bst.get("tsync") is None:
                             bst["tsync"] = bs.stream_state(S, self.tsync_max_frames, enc.device)
@@ -403,7 +471,7 @@ class Speech2TextStreaming:
                 ids_host.copy_(ids, non_blocking=True)  # ONE device -> host read per tick for all streams
                 event = torch.cuda.Event()
                 event.record()
-        tick = PendingTick(self, bst, ids_host, event, bst["pending"], collect)
+        tick = PendingTick(self, bst, ids_host, event, bst["pending"], collect, td)
         bst["pending"] = tick
         if is_final:
             tg = bst.get("graph")
@@ -541,8 +609,9 @@ class PendingTick:
     """A tick of `Speech2TextStreaming.batch_call_async` whose launches are queued: `result()` waits for its token ids and
     returns, per stream, the ids decoded so far."""
 
-    def __init__(self, s2t, bst, ids_host, event, prev, collect=None):
+    def __init__(self, s2t, bst, ids_host, event, prev, collect=None, transducer=None):
         self._s2t, self._bst, self._ids_host, self._event, self._prev = s2t, bst, ids_host, event, prev
+        self._td = transducer  # a transducer model: (the tick `extend_start` enqueued, the pinned copy of its outputs)
         self._collect = collect  # search="tsync": the queued copy of the tick's n-best lists
         self._res = None
         self.nbest = None  # search="tsync", after result(): per stream the n-best list so far (Hypothesis: score, scores)
@@ -564,6 +633,12 @@ class PendingTick:
                 for s_, row in enumerate(self._ids_host.tolist()):
                     bst["last"][s_] = _collapse_greedy(row, bst["last"][s_], bst["ids"][s_], drop)
                 self._ids_host = None
+            if self._td is not None:  # the hypotheses so far, labels appended by `extend_collect`
+                self._event.synchronize()
+                hyps = self._s2t.transducer.extend_collect(*self._td)
+                bst["nbest"] = [[h] for h in hyps]
+                bst["ids"] = [[t for t in h.yseq[1:] if t != 0] for h in hyps]
+                self._td = None
             if self._collect is not None:  # the lists so far REPLACE the last tick's
                 bst["nbest"] = self._collect.result()
                 bst["ids"] = [[t for t in hyps[0].yseq[1:-1].tolist() if t != 0] if hyps else [] for hyps in bst["nbest"]]
@@ -600,6 +675,8 @@ class StreamPool:
         # tick.  `nbest_last_tick`: {stream id: the n-best list so far} of the last tick's active streams.
         self.tsync_state = None
         self.nbest_last_tick = {}
+        # a transducer model: ONE slab of the resumable greedy walk for the pool, slots held as with search="tsync"
+        self.transducer_state = None
 
     @staticmethod
     def _shape(t):
@@ -654,6 +731,9 @@ class StreamPool:
         dev = next(m.parameters()).device
         if tsync and self.tsync_state is None:
             self.tsync_state = s2t.beam_search_timesync.stream_state(4, s2t.tsync_max_frames, dev)
+        td = s2t.transducer
+        if td is not None and self.transducer_state is None:
+            self.transducer_state = td.stream_state(4, dev)
         groups = {}
         for sid, (speech, is_final) in chunks.items():
             if isinstance(speech, np.ndarray):
@@ -663,6 +743,8 @@ class StreamPool:
                 st = self.streams[sid] = dict(frontend=None, encoder=None, last=-1, ids=[])
                 if tsync:  # the stream joins: a slot of its own, reset by its first frames
                     st.update(slot=self.tsync_state.acquire(), started=False, nbest=None)
+                if td is not None:  # the stream joins: a fresh slot of its own
+                    st.update(slot=self.transducer_state.acquire(), nbest=None)
             groups.setdefault(self._signature(st, speech.numel(), is_final), []).append((sid, speech))
         self.groups_last_tick = len(groups)
         drop = (m.blank_id, m.sos, m.eos)
@@ -678,7 +760,11 @@ class StreamPool:
                 if en is not None and isinstance(en["n_processed_blocks"], list) and len(set(en["n_processed_blocks"])) == 1:
                     en["n_processed_blocks"] = en["n_processed_blocks"][0]
                 enc, y_len, en_next = m.encoder.forward_infer_batch(feats.contiguous(), en, is_final)
-                if y_len > 0 and tsync:  # one `extend` on the rows' slots; one device -> host read per group and tick
+                if y_len > 0 and td is not None:  # one walk on the rows' slots; one device -> host read per group and tick
+                    tk = s2t._transducer_ticks(self.transducer_state, [st["slot"] for st in sts], enc, int(y_len))
+                    for st, hyp in zip(sts, td.extend_collect(tk)):
+                        st["nbest"], st["ids"] = [hyp], [t for t in hyp.yseq[1:] if t != 0]
+                elif y_len > 0 and tsync:  # one `extend` on the rows' slots; one device -> host read per group and tick
                     bs = s2t.beam_search_timesync
                     tk = s2t._tsync_extend(enc, [y_len] * len(sts), [st["slot"] for st in sts],
                                            [not st["started"] for st in sts], self.tsync_state, [sid for sid, _ in members])
@@ -696,12 +782,14 @@ class StreamPool:
                 if ids is not None:
                     st["last"] = _collapse_greedy(ids[i], st["last"], st["ids"], drop)
         res = {sid: list(self.streams[sid]["ids"]) for sid in chunks}
-        if tsync:
+        if tsync or td is not None:
             self.nbest_last_tick = {sid: self.streams[sid]["nbest"] for sid in chunks}
         for sid, (_, is_final) in chunks.items():
             if is_final:
                 if tsync:  # the stream leaves: its slot is free for the next one
                     self.tsync_state.release(self.streams[sid]["slot"])
+                if td is not None:
+                    self.transducer_state.release(self.streams[sid]["slot"])
                 del self.streams[sid]
         return res
 

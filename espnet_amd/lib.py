@@ -454,6 +454,12 @@ _SIGNATURES = {
     "em_transducer_beam_workspace_bytes_lm": (_sz, [C.c_int, C.POINTER(EmTransducerWeights),
                                                     C.POINTER(EmTransducerLmWeights), _i32, _i32, _i32]),
     "em_transducer_beam_limits": (None, [_vp, _vp, _vp, _vp, _vp]),
+    "em_transducer_stream_slot_bytes": (_sz, [C.c_int, C.POINTER(EmTransducerWeights)]),
+    "em_transducer_stream_limits": (None, [_vp, _vp, _vp]),
+    "em_transducer_stream_enc_proj": (C.c_int, [C.c_int, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp]),
+    "em_transducer_greedy_extend_workspace_bytes": (_sz, [C.c_int, C.POINTER(EmTransducerWeights), _i32, _i32]),
+    "em_transducer_greedy_extend": (C.c_int, [C.c_int, C.POINTER(EmTransducerWeights), _vp, _i32, _vp, _vp, _vp, _i32, _i32,
+                                              _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "em_transducer_lattice_logp": (C.c_int, [C.c_int, C.POINTER(EmTransducerWeights), _vp, _vp, _i32, _i32, _vp, _vp, _i32,
                                              _vp, _vp, _i32, _vp, _vp, _sz, _vp]),
     "em_transducer_lattice_logp_workspace_bytes": (_sz, [C.c_int, C.POINTER(EmTransducerWeights), _i32, _i32, _i32]),

@@ -1576,6 +1576,54 @@ size_t em_transducer_beam_workspace_bytes_lm(int dtype, const EmTransducerWeight
 void em_transducer_beam_limits(int32_t* beam_max, int32_t* open_max, int32_t* kept_max, int32_t* expansions_max,
                                int32_t* labels_max);
 
+/* ---- transducer on streams (csrc/transducer_stream.hip): the greedy search above, RESUMABLE.  A stream lives in one slot
+ *      of a state slab; a call (a tick) feeds stream s - the one in slot slot_ids[s] - its next nframes[s] encoder frames
+ *      and returns the labels they added and the score so far.  Greedy decisions do not need to move frame by frame: while
+ *      a hypothesis emits blanks its prediction network stands still, so a round decides ALL remaining frames of the chunk
+ *      against the current state in one launch, commits the frames up to and including the first label, advances the
+ *      prediction network once and redoes the rest.  F rounds are enqueued; behind the last needed one every launch
+ *      returns at once (device counters, no read-back).
+ *   State slab: n_slots slots of em_transducer_stream_slot_bytes(dtype, w) bytes each (0 for refused weights; a multiple
+ *      of 256).  The slab is PERSISTENT, the caller keeps it between calls - it is not scratch.  A slot holds: a 32-byte
+ *      header (f64 score; i32 frames, labels, status, started), the lin_dec row [jp] f32, the master states [layers][d]
+ *      f32, the hidden states [layers][d] act, the label list (em_transducer_stream_limits: labels_max entries).  A slot
+ *      of ZERO BYTES is a fresh stream: its first call runs the prediction network on the blank from the zero state, as
+ *      the one-shot walk begins.  A slot holds no address and no slot index: it may be copied or moved between calls.
+ *   em_transducer_greedy_extend.  slot_ids [S]: DISTINCT slots in [0, n_slots) - the caller's duty; enc_proj [S][F][jp]
+ *      f32, the caller's product on the NEW frames (see "transducer decoding"), row s's at [s][0 .. nframes[s]);
+ *      nframes [S] is clamped to [0, F] (0: the stream pauses this tick).  Per frame the arg-max of the joint log-softmax
+ *      (lowest id on exact ties), at most one label per frame, as em_transducer_greedy decides; the slot's score is the sum,
+ *      in frame order and in double, of the log-probability of EVERY frame's decision, blanks included (the one-shot
+ *      walk's score holds the labels' terms only).  The head's reduction order is its own: the bits are not those of
+ *      em_transducer_greedy, the decisions agree wherever the top-1 / top-2 margin exceeds the rounding of either.
+ *      The defining property: a row's result depends on its own slot, its own frames and the weights only - not on S, F,
+ *      the other rows, or how the frames were split into calls: any chunking of the same frames leaves the same bytes
+ *      in the slot.
+ *      Outputs, all whole on every call: out_score [S] f64; out_info [S][5] i32 = labels before the call, labels after,
+ *      status, frames so far, rounds the tick needed (the same number in every row, at least 1); out_labels [S][F] the
+ *      labels this call added, -1 behind them.  status: 0; 1 = the label list is full (labels_max): the stream stopped in
+ *      front of the frame of the label that does not fit, consumes nothing further and never writes past its slot; 3 =
+ *      slot_ids[s] outside [0, n_slots): nothing touched.  Optional trace (frame_tok NULL: none, else all three), written
+ *      at the frames a call consumed only: frame_tok [S][F] the arg-max, frame_top its log-probability, frame_margin the
+ *      top-1 minus top-2 logit.
+ *      S <= S_max, F <= F_max of em_transducer_stream_limits and jp <= 1024 (bf16: the head's 64 rows in LDS):
+ *      EM_ERR_UNSUPPORTED beyond, and the workspace size is 0.  ws: em_transducer_greedy_extend_workspace_bytes(dtype, w,
+ *      S, F) bytes of device memory, a smaller one: EM_ERR_WORKSPACE; its contents on entry are ignored.  Enqueue only.
+ *      (tests/test_gpu_transducer_stream.py)
+ *   em_transducer_stream_enc_proj.  enc_proj [M][jp] f32 = enc [M][D] act . lin_enc [jp][D] act ^T + enc_b [jp], the
+ *      product em_transducer_greedy_extend reads, for the M new rows of a tick.  em_gemm chooses its kernel, and with it
+ *      the order of a row's sum, by M; here a row's bits do not depend on M, which the defining property above needs.
+ *      D and jp multiples of 64, M <= S_max * F_max: EM_ERR_UNSUPPORTED otherwise.                                      */
+int em_transducer_stream_enc_proj(int dtype, const void* enc, const void* lin_enc, const float* enc_b, int32_t M, int32_t D,
+                                  int32_t jp, float* enc_proj, void* stream);
+size_t em_transducer_stream_slot_bytes(int dtype, const EmTransducerWeights* w);
+void em_transducer_stream_limits(int32_t* S_max, int32_t* F_max, int32_t* labels_max);
+size_t em_transducer_greedy_extend_workspace_bytes(int dtype, const EmTransducerWeights* w, int32_t S, int32_t F);
+int em_transducer_greedy_extend(int dtype, const EmTransducerWeights* w, void* slab, int32_t n_slots, const int32_t* slot_ids,
+                                const float* enc_proj, const int32_t* nframes, int32_t S, int32_t F, double* out_score,
+                                int32_t* out_info, int32_t* out_labels, int32_t* frame_tok, float* frame_top,
+                                float* frame_margin, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- transducer likelihood of given transcripts (csrc/transducer_nll.hip): log p(y | x) of a ragged batch of N candidate
  *      transcripts, the forward value of the RNN-T loss (espnet2/asr/espnet_model.py `_calc_transducer_loss`), in two
  *      calls: the joint network's two wanted log-probabilities at every lattice node, then the forward (sum-product)
