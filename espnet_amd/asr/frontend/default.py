@@ -1,4 +1,5 @@
-"""DefaultFrontend: STFT -> power -> log-mel on the MI355X (csrc/frontend.hip).
+"""DefaultFrontend: STFT -> power -> log-mel on the MI355X (csrc/frontend.hip for n_fft = 512, the mixed-radix kernel
+of csrc/frontend_mr.hip for the other sizes it takes).
 
 Mirrors espnet2/asr/frontend/default.py:17-131 (constructor arguments, `output_size()`,
 `forward(input, input_lengths) -> (feats, feats_lens)`) for the single-channel path without
@@ -11,6 +12,7 @@ import torch
 
 from espnet_amd import lib as L
 from espnet_amd.layers.log_mel import LogMel, pack_banded
+from espnet_amd.layers.stft_plan import N_FFT_RULE, radix_plan, twiddle_table
 from espnet_amd.nets_utils import stft_frame_lengths
 from espnet_amd.packing import PackedModule
 
@@ -33,9 +35,10 @@ class DefaultFrontend(PackedModule):
                  frontend_conf: Optional[dict] = None, apply_stft: bool = True):
         super().__init__()
         fs = _parse_fs(fs)
-        if n_fft != 512 or not center or normalized or not onesided or not apply_stft:
-            raise NotImplementedError(
-                "MI355X frontend fast path: n_fft=512, center=True, normalized=False, onesided=True")
+        if radix_plan(n_fft) is None:
+            raise NotImplementedError(f"MI355X frontend fast path: n_fft={n_fft} is not a size it takes ({N_FFT_RULE})")
+        if not center or normalized or not onesided or not apply_stft:
+            raise NotImplementedError("MI355X frontend fast path: center=True, normalized=False, onesided=True")
         if frontend_conf is not None:
             raise NotImplementedError("WPE/beamformer frontend_conf is outside the MI355X fast path")
         if window not in ("hann", None):
@@ -66,6 +69,8 @@ class DefaultFrontend(PackedModule):
     def _build_pack(self, pk):
         packed, lo, maxlen = pack_banded(self.logmel.melmat)
         pk.window, pk.mel, pk.lo, pk.maxlen = pk.hold(self._window_padded()), pk.hold(packed), pk.hold(lo), maxlen
+        # the 512 kernels carry their twiddles; every other size reads the table of its radix plan
+        pk.plan = None if self.n_fft == 512 else pk.hold(torch.from_numpy(twiddle_table(self.n_fft)))
 
     # ---- forward --------------------------------------------------------------------------------
     def feature_lengths(self, input_lengths) -> list:
@@ -83,10 +88,16 @@ class DefaultFrontend(PackedModule):
             raise ValueError(f"input of {N} samples is too short for reflect padding of {self.n_fft // 2}")
         T_f = 1 + N // self.hop_length
         feats = torch.empty(B, T_f, self.n_mels, dtype=torch.float32, device=speech.device)
-        L.check(L.load().em_frontend_logmel_f32(
-            L.ptr(speech), B, N, self.hop_length, L.ptr(pk.window), L.ptr(pk.mel),
-            L.ptr(pk.lo), pk.maxlen, self.n_mels, L.ptr(flens_dev), L.ptr(wlens_dev), T_f,
-            L.ptr(feats), L.current_stream_ptr()), "em_frontend_logmel_f32")
+        if self.n_fft == 512:
+            L.check(L.load().em_frontend_logmel_f32(
+                L.ptr(speech), B, N, self.hop_length, L.ptr(pk.window), L.ptr(pk.mel),
+                L.ptr(pk.lo), pk.maxlen, self.n_mels, L.ptr(flens_dev), L.ptr(wlens_dev), T_f,
+                L.ptr(feats), L.current_stream_ptr()), "em_frontend_logmel_f32")
+        else:
+            L.check(L.load().em_frontend_logmel_nfft_f32(
+                L.ptr(speech), B, N, self.n_fft, self.hop_length, L.ptr(pk.window), L.ptr(pk.plan), L.ptr(pk.mel),
+                L.ptr(pk.lo), pk.maxlen, self.n_mels, L.ptr(flens_dev), L.ptr(wlens_dev), T_f,
+                L.ptr(feats), L.current_stream_ptr()), "em_frontend_logmel_nfft_f32")
         return feats
 
     def forward(self, input: torch.Tensor, input_lengths: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:

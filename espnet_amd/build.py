@@ -25,10 +25,11 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc",
 # ngram_seq.hip: its values must match the step scorer's single f32 adds bit for bit; no packed-f32 VALU forms there.
 # rnn_lm_seq.hip: the cells' f32 arithmetic is that of the step kernels, one scalar operation at a time.
 # transducer_stream.hip: the records' merges must give one result per row whatever the tile; scalar f32 forms only.
+# frontend_mr.hip: the butterflies' complex arithmetic as scalar f32 operations, one rounding each.
 _NO_PACKED_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 EXTRA_FLAGS = {"block.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
                "ngram_seq.hip": _NO_PACKED_F32, "rnn_lm_seq.hip": _NO_PACKED_F32,
-               "transducer_stream.hip": _NO_PACKED_F32}
+               "transducer_stream.hip": _NO_PACKED_F32, "frontend_mr.hip": _NO_PACKED_F32}
 
 
 def _sources():

@@ -277,6 +277,9 @@ _SIGNATURES = {
     "em_error_string": (C.c_char_p, [C.c_int]),
     "em_frontend_logmel_f32": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _vp, _vp,
                                          _i32, _vp, _vp]),
+    "em_frontend_logmel_nfft_f32": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp,
+                                              _i32, _vp, _vp]),
+    "em_stft_radix_plan": (C.c_int, [_i32, C.POINTER(C.c_int32)]),
     "em_utt_mvn_partial_f32": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _vp]),
     "em_utt_mvn_apply_f32": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _vp]),
     "em_global_mvn_f32": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),

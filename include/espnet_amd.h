@@ -134,6 +134,24 @@ int em_frontend_logmel_f32(const float* wav, int32_t B, int32_t N, int32_t hop, 
                            int32_t n_mels, const int32_t* flens, const int32_t* wlens, int32_t T_f,
                            float* feats, void* stream);
 
+/*   The same for a general STFT size (csrc/frontend_mr.hip, a mixed-radix Stockham FFT over radices 4, 2, 3, 5):
+ *   n_fft even, 64 <= n_fft <= 1024, n_fft / 2 = 2^a 3^b 5^c; EM_ERR_UNSUPPORTED otherwise.  512 is taken too (a second
+ *   route for A/B runs: close to em_frontend_logmel_f32, not its bits).  Arguments as above with
+ *   window     [n_fft] f32
+ *   twiddles   [2 H + 1][2] f32 (re, im), H = n_fft / 2: the table of espnet_amd/layers/stft_plan.py - stage s of the radix
+ *              plan (radix r, p = product of the radices before it) at entry p - 1 as [q - 1][k] = W_{rp}^{kq}, then
+ *              W_{n_fft}^k for k = 0 .. H at entry H
+ *   mel_packed rows of n_fft / 2 + 1 bins: 1 <= mel_maxlen <= H + 1
+ *   N > H, T_f = 1 + N / hop                                                                      */
+int em_frontend_logmel_nfft_f32(const float* wav, int32_t B, int32_t N, int32_t n_fft, int32_t hop,
+                                const float* window, const float* twiddles, const float* mel_packed,
+                                const int32_t* mel_lo, int32_t mel_maxlen, int32_t n_mels,
+                                const int32_t* flens, const int32_t* wlens, int32_t T_f, float* feats,
+                                void* stream);
+/*   Its radix plan (host only, no GPU): the radices of n_fft / 2 in stage order - 4s, one 2, 3s, 5s - into radix[0 .. 6);
+ *   returns the number of stages (at most 6: n_fft 972), 0 for a size the kernel does not take.                    */
+int em_stft_radix_plan(int32_t n_fft, int32_t* radix);
+
 /* ---- A3: utterance_mvn (espnet2/layers/utterance_mvn.py:45-88), first half: per-utterance
  *      partial column sums over the valid frames.  partial [B][8][n_mels] f32 out.  The mean
  *      subtraction itself is fused into em_conv2d_sub1 (padded frames become -mean, :73).       */
