@@ -352,6 +352,10 @@ class Speech2Text:
             results.append(row_result([c[b] for c in parts[:n_out]], y, self.converter.ids2tokens(y), st.olens[b], spf))
         return results
 
+    def _need_ctc_head(self):
+        if self.asr_model.ctc is None:
+            raise ValueError("forced alignment needs a CTC head (the model has ctc_weight == 0)")
+
     @torch.no_grad()
     def align(self, speech: Union[torch.Tensor, np.ndarray], text=None):
         """Token timestamps of one utterance: `batch_align` for a batch of one."""
@@ -370,8 +374,7 @@ class Speech2Text:
         per batch (texts=None beyond `align_no_sync_frames` encoder frames: one more word, the longest hypothesis' length,
         is read first)."""
         m = self.asr_model
-        if m.ctc is None:
-            raise ValueError("forced alignment needs a CTC head (the model has ctc_weight == 0)")
+        self._need_ctc_head()
 
         def hypothesis(st):
             return (*m.greedy_ctc_device(st)[1:], self.align_no_sync_frames)
@@ -478,13 +481,14 @@ class Speech2Text:
             V = min(V, getattr(self.lm_model.lm, "vocab_size", V))
         return CandidateBatch(texts, int(speech.shape[0]), self._target_ids, V)
 
-    def _enqueue_candidates(self, speech, speech_lengths, cb: CandidateBatch, score, min_width: int = 1) -> torch.Tensor:
+    def _enqueue_candidates(self, speech, speech_lengths, cb: CandidateBatch, score, min_width: int = 1, st=None) -> torch.Tensor:
         """The shared driver of the `batch_*` scorers up to their one D2H copy: encodes the utterances once (as
         `batch_decode` does) and runs the candidates through score(st, olens, sl) in slices of `nll_rows_per_call` - st
         the EncoderState, olens its (B,) int32 host lengths, sl a `CandidateSlice`.  Returns the slices' device tensors
-        concatenated; only enqueues."""
-        speech = speech.to(self.device, torch.float32, non_blocking=True)
-        st = self.asr_model.encode_device(speech, [int(n) for n in speech_lengths], isolate=True)
+        concatenated; only enqueues.  `st`: the batch already encoded."""
+        if st is None:
+            speech = speech.to(self.device, torch.float32, non_blocking=True)
+            st = self.asr_model.encode_device(speech, [int(n) for n in speech_lengths], isolate=True)
         olens = torch.tensor(st.olens, dtype=torch.int32)
         return torch.cat([score(st, olens, sl) for sl in cb.slices(self.nll_rows_per_call, min_width)])
 
@@ -591,6 +595,46 @@ class Speech2Text:
         if "length_bonus" in keys:
             col["length_bonus"] = torch.tensor([n + 1.0 for n in sl.ylens], dtype=torch.float32).to(dev, non_blocking=True)
         return torch.stack([col[k] for k in keys], dim=1)
+
+    # ------------------------------------------------------------------ token confidences under the CTC head
+    @torch.no_grad()
+    def batch_confidence(self, speech: torch.Tensor, speech_lengths: Sequence[int], texts=None):
+        """How sure the CTC head is of every token of given transcripts: the forward-backward posteriors of
+        `CTC.posteriors_device` (csrc/ctc_post.hip), all paths of the transcript, where `batch_align` sees the best one.
+        speech, speech_lengths and texts as `batch_nll` takes them - texts[b] one transcript or an n-best list of utterance
+        b, strings or token ids; texts=None scores every utterance's own greedy CTC tokens (one small D2H copy brings
+        them to the host first).  Returns one list per utterance with a tuple per candidate, in the caller's order:
+        (tokens, confidence, occupancy, peak_frame_seconds, nll) - the ids; per token the largest occupancy of its state
+        over the frames, the expected number of its frames and the time of the most occupied frame (frame index x
+        `seconds_per_frame`, -1.0 where there is none); -log p_ctc(y|x), inf for a transcript the frames cannot carry
+        (its confidences and occupancies are 0).  Needs only frontend, encoder and CTC head.  The candidates go through
+        in slices of `nll_rows_per_call` and share their utterance's log-probabilities; one D2H copy for the results."""
+        m = self.asr_model
+        self._need_ctc_head()
+        cb = None if texts is None else self._candidates(speech, texts)
+        speech = speech.to(self.device, torch.float32, non_blocking=True)
+        st = m.encode_device(speech, [int(n) for n in speech_lengths], isolate=True)
+        if cb is None:
+            _, tokens, tlens = m.greedy_ctc_device(st)
+            own = torch.cat([tlens[:, None], tokens], dim=1).cpu().tolist()
+            cb = CandidateBatch([row[1 : 1 + row[0]] for row in own], len(own), list)
+        if not len(cb):
+            return cb.regroup([])
+        W = max(cb.ylens)
+
+        def score(st, olens, sl):
+            nll, occ, peak, peak_t = m.ctc.posteriors_device(st.enc_act[sl.u0 : sl.u1].contiguous(), st.olens[sl.u0 : sl.u1],
+                                                             sl.ids, sl.ylens, m.blank_id, mem_of=sl.mem_rel)
+            cols = [torch.nn.functional.pad(c.to(torch.float32), (0, W - c.shape[1])) for c in (peak, occ, peak_t)]
+            return torch.cat([nll[:, None]] + cols, dim=1)
+
+        host = self._enqueue_candidates(speech, speech_lengths, cb, score, st=st).cpu().numpy()
+        spf, res = self.seconds_per_frame, []
+        for y, row in zip(cb.ids, host):
+            n = len(y)
+            peak, occ, pt = row[1 : 1 + n], row[1 + W : 1 + W + n], row[1 + 2 * W : 1 + 2 * W + n]
+            res.append((y, peak.tolist(), occ.tolist(), [float(t) * spf if t >= 0 else -1.0 for t in pt], float(row[0])))
+        return cb.regroup(res)
 
     # ------------------------------------------------------------------ the n-gram's score of given transcripts
     @torch.no_grad()

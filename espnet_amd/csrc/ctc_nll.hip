@@ -26,9 +26,11 @@
 
 namespace {
 
+using ctc_trellis::lse2;
+using ctc_trellis::lse3;
 using ctc_trellis::NINF;
-constexpr float CN_LOG2E = 1.44269504088896340736f;
-constexpr float CN_LN2 = 0.69314718055994530942f;
+constexpr float CN_LOG2E = ctc_trellis::LOG2E;
+constexpr float CN_LN2 = ctc_trellis::LN2;
 
 struct NllArgs {
   const float* lpT;
@@ -36,20 +38,6 @@ struct NllArgs {
   int32_t ldT, Lmax, T, Bm, blank, vec;
   float* nll;
 };
-
-// log2(2^a + 2^b) and log2(2^a + 2^b + 2^c); -inf terms (all of them too) give -inf, never NaN
-__device__ __forceinline__ float lse2(float a, float b) {
-  const float hi = fmaxf(a, b), lo = fminf(a, b);
-  const float s = 1.f + __builtin_amdgcn_exp2f(lo - fmaxf(hi, -FLT_MAX));
-  return hi + __builtin_amdgcn_logf(s);
-}
-__device__ __forceinline__ float lse3(float a, float b, float c) {
-  const float hi = __builtin_fmaxf(__builtin_fmaxf(a, b), c), lo = __builtin_fminf(__builtin_fminf(a, b), c);
-  const float mid = __builtin_amdgcn_fmed3f(a, b, c);
-  const float sh = fmaxf(hi, -FLT_MAX);
-  const float s = (1.f + __builtin_amdgcn_exp2f(mid - sh)) + __builtin_amdgcn_exp2f(lo - sh);
-  return hi + __builtin_amdgcn_logf(s);
-}
 
 // the sum-product cell in the base-2 logarithm; nothing is kept per frame
 struct SumCell {

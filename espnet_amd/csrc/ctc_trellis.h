@@ -21,6 +21,8 @@
 //                                                                   -inf where the move by two states is not allowed;
 //   void frame(int t)                                               once per thread and frame t >= 1, behind its 8 cells.
 #pragma once
+#include <cfloat>
+
 #include "em_common.h"
 
 namespace ctc_trellis {
@@ -31,6 +33,24 @@ constexpr int MAX_L = (MAX_WAVES * 64 * SPL - 1) / 2;   // 4 095 tokens (S = 8 1
 constexpr float NINF = -INFINITY;
 
 static inline int waves(int Lmax) { return em_cdiv(2 * Lmax + 1, 64 * SPL); }
+
+// The log-add of the sum-product cells (ctc_nll.hip, ctc_post.hip), in the base-2 logarithm: log2(2^a + 2^b) and
+// log2(2^a + 2^b + 2^c); -inf terms (all of them too) give -inf, never NaN.  An emission enters such a trellis times
+// LOG2E, a result leaves it times LN2.
+constexpr float LOG2E = 1.44269504088896340736f;
+constexpr float LN2 = 0.69314718055994530942f;
+__device__ __forceinline__ float lse2(float a, float b) {
+  const float hi = fmaxf(a, b), lo = fminf(a, b);
+  const float s = 1.f + __builtin_amdgcn_exp2f(lo - fmaxf(hi, -FLT_MAX));
+  return hi + __builtin_amdgcn_logf(s);
+}
+__device__ __forceinline__ float lse3(float a, float b, float c) {
+  const float hi = __builtin_fmaxf(__builtin_fmaxf(a, b), c), lo = __builtin_fminf(__builtin_fminf(a, b), c);
+  const float mid = __builtin_amdgcn_fmed3f(a, b, c);
+  const float sh = fmaxf(hi, -FLT_MAX);
+  const float s = (1.f + __builtin_amdgcn_exp2f(mid - sh)) + __builtin_amdgcn_exp2f(lo - sh);
+  return hi + __builtin_amdgcn_logf(s);
+}
 
 // four consecutive columns c0 .. c0 + 3 of one lpT row
 __device__ __forceinline__ f32x4 load4(const float* row, long c0, bool vec, long ldT) {
@@ -142,6 +162,101 @@ __device__ __forceinline__ void forward(const float* lpT, long ldT, long colb, b
       if (s == S - 1) fin[0] = al[j];
       if (s == S - 2) fin[1] = al[j];
     }
+  }
+  group_sync<MULTI>();
+}
+
+// The same walk from right to left: beta over the frames Tb - 1 .. 0, beta[t][s] = cell(beta[t+1][s], beta[t+1][s+1],
+// beta[t+1][s+2]) with the frame's own emission inside, the move by two only from a token to a DIFFERENT next token.
+// It starts from a frame Tb that holds 0 in state S - 1 and -inf elsewhere, so that EVERY frame passes through the
+// cell (frame Tb - 1 comes out as the two emissions, exactly: the cell adds them to log(1)) and cell.frame(t) is called
+// for every t.  Of its neighbours a thread needs beta[8 i + 8] and beta[8 i + 9]: two lane shifts (DPP wave_shl:1) per
+// frame and, across waves, two LDS words behind the same one barrier per frame; it runs as many barriers as forward
+// does over the same Tb, so a wave group walking down may share a workgroup with one walking up.  Tb > 0.
+template <bool MULTI, class Cell>
+__device__ __forceinline__ void backward(const float* lpT, long ldT, long colb, bool vec, const int32_t* y, int L, int Tb,
+                                         int blank, float (*xch)[MAX_WAVES][2], Cell& cell) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nwaves = blockDim.x >> 6;
+  const int S = 2 * L + 1;
+
+  group_sync<MULTI>();
+
+  float be[SPL];
+#pragma unroll
+  for (int j = 0; j < SPL; ++j) be[j] = SPL * tid + j == S - 1 ? 0.f : NINF;
+  const float* rows[4];
+  float cap[4];  // +inf where the move by two states is allowed, -inf where not
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const int i = 4 * tid + q;
+    const int lab = i < L ? y[i] : blank;
+    rows[q] = lpT + (size_t)lab * ldT;
+    cap[q] = (i + 1 < L && y[i + 1] != lab) ? INFINITY : NINF;
+  }
+  const float* rowb = lpT + (size_t)blank * ldT;
+  const long col0 = vec ? (colb & ~3L) : colb;
+  const int off = (int)(colb - col0);
+  const int NG = (off + Tb + 3) >> 2;
+
+  f32x4 cur[5], nxt[5];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) cur[q] = Cell::prepare(load4(rows[q], col0 + 4L * (NG - 1), vec, ldT));
+  cur[4] = Cell::prepare(load4(rowb, col0 + 4L * (NG - 1), vec, ldT));
+#pragma unroll
+  for (int q = 0; q < 5; ++q) nxt[q] = cur[q];
+  for (int k = NG - 1; k >= 0; --k) {
+    if (k > 0) {
+      const long c = col0 + 4L * (k - 1);
+#pragma unroll
+      for (int q = 0; q < 4; ++q) nxt[q] = Cell::prepare(load4(rows[q], c, vec, ldT));
+      nxt[4] = Cell::prepare(load4(rowb, c, vec, ldT));
+    }
+#pragma unroll
+    for (int i = 3; i >= 0; --i) {
+      const int t = 4 * k + i - off;
+      if (t < 0 || t >= Tb) continue;  // the same in every thread of the workgroup
+      const float eb = cur[4][i];
+      // beta[t+1] of the two states above this thread's run
+      float n0, n1;
+      if (t == Tb - 1) {
+        n0 = SPL * tid + SPL == S - 1 ? 0.f : NINF;
+        n1 = NINF;
+      } else {
+        n0 = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, NINF), __builtin_bit_cast(int, be[0]),
+                                                                   0x130, 0xf, 0xf, false));  // wave_shl:1; lane 63 keeps -inf
+        n1 = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, NINF), __builtin_bit_cast(int, be[1]),
+                                                                   0x130, 0xf, 0xf, false));
+        if (MULTI) {
+          if (lane == 63 && wave + 1 < nwaves) {
+            n0 = xch[(t + 1) & 1][wave + 1][0];
+            n1 = xch[(t + 1) & 1][wave + 1][1];
+          }
+        }
+      }
+      float nw[SPL];
+#pragma unroll
+      for (int j = 0; j < SPL; ++j) {
+        const float one = j == SPL - 1 ? n0 : be[j + 1];
+        if (j & 1) {
+          const float two = fminf(j == SPL - 1 ? n1 : be[j + 2], cap[j >> 1]);
+          nw[j] = cell.token(j, be[j], one, two, cur[j >> 1][i]);
+        } else {
+          nw[j] = cell.blank(j, be[j], one, eb);
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < SPL; ++j) be[j] = nw[j];
+      cell.frame(t);
+      if (MULTI) {
+        if (lane == 0) {
+          xch[t & 1][wave][0] = be[0];
+          xch[t & 1][wave][1] = be[1];
+        }
+        __syncthreads();
+      }
+    }
+#pragma unroll
+    for (int q = 0; q < 5; ++q) cur[q] = nxt[q];
   }
   group_sync<MULTI>();
 }

@@ -1383,6 +1383,35 @@ int em_ctc_seq_nll(const float* lpT, int32_t ldT, const int32_t* xlens, int32_t 
                    int32_t Lmax, const int32_t* ylens, const int32_t* mem_of, int32_t N, int32_t blank, float* nll,
                    void* stream);
 
+/* ---- CTC token posteriors (csrc/ctc_post.hip): the forward-backward (sum-product) state occupancies of given transcripts,
+ *      reduced per token, for a ragged batch of N candidate transcripts in one launch.  lpT, ldT, xlens, Bm, T, targets,
+ *      Lmax, ylens, mem_of, N and blank are em_ctc_seq_nll's, with its layout, its clamping of mem_of and its alpha.
+ *   Per candidate n, with em_ctc_seq_nll's states, lab, lp and alpha:
+ *      beta[T_b-1][S-1] = lp[T_b-1][blank], beta[T_b-1][S-2] = lp[T_b-1][y[L-1]] (L > 0), every other state -inf;
+ *      beta[t][s] = logsumexp(beta[t+1][s], beta[t+1][s+1], beta[t+1][s+2]) + lp[t][lab[s]], the move by two only for odd
+ *      s <= S-4 with lab[s+2] != lab[s];
+ *      gamma[t][s] = exp(alpha[t][s] + beta[t][s] - lp[t][lab[s]] - log P), P = sum over s of the same product at ONE
+ *      frame (the kernel takes it at the first frame behind the middle on the way up, at the middle frame on the way
+ *      down; the two agree to rounding).
+ *   Outputs, all written for every candidate: nll [N] = em_ctc_seq_nll's value, bit for bit; for the token i < L, state
+ *      2i + 1: occ [N][Lmax] = sum over t of gamma (the expected number of frames of the token), peak [N][Lmax] = max over
+ *      t of gamma (the token's confidence), peak_t [N][Lmax] = the frame of that maximum, of equal values the lowest;
+ *      blank_post [N][T] (NULL: not wanted) = per frame the sum of gamma over the even states, 0 for t >= T_b.  Entries
+ *      i >= L read 0.
+ *   All f32; every logsumexp is shifted by its largest term, and terms of -inf (all of them too) give -inf, never NaN.
+ *   A candidate that admits no path (T_b < L + number of adjacent equal tokens, or T_b == 0) is a defined result:
+ *      nll = +inf, occ = peak = 0, peak_t = -1, blank_post = 0.  A row's values depend on its own transcript and its
+ *      utterance's columns and on nothing else (bit for bit, whatever N, Lmax and the companions are).
+ *   Transcripts up to Lmax = em_ctc_forced_align_max_tokens() (4 095) tokens; above: EM_ERR_UNSUPPORTED.  ws:
+ *   em_ctc_seq_posteriors_workspace_bytes(N, T, Lmax) bytes of device memory, 16-byte aligned (two half trellises of f32
+ *   rows per candidate); NULL or a smaller one: EM_ERR_UNSUPPORTED, nothing is launched.  What ws holds on entry is
+ *   ignored.  Any T, any N.  Enqueue only.                                                                              */
+int em_ctc_seq_posteriors(const float* lpT, int32_t ldT, const int32_t* xlens, int32_t Bm, int32_t T, const int32_t* targets,
+                          int32_t Lmax, const int32_t* ylens, const int32_t* mem_of, int32_t N, int32_t blank, float* nll,
+                          float* occ, float* peak, int32_t* peak_t, float* blank_post, void* ws, size_t ws_bytes,
+                          void* stream);
+size_t em_ctc_seq_posteriors_workspace_bytes(int32_t N, int32_t T, int32_t Lmax);
+
 /* ---- time-synchronous CTC prefix beam search with n-gram fusion (csrc/ctc_tsync.hip): BeamSearchTimeSync of
  *      espnet/nets/beam_search_timesync.py (Speech2Text(time_sync=True)) for ctc_weight = 1, with the n-gram scorer of
  *      em_ngram_score as an extension.  Two launches, nothing read back in between; all pointers on the device.
