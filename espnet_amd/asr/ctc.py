@@ -364,12 +364,16 @@ class CTC(PackedModule):
         return self.nll_device(act, host[0], host[1], host[2], int(blank_idx))
 
     # ------------------------------------------------------------------ token posteriors (csrc/ctc_post.hip)
-    def posteriors_device(self, enc_act: torch.Tensor, olens, targets, ylens, blank: int, mem_of=None, blank_post: bool = False):
+    def posteriors_device(self, enc_act: torch.Tensor, olens, targets, ylens, blank: int, mem_of=None, blank_post: bool = False,
+                          renorm: bool = False):
         """The forward-backward occupancies of N candidate transcripts, reduced per token, by `em_ctc_log_probs_t` ->
         `em_ctc_seq_posteriors` (include/espnet_amd.h states the recursion and the outputs); only enqueues work.  The
         arguments, their two forms (HOST data is checked first: ValueError before any launch; int32 DEVICE tensors are
         taken as they are) and the meaning of mem_of are `nll_device`'s.  Returns device tensors (nll (N,) f32, occ
-        (N, Lmax) f32, peak (N, Lmax) f32, peak_t (N, Lmax) i32) and, with blank_post=True, blank_post (N, T) f32."""
+        (N, Lmax) f32, peak (N, Lmax) f32, peak_t (N, Lmax) i32) and, with blank_post=True, blank_post (N, T) f32.
+        renorm=True takes `em_ctc_seq_posteriors_renorm` (csrc/ctc_post_renorm.hip): alpha and beta renormalised as the
+        walks go, so the error of the posteriors does not grow with |nll|.  Use it for long recordings, or whenever |nll|
+        is in the thousands; its nll agrees with the default's to rounding, not bit for bit."""
         L.require_gpu(enc_act, "enc_act")
         Bm, T, _ = enc_act.shape
         olens_d, tg_d, ylens_d, mo_d, N, Lmax = self._trellis_inputs(enc_act, olens, targets, ylens, blank, mem_of, align=False)
@@ -378,36 +382,40 @@ class CTC(PackedModule):
         if mo_d is None and N != Bm:
             raise ValueError(f"{N} transcripts for {Bm} utterances need mem_of")
         return self.posteriors_log_probs_t(self.log_probs_t_device(enc_act), Bm * T, olens_d, Bm, T, tg_d, Lmax, ylens_d, mo_d, N,
-                                           blank, blank_post=blank_post)
+                                           blank, blank_post=blank_post, renorm=renorm)
 
     @staticmethod
-    def posteriors_log_probs_t(lpT, ldT, olens_d, Bm, T, tg_d, Lmax, ylens_d, mem_of_d, N, blank, blank_post=False, ws=None):
+    def posteriors_log_probs_t(lpT, ldT, olens_d, Bm, T, tg_d, Lmax, ylens_d, mem_of_d, N, blank, blank_post=False, ws=None,
+                               renorm: bool = False):
         """`em_ctc_seq_posteriors` on given transposed log-posteriors lpT [V][ldT] (device tensors throughout; tg_d's row
-        stride is Lmax, or 1 when Lmax == 0).  `ws`: a uint8 device tensor to use as the workspace."""
+        stride is Lmax, or 1 when Lmax == 0).  `ws`: a uint8 device tensor to use as the workspace.  renorm=True:
+        `em_ctc_seq_posteriors_renorm` and its workspace size (long recordings, |nll| in the thousands)."""
         lib, dev = L.load(), lpT.device
+        name = "em_ctc_seq_posteriors_renorm" if renorm else "em_ctc_seq_posteriors"
         if ws is None:
-            ws = torch.empty(max(int(lib.em_ctc_seq_posteriors_workspace_bytes(N, T, Lmax)), 16), dtype=torch.uint8, device=dev)
+            ws = torch.empty(max(int(getattr(lib, name + "_workspace_bytes")(N, T, Lmax)), 16), dtype=torch.uint8, device=dev)
         Lp = max(Lmax, 1)
         nll = torch.empty(N, dtype=torch.float32, device=dev)
         occ = torch.empty(N, Lp, dtype=torch.float32, device=dev)
         peak = torch.empty(N, Lp, dtype=torch.float32, device=dev)
         peak_t = torch.empty(N, Lp, dtype=torch.int32, device=dev)
         bp = torch.empty(N, T, dtype=torch.float32, device=dev) if blank_post else None
-        L.check(lib.em_ctc_seq_posteriors(L.ptr(lpT), ldT, L.ptr(olens_d), Bm, T, L.ptr(tg_d), Lmax, L.ptr(ylens_d),
-                                          L.ptr(mem_of_d), N, blank, L.ptr(nll), L.ptr(occ), L.ptr(peak), L.ptr(peak_t),
-                                          L.ptr(bp), L.ptr(ws), ws.numel(), L.current_stream_ptr()), "em_ctc_seq_posteriors")
+        L.check(getattr(lib, name)(L.ptr(lpT), ldT, L.ptr(olens_d), Bm, T, L.ptr(tg_d), Lmax, L.ptr(ylens_d),
+                                   L.ptr(mem_of_d), N, blank, L.ptr(nll), L.ptr(occ), L.ptr(peak), L.ptr(peak_t),
+                                   L.ptr(bp), L.ptr(ws), ws.numel(), L.current_stream_ptr()), name)
         outs = (nll, occ[:, :Lmax], peak[:, :Lmax], peak_t[:, :Lmax])
         return outs + (bp,) if blank_post else outs
 
-    def token_posteriors(self, hs_pad: torch.Tensor, hlens, ys_pad, ys_lens, blank_idx: int = 0):
+    def token_posteriors(self, hs_pad: torch.Tensor, hlens, ys_pad, ys_lens, blank_idx: int = 0, renorm: bool = False):
         """Per-token posteriors of one transcript per utterance: hs_pad (B,T,d) encoder output on the device, hlens (B,),
         ys_pad (B,Lmax) target ids, ys_lens (B,) -> (nll (B,), occupancy (B,Lmax), confidence (B,Lmax), peak_frame
         (B,Lmax) i32) on the device: the expected number of frames of each token, its largest state occupancy over the
         frames and the frame of it.  Entries behind ys_lens read 0; a transcript the frames cannot carry has nll = +inf,
-        zeros and peak_frame -1.  Ids equal to the blank or outside [0, V) raise ValueError."""
+        zeros and peak_frame -1.  Ids equal to the blank or outside [0, V) raise ValueError.  renorm=True: the
+        renormalised kernel of `posteriors_device`, for long recordings or whenever |nll| is in the thousands."""
         act = self._to_act(hs_pad)
         host = [x.cpu() if torch.is_tensor(x) else x for x in (hlens, ys_pad, ys_lens)]
-        return self.posteriors_device(act, host[0], host[1], host[2], int(blank_idx))
+        return self.posteriors_device(act, host[0], host[1], host[2], int(blank_idx), renorm=renorm)
 
     @staticmethod
     def _token_outputs(B, T, dev, out):

@@ -598,7 +598,7 @@ class Speech2Text:
 
     # ------------------------------------------------------------------ token confidences under the CTC head
     @torch.no_grad()
-    def batch_confidence(self, speech: torch.Tensor, speech_lengths: Sequence[int], texts=None):
+    def batch_confidence(self, speech: torch.Tensor, speech_lengths: Sequence[int], texts=None, renorm: bool = False):
         """How sure the CTC head is of every token of given transcripts: the forward-backward posteriors of
         `CTC.posteriors_device` (csrc/ctc_post.hip), all paths of the transcript, where `batch_align` sees the best one.
         speech, speech_lengths and texts as `batch_nll` takes them - texts[b] one transcript or an n-best list of utterance
@@ -608,7 +608,9 @@ class Speech2Text:
         over the frames, the expected number of its frames and the time of the most occupied frame (frame index x
         `seconds_per_frame`, -1.0 where there is none); -log p_ctc(y|x), inf for a transcript the frames cannot carry
         (its confidences and occupancies are 0).  Needs only frontend, encoder and CTC head.  The candidates go through
-        in slices of `nll_rows_per_call` and share their utterance's log-probabilities; one D2H copy for the results."""
+        in slices of `nll_rows_per_call` and share their utterance's log-probabilities; one D2H copy for the results.
+        renorm=True scores with the renormalised kernel (csrc/ctc_post_renorm.hip), whose error does not grow with |nll|:
+        for long recordings, or whenever nll is in the thousands."""
         m = self.asr_model
         self._need_ctc_head()
         cb = None if texts is None else self._candidates(speech, texts)
@@ -624,7 +626,7 @@ class Speech2Text:
 
         def score(st, olens, sl):
             nll, occ, peak, peak_t = m.ctc.posteriors_device(st.enc_act[sl.u0 : sl.u1].contiguous(), st.olens[sl.u0 : sl.u1],
-                                                             sl.ids, sl.ylens, m.blank_id, mem_of=sl.mem_rel)
+                                                             sl.ids, sl.ylens, m.blank_id, mem_of=sl.mem_rel, renorm=renorm)
             cols = [torch.nn.functional.pad(c.to(torch.float32), (0, W - c.shape[1])) for c in (peak, occ, peak_t)]
             return torch.cat([nll[:, None]] + cols, dim=1)
 

@@ -27,11 +27,12 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc",
 # transducer_stream.hip: the records' merges must give one result per row whatever the tile; scalar f32 forms only.
 # frontend_mr.hip: the butterflies' complex arithmetic as scalar f32 operations, one rounding each.
 # ctc_post.hip: the cells of both directions are ctc_nll.hip's scalar f32 chain; the merged sums likewise.
+# ctc_post_renorm.hip: the same cells; its three forms must give a candidate the same bits.
 _NO_PACKED_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 EXTRA_FLAGS = {"block.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
                "ngram_seq.hip": _NO_PACKED_F32, "rnn_lm_seq.hip": _NO_PACKED_F32,
                "transducer_stream.hip": _NO_PACKED_F32, "frontend_mr.hip": _NO_PACKED_F32,
-               "ctc_post.hip": _NO_PACKED_F32}
+               "ctc_post.hip": _NO_PACKED_F32, "ctc_post_renorm.hip": _NO_PACKED_F32}
 
 
 def _sources():

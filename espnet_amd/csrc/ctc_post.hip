@@ -26,9 +26,7 @@
 // after the walks.
 //
 // hipcc -O3 --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage (ROCm 7.2): see DESIGN.md 4ac.
-#include <cfloat>
-
-#include "ctc_trellis.h"
+#include "ctc_post_common.h"
 
 namespace {
 
@@ -37,7 +35,7 @@ using ctc_trellis::lse3;
 using ctc_trellis::MAX_WAVES;
 using ctc_trellis::NINF;
 using ctc_trellis::SPL;
-constexpr int CP_DUAL_WAVES = 8;  // waves per direction up to which both directions share a workgroup (1 024 threads)
+using namespace ctc_post_common;  // CP_DUAL_WAVES, the row geometry, lse_merge, TokAcc
 // frames a stored row is loaded ahead of its use: what the registers allow (128 per lane in a 1 024-thread workgroup)
 template <bool MULTI>
 constexpr int CP_RING = MULTI ? 1 : 3;
@@ -51,26 +49,10 @@ struct PostArgs {
   float* ws;
 };
 
-static inline int row_states(int Lmax) { return (2 * Lmax + 1 + 7) & ~7; }
-static inline int ws_rows(int T) { return (T + 1) / 2 + 1; }
 // floats per candidate: the rows of both directions, then blank_post's parts [T][waves] (more waves than one), 16-byte whole
 __host__ __device__ static inline size_t ws_floats_per_cand(int R, int RS, int T, int nw) {
   return (size_t)2 * R * RS + (nw > 1 ? ((size_t)T * nw + 3) & ~(size_t)3 : 0);
 }
-
-// (m, s): a sum s * 2^m of terms kept relative to their maximum m; merging is symmetric, so a butterfly gives every
-// lane the same bits, and a part (-inf, 0) changes nothing
-__device__ __forceinline__ void lse_merge(float& m, float& s, float mo, float so) {
-  const float mm = fmaxf(m, mo), sh = fmaxf(mm, -FLT_MAX);
-  s = s * __builtin_amdgcn_exp2f(m - sh) + so * __builtin_amdgcn_exp2f(mo - sh);
-  m = mm;
-}
-
-// what a direction keeps per token of the lane
-struct TokAcc {
-  float occ[4], peak[4];
-  int pt[4];
-};
 
 // The sum-product cell of ctc_nll.hip, with the row's fate behind it.  UP: the alpha direction (frames ascending).
 // A frame of the own half is stored (do_store), at the frame h the groups meet, a frame of the other half is combined

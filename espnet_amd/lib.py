@@ -429,6 +429,9 @@ _SIGNATURES = {
     "em_ctc_seq_posteriors": (C.c_int, [_vp, _i32, _vp, _i32, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp,
                                         _vp, _sz, _vp]),
     "em_ctc_seq_posteriors_workspace_bytes": (_sz, [_i32, _i32, _i32]),
+    "em_ctc_seq_posteriors_renorm": (C.c_int, [_vp, _i32, _vp, _i32, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp,
+                                               _vp, _vp, _sz, _vp]),
+    "em_ctc_seq_posteriors_renorm_workspace_bytes": (_sz, [_i32, _i32, _i32]),
     "em_ctc_frame_topk": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     "em_ctc_tsync_search": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, C.c_float, C.c_float,
                                       C.c_float, C.POINTER(EmNgramModel), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),

@@ -1412,6 +1412,30 @@ int em_ctc_seq_posteriors(const float* lpT, int32_t ldT, const int32_t* xlens, i
                           void* stream);
 size_t em_ctc_seq_posteriors_workspace_bytes(int32_t N, int32_t T, int32_t Lmax);
 
+/* ---- CTC token posteriors, renormalised (csrc/ctc_post_renorm.hip): em_ctc_seq_posteriors for long recordings.  The
+ *      arguments, states, alpha, beta, gamma, outputs, no-path and T_b == 0 results, clamping, mem_of batching, limits,
+ *      argument checks and return codes are the block's above; a row's values depend on its own transcript and its
+ *      utterance's columns and on nothing else, bit for bit.  The differences:
+ *   Offsets.  alpha[t] and beta[t] are held in the base-2 logarithm RELATIVE to integer offsets Aoff[t], Boff[t] (exact
+ *      int32 sums of per-frame shifts; a frame's shift is the rounded maximum, over the states s < S, of the same
+ *      direction's row three frames earlier, clamped to +-8 192 per frame):
+ *      gamma[t][s] = exp2((a + b - e) + (Aoff[t] + Boff[t] - Poff) - P_rel), with a, b the relative rows, e the emission
+ *      and P = 2^(P_rel + Poff) taken as above.  The bracket of offsets is a small exact integer; nothing of magnitude
+ *      |nll| is added to or subtracted from an f32.
+ *   nll [N] is NOT em_ctc_seq_nll's bits: it is -ln 2 * (log2 of the last alpha row's two end states, relative,
+ *      + Aoff[T_b-1]), that one sum formed in double; it agrees with em_ctc_seq_nll's value to rounding.
+ *   Error.  That of occ, peak and blank_post is set by what a row's maximum moves in three frames (their nats, times
+ *      2^-24), not by |nll|: below 2e-4 absolute at 50 nats per frame where em_ctc_seq_posteriors is near 1e-2
+ *      (DESIGN.md 4ad).  Use it for long recordings, or whenever |nll| is in the thousands.
+ *   ws: em_ctc_seq_posteriors_renorm_workspace_bytes(N, T, Lmax) bytes (the rows and one int32 offset per row), 16-byte
+ *      aligned; 0 for shapes outside the limits.  What ws holds on entry is ignored.  Any T, any N (the offsets
+ *      are int32: |nll| below 1e9 nats).  Enqueue only.                                                                 */
+int em_ctc_seq_posteriors_renorm(const float* lpT, int32_t ldT, const int32_t* xlens, int32_t Bm, int32_t T,
+                                 const int32_t* targets, int32_t Lmax, const int32_t* ylens, const int32_t* mem_of, int32_t N,
+                                 int32_t blank, float* nll, float* occ, float* peak, int32_t* peak_t, float* blank_post,
+                                 void* ws, size_t ws_bytes, void* stream);
+size_t em_ctc_seq_posteriors_renorm_workspace_bytes(int32_t N, int32_t T, int32_t Lmax);
+
 /* ---- time-synchronous CTC prefix beam search with n-gram fusion (csrc/ctc_tsync.hip): BeamSearchTimeSync of
  *      espnet/nets/beam_search_timesync.py (Speech2Text(time_sync=True)) for ctc_weight = 1, with the n-gram scorer of
  *      em_ngram_score as an extension.  Two launches, nothing read back in between; all pointers on the device.

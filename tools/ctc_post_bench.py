@@ -1,4 +1,5 @@
-"""CTC token posteriors on the device (csrc/ctc_post.hip): forward-backward for a ragged batch of candidates.
+"""CTC token posteriors on the device (csrc/ctc_post.hip, csrc/ctc_post_renorm.hip): forward-backward for a ragged batch
+of candidates, as f32 logarithms and renormalised.
 
     python tools/ctc_post_bench.py [--reps 20] [--warmup 3] [--out profiles/ctc_post_bench.json]
 
@@ -9,9 +10,11 @@ by the wall clock, one run):
   * long form: 1 x (T 15 000, L 3 000), V 5 000 (S above 4 096: the three-walk form of the kernel).
 Per shape:
   * post_ms     em_ctc_seq_posteriors alone on ready lpT, outputs and workspace allocated once per call of the wrapper;
+  * renorm_ms   em_ctc_seq_posteriors_renorm on the same inputs, timed the same way;
   * alpha_ms    em_ctc_seq_nll on the same inputs: the alpha pass alone;
   * host_ms     D2H of the utterances' (T, V) log-probs + the float64 NumPy forward-backward (tests/ctc_post_ref.py).
-The device's occ and peak are compared with the host route before anything is timed; the largest error is reported.
+Beside every device leg stands what its result is worth: the largest absolute error of occ, peak and blank_post against
+the float64 pass (`max_abs_err`), taken before anything is timed.
 """
 import argparse
 import json
@@ -35,7 +38,8 @@ def shape(name, lpT, Bm, T, olens, tg, ylens, mem_of, a):
     N, Lm = len(ylens), int(tg.shape[1])
     i32 = lambda v: torch.as_tensor(v, dtype=torch.int32).cuda()  # noqa: E731
     ol_d, yl_d, mo_d, tg_d = i32(olens), i32(ylens), i32(mem_of), tg.to(torch.int32).cuda()
-    post = lambda: CTC.posteriors_log_probs_t(lpT, Bm * T, ol_d, Bm, T, tg_d, Lm, yl_d, mo_d, N, 0)  # noqa: E731
+    post = lambda **kw: CTC.posteriors_log_probs_t(lpT, Bm * T, ol_d, Bm, T, tg_d, Lm, yl_d, mo_d, N, 0, **kw)  # noqa: E731
+    renorm = lambda **kw: post(renorm=True, **kw)  # noqa: E731
     alpha = lambda: CTC.nll_log_probs_t(lpT, Bm * T, ol_d, Bm, T, tg_d, Lm, yl_d, mo_d, N, 0)  # noqa: E731
 
     def host():
@@ -45,20 +49,30 @@ def shape(name, lpT, Bm, T, olens, tg, ylens, mem_of, a):
     t0 = time.perf_counter()
     want = host()
     host_ms = (time.perf_counter() - t0) * 1e3
-    nll, occ, peak, _ = [o.cpu().numpy() for o in post()]
-    err = max(max(float(np.abs((occ[n, : ylens[n]] - w[2]) / np.maximum(w[2], 1.0)).max()), float(np.abs(peak[n, : ylens[n]] - w[3]).max()))
-              for n, w in enumerate(want))
-    # (reported, not a threshold: alpha and beta are f32 logarithms of magnitude |nll|, and these flat synthetic posteriors
-    # cost ~8 nats per frame - at |nll| ~ 1e5 the f32 trellis resolves gamma no longer)
-    if not np.isfinite(nll).all() or not np.isfinite(occ).all():
-        raise SystemExit(f"ctc_post_bench: {name}: a value that is not finite")
-    r = dict(candidates=N, Lmax=Lm, utterances=Bm, T=T, mean_nll=round(float(nll.mean()), 2), max_err_vs_float64=err,
-             workspace_bytes=int(EL.load().em_ctc_seq_posteriors_workspace_bytes(N, T, Lm)),
+
+    def worth(route):
+        """Largest absolute error of occ, peak and blank_post of a device route against float64."""
+        nll, occ, peak, _, bp = [o.cpu().numpy() for o in route(blank_post=True)]
+        if not np.isfinite(nll).all() or not np.isfinite(occ).all():
+            raise SystemExit(f"ctc_post_bench: {name}: a value that is not finite")
+        err = max(max(float(np.abs(occ[n, : ylens[n]] - w[2]).max()), float(np.abs(peak[n, : ylens[n]] - w[3]).max()),
+                      float(np.abs(bp[n, : len(w[5])] - w[5]).max())) for n, w in enumerate(want))
+        return float(nll.mean()), err
+
+    # (reported, not a threshold: the plain route's alpha and beta are f32 logarithms of magnitude |nll|, and these flat
+    # synthetic posteriors cost ~8 nats per frame - at |nll| ~ 1e5 it resolves gamma no longer; DESIGN.md 4ac, 4ad)
+    (mean_nll, err), (_, err_rn) = worth(post), worth(renorm)
+    lib = EL.load()
+    r = dict(candidates=N, Lmax=Lm, utterances=Bm, T=T, mean_nll=round(mean_nll, 2), max_abs_err=dict(post=err, renorm=err_rn),
+             workspace_bytes=int(lib.em_ctc_seq_posteriors_workspace_bytes(N, T, Lm)),
+             renorm_workspace_bytes=int(lib.em_ctc_seq_posteriors_renorm_workspace_bytes(N, T, Lm)),
              log_probs_bytes=int(lpT.numel()) * 4)
     r["post_ms"] = timed(post, a.reps, a.warmup)
+    r["renorm_ms"] = timed(renorm, a.reps, a.warmup)
     r["alpha_ms"] = timed(alpha, a.reps, a.warmup)
     r["host_ms"] = round(host_ms, 1)
     r["post_over_alpha"] = round(r["post_ms"]["median"] / r["alpha_ms"]["median"], 2)
+    r["renorm_over_post"] = round(r["renorm_ms"]["median"] / r["post_ms"]["median"], 2)
     print(f"[ctc_post_bench] {name}: {json.dumps(r)}", flush=True)
     return r
 
